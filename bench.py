@@ -6,18 +6,21 @@ stand-in returning the HBM-resident cached box features -> graph head -> classif
 Inputs are resident in HBM before the timed region.  N GPUs = N independent shards of images (no data-path
 collective: images are independent); value = N * B * K / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints ONE JSON line (rank 0) with the contract
+fields (metric, value, unit, ms_per_step, higher_is_better, dtype, ...).  --dump-outputs DIR also writes what the last
+timed step returned to the caller as DIR/<name>.npy (float32; rank 0).  --full adds everything else, in the same run:
   roofline     : dominant kernel (the fp32-MFMA GEMM) algorithmic FLOP/s from HIP-event timings of every launch
   cpu_baseline : the CPU oracle (faithful restatement of the reference head, oracle/skg_oracle.py) timed on this
                  box's host cores on a bounded sample (rank 0, N=1 only)
-and, at N=1, extra legs of the same run: two_stream_chunks (the engine's default stream setting; the timed region itself
+and, at N=1, extra legs of the same run (--full only): two_stream_chunks (the engine's default stream setting; the timed region itself
 runs the chunks on one stream so that the per-launch HIP-event durations of the roofline record are those of un-shared
 launches), fp16x2 (the opt-in split-operand GEMM path, own roofline), b1_latency_ms / b4_latency_ms (the reference
 evaluates one image per forward), train (the batch-4 training step: forward + backward + AdamW, fp32 and bf16 operands).
-The headline value / dtype / roofline are the exact fp32 path (precision="fp32", the head's default).
+The headline value / dtype / roofline are the exact fp32 path (precision="fp32", the head's default).  At N > 1, --full
+adds the data-parallel training leg (every rank).
 """
 import argparse
 import json
@@ -563,7 +566,7 @@ def dry_run(args, rank, world):
                dist=dist_info(world))
     leg = os.environ.get("SKG_BENCH_DRY_TRAIN_LEG")           # test hook: rehearse the N > 1 training leg's guard --
     clean = True                                              # "ok" | "raise:<rank>" | "hang:<rank>"
-    if leg and world > 1:
+    if leg and world > 1 and args.full:
         guard = LegGuard(rank, world, out, float(os.environ.get("SKG_BENCH_TRAIN_DEADLINE", "300")),
                          evidence=lambda: dict(route="dry run", stages_issued=0, collectives_issued=0))
         kind, _, who = leg.partition(":")
@@ -759,22 +762,52 @@ def release_plans(head):
         eng._small = None
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(results, out_dir, seed=0):
+    """Writes the result dicts of one eval forward (what a caller of the head receives) as out_dir/<key>.npy, float32:
+    every key's per-image tensors concatenated along dim 0 in image order, plus image_index.npy (which images of the batch
+    are in the dump) and rows_<key>.npy (each image's row count).  If all images do not fit in DUMP_BUDGET_BYTES, a fixed
+    seeded sample of whole images does.  Returns the list of files written."""
+    per_image = [{k: v.detach().float().cpu().numpy() for k, v in r.items()} for r in results]
+    sizes = np.array([sum(a.size * 4 for a in d.values()) for d in per_image])
+    keep = np.arange(len(per_image))
+    if sizes.sum() > DUMP_BUDGET_BYTES:
+        order = np.random.RandomState(seed).permutation(len(per_image))
+        n = int(np.searchsorted(np.cumsum(sizes[order]), DUMP_BUDGET_BYTES, side="right"))
+        keep = np.sort(order[:n])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = OrderedDict(image_index=keep.astype(np.float32))
+    for k in per_image[0]:
+        parts = [np.asarray(per_image[i][k], np.float32) for i in keep]
+        axis = 1 if k == "prior" else 0                          # prior is [2, n]: pairs along dim 1
+        arrays[k] = np.concatenate(parts, axis=axis) if parts else np.zeros(0, np.float32)
+        arrays["rows_" + k] = np.array([p.shape[axis] for p in parts], np.float32)
+    written = []
+    for k, a in arrays.items():
+        path = os.path.join(out_dir, k + ".npy")
+        np.save(path, a)
+        written.append(path)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--chunk", type=int, default=0, help="override HeadEngine.chunk_images")
     ap.add_argument("--streams", type=int, default=0, help="override HeadEngine.n_streams")
-    ap.add_argument("--no-gemm-timer", action="store_true", help="skip the per-launch HIP-event GEMM timing")
-    ap.add_argument("--gemm-table", action="store_true", help="per-shape GEMM timing table on stderr")
+    ap.add_argument("--no-gemm-timer", action="store_true", help="with --full: skip the per-launch HIP-event GEMM timing")
+    ap.add_argument("--gemm-table", action="store_true", help="with --full: per-shape GEMM timing table on stderr")
     ap.add_argument("--precision", choices=["fp16x2", "fp32", "bf16"], default=None,
                     help="dense-layer path of the HEADLINE leg.  infer: fp32 (default; exact fp32 MFMA, the reference's "
                          "arithmetic) or fp16x2 (opt-in split operands on the fp16 MFMA).  train: fp32 (default) or bf16")
     ap.add_argument("--no-legs", action="store_true",
-                    help="headline only: skip the extra legs (fp16x2, small-batch latency, training step)")
+                    help="with --full: skip the extra legs (fp16x2, small-batch latency, training step)")
     ap.add_argument("--b1-stream", action="store_true", help="only the single-image shape-stream leg (prints its record)")
     ap.add_argument("--b4-validate", action="store_true", help="only the batch-4 validation-stream leg (prints its record)")
     ap.add_argument("--mode", choices=["infer", "train"], default="infer",
@@ -788,7 +821,14 @@ def main():
                     help="launcher rehearsal on a box without a GPU: the ranks rendezvous (SKG_BENCH_BACKEND=gloo), run the "
                          "barrier / max-over-ranks / gather plumbing around an empty step and print the line; no head, no "
                          "throughput claim (value is null)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-launch GEMM timing and roofline, the extra legs (two-stream "
+                         "chunks, fp16x2, small batches, training steps), the N > 1 training leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- `bench.py --gpus N` launches its N ranks itself (the reference does: mp.spawn(main, nprocs=world_size),
     # configures/hicodet/adamixer_transH_spatial_r50_main.py:175-179).  Nothing in this process has touched the GPU yet.
@@ -853,9 +893,13 @@ def main():
     default_streams = head.engine().n_streams
     head.engine().n_streams = args.streams or 1
 
+    last = []
+
     def step():
         with torch.no_grad():
-            return head(feats, dets, shapes)
+            res = head(feats, dets, shapes)
+        last[:] = [res]                         # (--dump-outputs writes what the last timed step returned)
+        return res
 
     def barrier():
         torch.cuda.synchronize()
@@ -865,7 +909,7 @@ def main():
 
     traffic_table = {}
     tpath = os.path.join(ROOT, "profiles", "traffic.json")     # HBM bytes per launch from the rocprofv3 --pmc passes
-    if os.path.isfile(tpath):
+    if args.full and os.path.isfile(tpath):
         try:
             traffic_table = json.load(open(tpath))
         except Exception:
@@ -876,9 +920,14 @@ def main():
     for _ in range(args.warmup):
         res = step()
     assert len(res) == args.batch and res[0]["boxes_h"].shape == (N_H * (N_H + N_O - 1), 4)
-    elapsed, timer = timed_infer(step, barrier, args.steps, not args.no_gemm_timer)
+    # a plain run times the steps alone; --full puts HIP events around the dominant kernel's launches
+    gemm_timer = args.full and not args.no_gemm_timer
+    elapsed, timer = timed_infer(step, barrier, args.steps, gemm_timer)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0], args.dump_outputs)
+    last.clear()
     timer_all = []
-    if not args.no_gemm_timer:          # every GEMM launch of ONE extra, untimed step: the all-GEMM figures and the table
+    if gemm_timer:                      # every GEMM launch of ONE extra, untimed step: the all-GEMM figures and the table
         engine.GEMM_TIMER = timer_all
         step()
         torch.cuda.synchronize()
@@ -888,6 +937,25 @@ def main():
     elapsed = skd.max_over_ranks(elapsed, device=device)
     total_images = sum(skd.gather_counts(args.batch * args.steps, device=device))
     value = total_images / elapsed
+    split = head.precision == "fp16x2"
+    out = OrderedDict(metric="images/sec through interaction head (20x20 pairs)", value=round(value, 2),
+                      unit="images/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
+                      ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling="weak",
+                      vs_baseline=None,
+                      dtype="f32 (fp16x2 split operands, fp32 accumulate)" if split else "f32", data="synthetic",
+                      config=dict(precision=head.precision, workload="HICO-DET-shaped synthetic cached detections: 20 humans x 20 objects per "
+                                           "image (G=800 grid rows, P=780 pairs, K=117 verbs), eval forward of "
+                                           "InteractionHead from cached AdaMixer-R50 box features [40,256,7,7]/image",
+                                  batch_per_gpu=args.batch, images_per_step=args.batch * world,
+                                  parallelism="dp%d (independent image shards, no data-path collective)" % world),
+                      dist=dist_info(world))
+    if not args.full:
+        out["runtime"] = runtime_info()
+        if rank == 0:
+            print(json.dumps(out))
+        if dist_on:
+            dist.destroy_process_group()
+        return
 
     t_all = sum(e0.elapsed_time(e1) * 1e-3 for e0, e1, *_ in timer_all) or 1e-9
     f_all = sum(2.0 * M * N * K for _, _, M, N, K, _ in timer_all)
@@ -916,19 +984,8 @@ def main():
                                                  if traffic and n_dom else None),
                            note="compulsory = 2.47 MB per image (pooled features + TransH tables + outputs, SURVEY 8d); "
                                 "dominant kernel = HBM bytes per launch (traffic_source) / measured launch time")
-
-    split = head.precision == "fp16x2"
-    out = OrderedDict(metric="images/sec through interaction head (20x20 pairs)", value=round(value, 2),
-                      unit="images/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
-                      ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling="weak",
-                      vs_baseline=None,
-                      dtype="f32 (fp16x2 split operands, fp32 accumulate)" if split else "f32", data="synthetic",
-                      config=dict(precision=head.precision, workload="HICO-DET-shaped synthetic cached detections: 20 humans x 20 objects per "
-                                           "image (G=800 grid rows, P=780 pairs, K=117 verbs), eval forward of "
-                                           "InteractionHead from cached AdaMixer-R50 box features [40,256,7,7]/image",
-                                  batch_per_gpu=args.batch, images_per_step=args.batch * world,
-                                  parallelism="dp%d (independent image shards, no data-path collective)" % world),
-                      roofline=roofline, dist=dist_info(world))
+    out["roofline"] = roofline
+    out.move_to_end("dist")
 
     # ---- extra legs, same run, one GPU only (the N-GPU runs of the scaling curve stay headline-only)
     if world == 1 and not args.no_legs:

@@ -4,6 +4,7 @@ Runs the reference's own, unmodified interaction head (imported from /root/refer
 on the seeded cases of tests/cases.py and stores its OUTPUTS (and the TransH tables it drew, so fixtures do not depend
 on the torch RNG of the box that replays them).  Inputs and weights are regenerated from seeds (skghoi_amd/synth.py),
 never stored.  Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [case ...]
+`--facts` records tests/golden/reference_facts.json instead (see record_reference_facts).
 """
 import os
 import sys
@@ -159,5 +160,59 @@ def main(names):
         print("%-12s %4d arrays  %8.1f KB" % (name, len(flat), os.path.getsize(path) / 1024))
 
 
+FACT_CASES = ("tiny", "ragged3", "train_tiny")
+
+
+def record_reference_facts():
+    """tests/golden/reference_facts.json: what the tests that pin the package against the reference itself compare with,
+    recorded from the live reference so that they run without it -- the head's state_dict keys and shapes, its child
+    order, the HICO-DET tables of hicodet/hico_text_label.py (parsed as data, never executed), and for FACT_CASES the
+    digest of the inputs the reference ran on and of the fixture it reproduced (checked equal here before recording)."""
+    import ast
+    import json
+    import helpers
+    from skghoi_amd import synth
+    head = ref_import.build_reference_head(117, 49, synth.hico_object_to_verb(), 256, 7, 15, 15)
+    facts = dict(state_dict=[[k, list(v.shape)] for k, v in head.state_dict().items()],
+                 children=[n for n, _ in head.named_children()],
+                 graph_head_children=[n for n, _ in head.box_pair_head.named_children()])
+    tables = {}
+    src = os.path.join(ref_import.REF_ROOT, "hicodet", "hico_text_label.py")
+    for node in ast.parse(open(src).read()).body:
+        if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name):
+            try:
+                tables[node.targets[0].id] = ast.literal_eval(node.value)
+            except Exception:
+                pass
+    facts["hico_text_label_keys"] = [list(k) for k in tables["hico_text_label"].keys()]
+    facts["hico_action_valid_object_list"] = {str(o): sorted(v) for o, v in tables["hico_action_valid_object_list"].items()}
+    facts["hico_obj_classes"] = list(tables["hico_obj_classes"])
+    facts["hico_action_classes"] = list(tables["hico_action_classes"])
+    facts["cases"] = {}
+    for name in FACT_CASES:
+        case = cases.build_case(name)
+        live = run_reference(case)
+        g = helpers.load_golden(name)
+        assert sorted(live) == sorted(g), name
+        for k in g:
+            assert np.array_equal(live[k], g[k], equal_nan=True), "fixture stale: %s %s" % (name, k)
+        facts["cases"][name] = dict(inputs_sha256=helpers.content_digest(case), fixture_sha256=helpers.content_digest(g))
+    case = cases.build_case("skips_raise")
+    try:
+        run_reference(case)
+        raised = None
+    except Exception as e:                               # noqa: BLE001
+        raised = type(e).__name__
+    facts["cases"]["skips_raise"] = dict(inputs_sha256=helpers.content_digest(case), raises=raised)
+    path = os.path.join(OUT, "reference_facts.json")
+    with open(path, "w") as f:
+        json.dump(facts, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("reference_facts.json  %8.1f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1:] or cases.ALL_CASES)
+    if sys.argv[1:] == ["--facts"]:
+        record_reference_facts()
+    else:
+        main(sys.argv[1:] or cases.ALL_CASES)

@@ -15,6 +15,44 @@ def load_golden(name):
     return dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
 
 
+def load_reference_facts():
+    """What the reference itself yielded, recorded by tests/golden/make_golden.py --facts (module structure, the HICO-DET
+    tables of its hico_text_label.py, digests of the cases it ran and of the fixtures it produced)."""
+    import json
+    return json.load(open(os.path.join(GOLDEN_DIR, "reference_facts.json")))
+
+
+def content_digest(obj):
+    """sha256 over a nested structure of tensors / arrays / dicts / lists / scalars: values, dtypes, shapes and keys.
+    NaNs hash alike whatever their bit pattern (the fixtures are compared with equal_nan)."""
+    import hashlib
+    h = hashlib.sha256()
+
+    def walk(x):
+        if torch.is_tensor(x):
+            x = x.detach().cpu().numpy()
+        if isinstance(x, np.ndarray):
+            a = np.ascontiguousarray(x)
+            if a.dtype.kind == "f":
+                a = np.where(np.isnan(a), np.array(np.nan, a.dtype), a)
+            h.update(("nd%s%s" % (a.dtype.str, a.shape)).encode())
+            h.update(a.tobytes())
+        elif isinstance(x, dict):
+            h.update(b"{")
+            for k in sorted(x, key=str):
+                h.update(repr(k).encode()); walk(x[k])
+            h.update(b"}")
+        elif isinstance(x, (list, tuple)):
+            h.update(b"[")
+            for v in x:
+                walk(v)
+            h.update(b"]")
+        else:
+            h.update(repr(x).encode())
+    walk(obj)
+    return h.hexdigest()
+
+
 def golden_tables(g):
     n = int(g["n_tables"])
     out = []

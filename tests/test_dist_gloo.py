@@ -147,7 +147,7 @@ def test_bench_training_leg_guard_exception_is_a_record_and_a_hang_is_an_exit_co
       evidence, and the run's exit code is bench.EXIT_LEG_STUCK -- a hang is not a clean run."""
     import json
     env = {"SKG_BENCH_BACKEND": "gloo", "SKG_BENCH_TRAIN_DEADLINE": "4"}
-    args = ["--gpus", "2", "--dry-run", "--steps", "2"]
+    args = ["--gpus", "2", "--dry-run", "--steps", "2", "--full"]              # (the training leg is part of --full)
 
     def line(r):
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -5,9 +5,8 @@ index, which hicodet/hicodet.py:139-153 turns into object_n_verb_to_interaction)
   * known answers from the published HICO-DET class list (no reference needed): the 20 PASCAL-VOC object classes come
     first, the other 60 alphabetically; HOI 1-10 are the airplane classes board .. no_interaction, HOI 600 is zebra
     no_interaction; 600 classes, 80 objects, 117 verbs, `no_interaction` closes every object's block
-  * reference-marked (build container): the committed JSON equals what the reference's file yields, and the object -> verb
-    sets agree with the file's own, independently written hico_action_valid_object_list."""
-import ast
+  * the committed JSON equals what the reference's file yields (its tables, recorded in tests/golden/reference_facts.json),
+    and the object -> verb sets agree with the file's own, independently written hico_action_valid_object_list."""
 import json
 import os
 
@@ -59,20 +58,13 @@ def test_lut_is_the_inverse_of_the_hoi_list():
         assert int(lut[o, v]) == i                                  # hicodet.py:139-153: lut[obj][verb] = hoi index
 
 
-@pytest.mark.reference
 def test_json_equals_reference_file_and_its_valid_object_list():
-    ref = os.path.join(os.environ.get("SKG_REFERENCE_ROOT", "/root/reference"), "hicodet", "hico_text_label.py")
-    tables = {}
-    for node in ast.parse(open(ref).read()).body:                   # parsed as data, never executed
-        if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name):
-            try:
-                tables[node.targets[0].id] = ast.literal_eval(node.value)
-            except Exception:
-                pass
-    keys = [list(k) for k in tables["hico_text_label"].keys()]       # (verb, object) in HOI order
+    import helpers
+    tables = helpers.load_reference_facts()                          # hicodet/hico_text_label.py's tables, recorded
+    keys = tables["hico_text_label_keys"]                            # (verb, object) in HOI order
     t = _table()
     assert t["hoi_verb_object"] == keys
-    valid = tables["hico_action_valid_object_list"]                  # object -> verbs, written out independently
+    valid = {int(o): v for o, v in tables["hico_action_valid_object_list"].items()}   # object -> verbs, written out independently
     assert sorted(valid) == list(range(80))
     for o in range(80):
         assert sorted(valid[o]) == sorted(t["object_to_verb"][o]), o

@@ -9,7 +9,7 @@ export PYTHONPATH=$R
 OUT=$R/gpurun_out/prof_$tag
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/stats --output-format csv -- python3 $R/bench.py --precision $prec --steps 5 --warmup 2 --no-cpu-baseline --no-legs > $OUT/bench_under_rocprof.json 2> $OUT/stats.log || echo "stats pass failed"
+rocprofv3 --kernel-trace --stats -d $OUT/stats --output-format csv -- python3 $R/bench.py --precision $prec --steps 5 --warmup 2 --full --no-cpu-baseline --no-legs > $OUT/bench_under_rocprof.json 2> $OUT/stats.log || echo "stats pass failed"
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$c --output-format csv -- python3 $R/bench.py --precision $prec --steps 2 --warmup 1 --no-cpu-baseline --no-legs --no-gemm-timer > $OUT/pmc_$c.log 2>&1 || echo "$c pass failed"
 done

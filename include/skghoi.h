@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SKG_ABI_VERSION 18
+#define SKG_ABI_VERSION 19
 #define SKG_E_ARG   (-1)   /* null pointer / negative size / unsupported shape            */
 #define SKG_E_ALIGN (-2)   /* pointer or leading dimension not 16-byte aligned            */
 #define SKG_E_LIMIT (-3)   /* exceeds a compiled-in limit (boxes per image, verbs, ...)   */
@@ -228,6 +228,25 @@ int skg_gemm_group_f32(const skg_gemm_desc* descs_host, int n, void* stream);
  * tiles a member may carry split_k > 1 (epilogues BIAS / BIAS_RELU / BIAS_RES_RELU): one more launch then reduces all
  * split members in slice order.  SKG_EPI_RELU_DOT members write 2 * ceil(N / (64 * scale)) dot_partial slabs.       */
 int skg_gemm_group_tile(const skg_gemm_desc* descs_host, int n);
+/* bf16 operands (inference_precision "bf16"): the product of skg_gemm_f32 / skg_gemm_group_f32 with every operand
+ * rounded to bf16 (round to nearest even), fp32 accumulation on v_mfma_f32_32x32x16_bf16; bias, epilogues and C stay fp32.
+ * W is read from w16, the bf16 twin of the fp32 weight with the SAME element indexing (skg_twin_bf16 of the whole fp32
+ * buffer: a column sub-view is the twin's base plus the same element offset): d.ldw % 8 == 0 (else SKG_E_ARG), w16
+ * 16-byte aligned, and each of its N rows readable through element ceil(K / 8) * 8 - 1 (the last row too).  A is the fp32
+ * operand (a_rows gather, any K % 4 == 0), rounded in registers; inf / nan propagate as on the exact loop.  d.w_split
+ * and d.a_exp are treated as NULL (the launch works on a copy with both cleared).  Tile scale and split-K rules as for
+ * the fp32 launches of that copy: skg_gemm_dot_partials / skg_gemm_group_tile give this launch's slab count / tile
+ * scale when queried with w_split = NULL.  Never routed to skg_gemmx_f32.  w16_host: one twin pointer per descriptor. */
+int skg_gemm_b16_f32(const skg_gemm_desc* desc_host, const uint16_t* w16, void* stream);
+int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uint16_t* const* w16_host, int n, void* stream);
+/* Launches per main loop of the skg_gemm_* entry points since the last reset (out_host: SKG_GEMM_PATHS counts, by
+ * SKG_GEMM_PATH_*; reset != 0 zeroes them after the read).  Process-wide, for tests and profiles.                   */
+#define SKG_GEMM_PATH_EXACT  0          /* exact fp32 loops (register-staged, DMA-staged, 64 x 64 latency loops)      */
+#define SKG_GEMM_PATH_FP16X2 1          /* fp16x2 split-operand loop                                                  */
+#define SKG_GEMM_PATH_BF16   2          /* bf16 loop (skg_gemm_b16_f32, skg_gemm_group_b16_f32)                       */
+#define SKG_GEMM_PATH_ROUTED 3          /* mid-size fp32 launches routed to skg_gemmx_f32                             */
+#define SKG_GEMM_PATHS       4
+void skg_gemm_path_counts(int64_t* out_host, int reset);
 /* Tuning switches of the eval GEMM (developer A/B knobs; 0 = the library's default).  They live in a CONTEXT the caller creates
  * (skg_context, below) and apply to the skg_gemm_* calls of the threads that made that context current
  * (skg_ctx_make_current) -- the library keeps no process-wide tuning state.

@@ -12,7 +12,7 @@ MAX_NODES = 160
 SPATIAL_LD = 48
 TRANSH_DIM = 50
 TRANSH_ENT = 80
-ABI_VERSION = 18
+ABI_VERSION = 19
 GEMM_GROUP_MAX = 4
 CHECKSUM_PARTIALS = 1024
 LOSS_CHUNKS = 64
@@ -130,6 +130,9 @@ PROTOTYPES = {
     "skg_split_weights_f16x2": (C.c_int, [_vp, C.c_int, C.c_int, _i64, _f32, _vp, _vp]),
     "skg_gemm_group_f32": (C.c_int, [C.POINTER(GemmDesc), C.c_int, _vp]),
     "skg_gemm_group_tile": (C.c_int, [C.POINTER(GemmDesc), C.c_int]),
+    "skg_gemm_b16_f32": (C.c_int, [C.POINTER(GemmDesc), _vp, _vp]),
+    "skg_gemm_group_b16_f32": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(_vp), C.c_int, _vp]),
+    "skg_gemm_path_counts": (None, [C.POINTER(_i64), C.c_int]),
     "skg_row_exponents_f32": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, _vp]),
     "skg_adamw_f32": (C.c_int, [_vp, C.c_int] + [C.c_double] * 7 + [_vp, C.c_int, _vp]),
     "skg_ctx_set_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),

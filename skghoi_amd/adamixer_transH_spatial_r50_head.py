@@ -313,6 +313,9 @@ class _Ready:
         pass
 
 
+_INFERENCE_PRECISIONS = (None, "fp32", "fp16x2", "bf16")
+
+
 class InteractionHead(Module):
     """Interaction head that constructs and classifies box pairs (HEAD:29-429): same constructor keywords, forward
     signature and result dictionaries.
@@ -326,7 +329,17 @@ class InteractionHead(Module):
           the 1e-4 logit bar, at about twice the speed; tiles that leave the fp16 range or contain inf / nan are
           recomputed exactly (skghoi_amd/csrc/skg_gemm.hip).
         "bf16": TRAINING-mode dense layers with bf16 operands (fp32 accumulation, fp32 master weights / gradients /
-          activations); inference as "fp16x2".  Training otherwise always uses the exact fp32 path.
+          activations); inference as "fp16x2" unless inference_precision says otherwise.  Training otherwise always
+          uses the exact fp32 path.
+      inference_precision: Optional[str] = None -- GEMM path of the target-less eval forward (the batched engine, the
+        captured small-batch plans, prefetch_eval, trainer.test); a plain attribute, not part of state_dict:
+        None (default): by `precision` -- "fp32" -> exact, "fp16x2" and "bf16" -> fp16x2 (bit for bit as before).
+        "fp32" / "fp16x2": that path whatever `precision` says.
+        "bf16": bf16 operands on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16), fp32 accumulation, bias, epilogues
+          and activations -- the contract of torch.autocast(dtype=torch.bfloat16) over nn.Linear.  Logits, scores and
+          weights carry bf16-grade error; index / prediction / object / boxes / prior do not depend on any GEMM and
+          stay bit-identical to the exact path.
+        Training and validation (eval with targets) are not affected.
       reference_quirks: bool = True -- reproduce (a) the node-offset bug on skipped images and (b) the
         eval-mode label-list zip with skipped images in a batch > 1 (HEAD:298-310: truncated results / IndexError).
         With False every image gets its own (possibly empty) result.
@@ -335,7 +348,8 @@ class InteractionHead(Module):
     def __init__(self, box_roi_pool: Module, box_pair_head: Module, box_pair_suppressor: Module,
                  box_pair_predictor: Module, human_idx: int, num_classes: int, box_nms_thresh: float = 0.5,
                  box_score_thresh: float = 0.2, max_human: int = 15, max_object: int = 15,
-                 distributed: bool = False, reference_quirks: bool = True, precision: str = "fp32") -> None:
+                 distributed: bool = False, reference_quirks: bool = True, precision: str = "fp32",
+                 inference_precision: Optional[str] = None) -> None:
         super().__init__()
         self.box_roi_pool = box_roi_pool
         self.box_pair_head = box_pair_head
@@ -352,6 +366,9 @@ class InteractionHead(Module):
         if precision not in ("fp32", "bf16", "fp16x2"):
             raise ValueError("precision must be 'fp32', 'fp16x2' or 'bf16'")
         self.precision = precision
+        if inference_precision not in _INFERENCE_PRECISIONS:
+            raise ValueError("inference_precision must be None, 'fp32', 'fp16x2' or 'bf16'")
+        self.inference_precision = inference_precision
         self.fused_training = True      # False: training through autograd over per-layer Functions (skghoi_amd/train_graph.py)
         self.grad_mode = "autograd"     # "direct": the fused step writes p.grad itself (skghoi_amd/train_fused.py, StepFn)
         self._engine = None
@@ -388,6 +405,10 @@ class InteractionHead(Module):
             self._engine = e
         e.faithful_skip_offset = self.reference_quirks
         e.precision = self.precision
+        ip = getattr(self, "inference_precision", None)
+        if ip not in _INFERENCE_PRECISIONS:
+            raise ValueError("inference_precision must be None, 'fp32', 'fp16x2' or 'bf16'")
+        e.inference_precision = ip
         return e
 
     # ------------------------------------------------------------------------------------------ HEAD:92-151

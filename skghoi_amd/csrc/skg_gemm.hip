@@ -29,6 +29,7 @@
 //     small-M layers.
 #include "skg_common.h"
 #include <string.h>
+#include <atomic>
 #include <type_traits>
 
 // 2^e for e in [-126, 127], exactly
@@ -37,6 +38,15 @@ __device__ __forceinline__ float skg_exp2i(int e) { return __uint_as_float((uint
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));     // 8 bf16 bit patterns: an operand of v_mfma_f32_32x32x16_bf16
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+
+// two floats -> two bf16 in one dword, round to nearest even (a plain conversion: v_cvt_pk_bf16_f32; nan stays nan)
+__device__ __forceinline__ uint32_t skg_pack_bf16x2(float a, float b) {
+    const f32x2_t v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+}
 
 #define BM 128
 #define BN 128
@@ -111,10 +121,13 @@ __device__ __forceinline__ const char* skg_uniform_ptr(const char* p) {
 // EPI >= 0: epilogue fixed at compile time; EPI < 0: taken from the descriptor (grouped launches of small GEMMs).
 // T = tile scale: block tile 64T x 64T, wave tile 32T x 32T = T x T MFMA tiles (T = 2: 128 x 128, the throughput
 // shape; T = 1: 64 x 64 for small M, four times the workgroups for the same problem).
-// MODE = main loop: 0 register-staged fp32 MFMA, 1 DMA-staged fp32 MFMA, 2 fp16x2-split operands on the fp16 MFMA.
+// MODE = main loop: 0 register-staged fp32 MFMA, 1 DMA-staged fp32 MFMA, 2 fp16x2-split operands on the fp16 MFMA,
+// 6 bf16 operands on the bf16 MFMA (3 / 4 / 5: the 64 x 64 latency loops).
+// MODE 6: bf16 operands (w16 = bf16 twin of W with W's element indexing), fp32 accumulation on the bf16 MFMA.
 template <int EPI_T, int MODE, int T>
-__device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_id, float* smem) {
-    static_assert(MODE == 1 || MODE == 3 || MODE == 4 || MODE == 5 || T == 2, "only the DMA-staged and the latency loops have a 64 x 64 variant");
+__device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_id, float* smem,
+                                              const uint16_t* w16 = nullptr) {
+    static_assert(MODE == 1 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 6 || T == 2, "only the DMA-staged, the latency and the bf16 loops have a 64 x 64 variant");
     static_assert((MODE != 3 && MODE != 4 && MODE != 5) || T == 1, "the latency loops are 64 x 64 tiles");
     constexpr bool GLDS = MODE == 1;
     const int Kmap = d.K;
@@ -500,6 +513,158 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             cur = cur + 1 == NB4 ? 0 : cur + 1;
         }
         __syncthreads();                                        // the epilogue's transposition reuses the ring
+    } else if constexpr (MODE == 6) {
+        // ---- bf16 operands, fp32 accumulation (inference_precision "bf16"): every product is bf16(A) . bf16(W)^T on
+        // v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate), bias / epilogue / stored activations stay fp32.  64 k per step,
+        // two LDS buffers of [64T rows][64 k] bf16 per operand (128-byte rows; the 16-byte slot s of row r holds k-chunk
+        // s ^ (r & 7): the ds_read_b128 of a fragment -- 32 rows, one chunk -- and the staging writes are conflict-free).
+        //   W: its bf16 twin (same element indexing as the fp32 weight, ldw % 8 == 0), staged by global_load_lds_dwordx4;
+        //      chunks past K read the row's first chunk and are zeroed in the fragments of the last step.
+        //   A: fp32 (gathers as in MODE 0), loaded into registers one step ahead and rounded to bf16 (RNE, a plain
+        //      conversion: inf / nan propagate as on the exact loop) on its way into LDS; rows past M / negative rows and
+        //      k past K are written as zeros.
+        // Fragment reads are inline asm with an explicit lgkmcnt wait (for a C++ LDS read hipcc waits vmcnt(0) on every
+        // DMA in flight, which would also drain the A prefetch); one barrier per step.  The C/D layout of the bf16 MFMA is
+        // that of v_mfma_f32_32x32x2_f32: the epilogue below takes the accumulators as they are.
+        constexpr int BK6 = 64, RB = 128, OPB = TBM * RB, BUFB = 2 * OPB;
+        constexpr int NPA = TBM / 32;                                 // A staging: rows (tid >> 3) + 32 p, k-chunk tid & 7
+        constexpr int NIW = 2 * T;                                    // W DMA instructions per wave (8 rows each)
+        char* lds = reinterpret_cast<char*>(smem);
+        const int ch = tid & 7, rs = tid >> 3;
+        const float* pa[NPA];
+        bool va[NPA];
+#pragma unroll
+        for (int p = 0; p < NPA; ++p) {
+            const int row = m0 + rs + 32 * p;
+            int src = -1;
+            if (row < d.M) src = d.a_rows ? d.a_rows[row] : row;
+            va[p] = src >= 0;
+            pa[p] = d.A + (int64_t)(va[p] ? src : 0) * d.lda;        // always a readable row; zeroed when written to LDS
+        }
+        const uint32_t sa = (uint32_t)(rs * RB + ((ch ^ (rs & 7)) << 4));   // + p * 32 rows (row & 7 is rs & 7)
+        const int wu = __builtin_amdgcn_readfirstlane(wid);           // wave-uniform: the DMA's LDS base stays scalar
+        const uint16_t* wrow[NIW];
+        int wk[NIW];
+#pragma unroll
+        for (int i = 0; i < NIW; ++i) {
+            const int r = 16 * T * wid + 8 * i + (lane >> 3);        // lane -> row r, 16-byte slot lane & 7 of the LDS row
+            wrow[i] = w16 + (int64_t)(n0 + r < d.N ? n0 + r : n0) * d.ldw;       // rows past N: a valid row, never stored
+            wk[i] = ((lane & 7) ^ (r & 7)) * 8;
+        }
+        int s_begin = 0, s_end = (d.K + BK6 - 1) / BK6;
+        if (d.split_k > 1) {
+            const int per = (s_end + d.split_k - 1) / d.split_k;
+            s_begin = split_slice * per < s_end ? split_slice * per : s_end;
+            s_end = s_begin + per < s_end ? s_begin + per : s_end;
+        }
+        f32x4 ra[NPA][2];
+        auto load_a = [&](int st) {
+#ifdef SKG_B16_NOLOAD                                 // (timing builds, tools/bf16_gemm_knockout.py: results are wrong)
+            if (st > s_begin + 1) return;
+#endif
+            const int k = st * BK6 + ch * 8;
+            const int k0 = k < d.K ? k : 0, k1 = k + 4 < d.K ? k + 4 : 0;     // K % 4 == 0: whole quads in or out
+#pragma unroll
+            for (int p = 0; p < NPA; ++p) {
+                ra[p][0] = *reinterpret_cast<const f32x4*>(pa[p] + k0);
+                ra[p][1] = *reinterpret_cast<const f32x4*>(pa[p] + k1);
+            }
+        };
+        auto store_a = [&](int st, int buf) {
+            const int k = st * BK6 + ch * 8;
+#pragma unroll
+            for (int p = 0; p < NPA; ++p) {
+                const bool in0 = va[p] && k < d.K, in1 = va[p] && k + 4 < d.K;
+                const f32x4 x = ra[p][0], y = ra[p][1];
+                u32x4 v;
+                v[0] = skg_pack_bf16x2(in0 ? x[0] : 0.f, in0 ? x[1] : 0.f);
+                v[1] = skg_pack_bf16x2(in0 ? x[2] : 0.f, in0 ? x[3] : 0.f);
+                v[2] = skg_pack_bf16x2(in1 ? y[0] : 0.f, in1 ? y[1] : 0.f);
+                v[3] = skg_pack_bf16x2(in1 ? y[2] : 0.f, in1 ? y[3] : 0.f);
+                *reinterpret_cast<u32x4*>(lds + buf * BUFB + sa + p * 32 * RB) = v;
+            }
+        };
+        auto issue_w = [&](int st, int buf) {
+#ifdef SKG_B16_NOLOAD
+            if (st > s_begin + 1) return;
+#endif
+            char* dst = lds + buf * BUFB + OPB + wu * (16 * T * RB);
+#pragma unroll
+            for (int i = 0; i < NIW; ++i) {
+                const int k = st * BK6 + wk[i];
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[i] + (k < d.K ? k : 0)),
+                                                 (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+            }
+        };
+        // fragment addresses: row (wr | wc) * 32T + 32 mi + li, k-chunk 2 ks + lh in slot (2 ks + lh) ^ (li & 7)
+        const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
+        uint32_t xo[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) xo[ks] = (uint32_t)(((2 * ks + lh) ^ (li & 7)) << 4);
+        const uint32_t ra0 = (uint32_t)((wr * 32 * T + li) * RB), rb0 = (uint32_t)(OPB + (wc * 32 * T + li) * RB);
+        if (s_begin < s_end) {
+            issue_w(s_begin, 0);
+            load_a(s_begin);
+            store_a(s_begin, 0);                                      // (waits for the A loads: the DMA issued before them has landed too)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (s_begin + 1 < s_end) load_a(s_begin + 1);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
+        int cur = 0;
+        for (int st = s_begin; st < s_end; ++st) {
+            const uint32_t base = lds0 + cur * BUFB;
+            u32x4 fa[T][4], fb[T][4];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int i = 0; i < T; ++i) {
+                    asm volatile("ds_read_b128 %0, %1" : "=v"(fa[i][ks]) : "v"(base + ra0 + i * 32 * RB + xo[ks]));
+                    asm volatile("ds_read_b128 %0, %1" : "=v"(fb[i][ks]) : "v"(base + rb0 + i * 32 * RB + xo[ks]));
+                }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int i = 0; i < T; ++i) asm volatile("" : "+v"(fa[i][ks]), "+v"(fb[i][ks]));   // uses stay below the wait
+            if (st + 1 < s_end) issue_w(st + 1, cur ^ 1);
+            if (st * BK6 + BK6 > d.K) {
+                // last step of a K that is not a multiple of 64: W chunks past K hold a clamped row start -- zero them (A is
+                // zero there, and 0 * inf would be nan)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    const int kb = st * BK6 + ks * 16 + lh * 8;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int i = 0; i < T; ++i) fb[i][ks][e] = kb + 2 * e < d.K ? fb[i][ks][e] : 0u;
+                }
+            }
+#ifdef SKG_B16_NOMFMA                                 // (timing builds: the fragments are consumed by one add each)
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int mi = 0; mi < T; ++mi)
+                    acc[mi][0][ks] += __uint_as_float(fa[mi][ks][0] ^ fb[mi][ks][1]);
+#else
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int mi = 0; mi < T; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < T; ++ni)
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(s16x8, fa[mi][ks]),
+                                                                              __builtin_bit_cast(s16x8, fb[ni][ks]),
+                                                                              acc[mi][ni], 0, 0, 0);
+#endif
+            if (st + 1 < s_end) {
+                store_a(st + 1, cur ^ 1);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // W of step st + 1 landed (nothing else in flight)
+                if (st + 2 < s_end) load_a(st + 2);
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            }
+            cur ^= 1;
+        }
+        __syncthreads();                                              // the epilogue's transposition reuses the buffers
     } else if constexpr (MODE == 2) {
         // ---- fp32-grade result from the fp16 matrix pipe (3 MFMA passes instead of the 8 of the fp32 MFMA per 16 k).
         // Every operand value x is carried as h + m with h = fp16(x), m = fp16(x - h): 22 significant bits, i.e.
@@ -1069,6 +1234,29 @@ __global__ __launch_bounds__(512, 1) void skg_gemm_group_khalves_kernel(const sk
     skg_gemm_tile<-1, 5, 1>(g.d[k], blockIdx.x - g.start[k], smem);
 }
 
+// ---- bf16 operands (MODE 6): W read from its bf16 twin w16 (W's element indexing), A rounded on its way into LDS
+#define SKG_SMEM6(T) (2 * 2 * 64 * (T) * 32)      // floats: two buffers x (A | W) x 64T rows x 128 bytes
+template <int EPI, int T>
+__global__ __launch_bounds__(256, 2) void skg_gemm_b16_kernel(const skg_gemm_desc d, const uint16_t* w16) {
+    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
+    skg_gemm_tile<EPI, 6, T>(d, blockIdx.x, smem, w16);
+}
+
+struct skg_gemm_group_b16_args {
+    skg_gemm_group_args g;
+    const uint16_t* w16[SKG_GEMM_GROUP_MAX];
+};
+
+template <int T>
+__global__ __launch_bounds__(256, 2) void skg_gemm_group_b16_kernel(const skg_gemm_group_b16_args a) {
+    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
+    int k = 0;
+#pragma unroll
+    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
+        if (t < a.g.n && (int)blockIdx.x >= a.g.start[t]) k = t;
+    skg_gemm_tile<-1, 6, T>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k]);
+}
+
 // Split-K reduction: adds the slices in slice order (deterministic) and applies the plain epilogues.
 __device__ __forceinline__ void skg_splitk_reduce_one(const skg_gemm_desc& d, int64_t i) {
     const int64_t total = (int64_t)d.M * d.N;
@@ -1282,6 +1470,18 @@ static bool skg_gemm_group_small(const skg_gemm_desc* descs, int n) {
     return tiles128 < g_small_tiles;
 }
 
+// launches per main loop since the last reset (statistics for tests and profiles: which loop a forward ran), by
+// SKG_GEMM_PATH_*: exact fp32 (MODE 0 / 1 / 3 / 4 / 5), fp16x2 (MODE 2), bf16 (MODE 6), routed to skg_gemmx_f32
+static std::atomic<long long> g_gemm_path[SKG_GEMM_PATHS];
+static inline void skg_gemm_count(int path) { g_gemm_path[path].fetch_add(1, std::memory_order_relaxed); }
+
+extern "C" void skg_gemm_path_counts(int64_t* out_host, int reset) {
+    for (int i = 0; i < SKG_GEMM_PATHS; ++i) {
+        if (out_host) out_host[i] = g_gemm_path[i].load(std::memory_order_relaxed);
+        if (reset) g_gemm_path[i].store(0, std::memory_order_relaxed);
+    }
+}
+
 extern "C" int skg_gemm_group_tile(const skg_gemm_desc* descs_host, int n) {
     if (!descs_host || n < 1 || n > SKG_GEMM_GROUP_MAX) return SKG_E_ARG;
     return skg_gemm_group_small(descs_host, n) ? 1 : 2;
@@ -1308,7 +1508,10 @@ extern "C" int skg_gemm_group_f32(const skg_gemm_desc* descs_host, int n, void* 
             ok = skg_route_desc(d, xs[i], fs[i]);
             tiles128 += (int64_t)((d.M + 127) / 128) * ((d.N + 127) / 128) * (d.split_k > 1 ? d.split_k : 1);
         }
-        if (ok && tiles128 >= g_route_tiles && tiles128 < 4 * g_small_tiles) return skg_gemmx_f32_fused(xs, fs, n, stream);
+        if (ok && tiles128 >= g_route_tiles && tiles128 < 4 * g_small_tiles) {
+            skg_gemm_count(SKG_GEMM_PATH_ROUTED);
+            return skg_gemmx_f32_fused(xs, fs, n, stream);
+        }
     }
     for (int i = 0; i < n; ++i) {
         const skg_gemm_desc& d = descs_host[i];
@@ -1333,6 +1536,7 @@ extern "C" int skg_gemm_group_f32(const skg_gemm_desc* descs_host, int n, void* 
     bool direct = small && g_small_mode == 4;               // every member with whole 64-k steps: the direct-to-LDS loop
     for (int i = 0; i < g.n && direct; ++i) direct = (g.d[i].K % 64) == 0;
     const bool halves = small && (g_small_mode == 5 || (g_small_mode == 6 && blocks <= g_khalves_blocks));
+    skg_gemm_count(split && !small ? SKG_GEMM_PATH_FP16X2 : SKG_GEMM_PATH_EXACT);
     if (direct) hipLaunchKernelGGL(skg_gemm_group_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g);
     else if (halves) hipLaunchKernelGGL(skg_gemm_group_khalves_kernel, dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, g);
     else if (small && g_small_mode >= 3) hipLaunchKernelGGL(skg_gemm_group_latency_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g);
@@ -1359,12 +1563,16 @@ extern "C" int skg_gemm_f32(const skg_gemm_desc* dh, void* stream) {
     if (!split && T == 1 && d.M > 64) {                    // mid-size launch: the free-layout GEMM (see g_route_tiles)
         const int64_t tiles128 = (int64_t)((d.M + 127) / 128) * ((d.N + 127) / 128) * (d.split_k > 1 ? d.split_k : 1);
         skg_gemmx_desc x; skg_gemmx_fused f;
-        if (tiles128 >= g_route_tiles && skg_route_desc(d, x, f)) return skg_gemmx_f32_fused(&x, &f, 1, stream);
+        if (tiles128 >= g_route_tiles && skg_route_desc(d, x, f)) {
+            skg_gemm_count(SKG_GEMM_PATH_ROUTED);
+            return skg_gemmx_f32_fused(&x, &f, 1, stream);
+        }
     }
     const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
     if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
     dim3 grid((unsigned)nblk), block(256);
     hipStream_t s = (hipStream_t)stream;
+    skg_gemm_count(split ? SKG_GEMM_PATH_FP16X2 : SKG_GEMM_PATH_EXACT);
 #define SKG_LAUNCH(E)                                                                              \
     if (split) hipLaunchKernelGGL((skg_gemm_kernel<E, 2, 2>), grid, block, 0, s, d);               \
     else if (glds && T == 1 && g_small_mode == 4 && (d.K % 64) == 0) hipLaunchKernelGGL((skg_gemm_kernel<E, 4, 1>), grid, block, 0, s, d); \
@@ -1384,6 +1592,95 @@ extern "C" int skg_gemm_f32(const skg_gemm_desc* dh, void* stream) {
     if (d.split_k > 1) {
         const int64_t total = (int64_t)d.M * d.N;
         hipLaunchKernelGGL(skg_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d);
+    }
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ bf16 operands (MODE 6)
+// Same descriptor, tile map, split-K and epilogues as skg_gemm_f32; the tile scale follows skg_gemm_tile_scale /
+// skg_gemm_group_small, so skg_gemm_dot_partials and skg_gemm_group_tile hold for these launches too.  Never routed to the
+// fp32 free-layout GEMM.  w16: bf16 twin of d.W with the same element indexing (skg_twin_bf16 of the fp32 buffer).
+static int skg_gemm_b16_check(const skg_gemm_desc& d, const uint16_t* w16) {
+    const int rc = skg_gemm_validate(d);
+    if (rc) return rc;
+    if (!w16 || (d.ldw & 7)) return SKG_E_ARG;                      // 16-byte DMA pieces of whole twin rows
+    if (!skg_aligned16(w16)) return SKG_E_ALIGN;
+    return 0;
+}
+
+extern "C" int skg_gemm_b16_f32(const skg_gemm_desc* dh, const uint16_t* w16, void* stream) {
+    if (!dh) return SKG_E_ARG;
+    skg_gemm_desc d = *dh;
+    d.w_split = nullptr; d.a_exp = nullptr;                         // ignored here (the tile scale reads w_split)
+    const int rc = skg_gemm_b16_check(d, w16);
+    if (rc) return rc;
+    if (d.M == 0) return 0;
+    const int T = skg_gemm_tile_scale(&d);
+    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
+    if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
+    dim3 grid((unsigned)nblk), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    skg_gemm_count(SKG_GEMM_PATH_BF16);
+#define SKG_LAUNCH(E)                                                                               \
+    if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 1>), grid, block, 0, s, d, w16);         \
+    else hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 2>), grid, block, 0, s, d, w16);
+    switch (d.epilogue) {
+        case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
+        case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;
+        case SKG_EPI_MUL_RELU:      SKG_LAUNCH(SKG_EPI_MUL_RELU) break;
+        case SKG_EPI_RELU_DOT:      SKG_LAUNCH(SKG_EPI_RELU_DOT) break;
+        case SKG_EPI_BIAS_RES_RELU: SKG_LAUNCH(SKG_EPI_BIAS_RES_RELU) break;
+    }
+#undef SKG_LAUNCH
+    if (d.split_k > 1) {
+        const int64_t total = (int64_t)d.M * d.N;
+        hipLaunchKernelGGL(skg_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d);
+    }
+    return skg_launch_status();
+}
+
+extern "C" int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uint16_t* const* w16_host, int n,
+                                      void* stream) {
+    if (!descs_host || !w16_host || n < 1 || n > SKG_GEMM_GROUP_MAX) return SKG_E_ARG;
+    skg_gemm_desc descs[SKG_GEMM_GROUP_MAX];
+    for (int i = 0; i < n; ++i) {
+        descs[i] = descs_host[i];
+        descs[i].w_split = nullptr; descs[i].a_exp = nullptr;          // ignored here (the tile scale reads w_split)
+        const int rc = skg_gemm_b16_check(descs[i], w16_host[i]);
+        if (rc) return rc;
+    }
+    const bool small = skg_gemm_group_small(descs, n);
+    skg_gemm_group_b16_args a;
+    skg_gemm_group_args r;
+    a.g.n = r.n = 0;
+    int64_t blocks = 0, rblocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const skg_gemm_desc& d = descs[i];
+        if (d.split_k > 1 && !small) return SKG_E_ARG;                     // split-K only with the 64 x 64 tiles
+        if (d.M == 0) continue;
+        const int64_t nb = skg_gemm_blocks(d.M, d.N, d.K, small ? 1 : 2) * (d.split_k > 1 ? d.split_k : 1);
+        if (blocks + nb > 0x7fffffffLL) return SKG_E_LIMIT;
+        a.g.d[a.g.n] = d;
+        a.w16[a.g.n] = w16_host[i];
+        a.g.start[a.g.n] = (int)blocks;
+        blocks += nb;
+        ++a.g.n;
+        if (d.split_k > 1) {
+            r.d[r.n] = d;
+            r.start[r.n] = (int)rblocks;
+            rblocks += ((int64_t)d.M * d.N + 255) / 256;
+            ++r.n;
+        }
+    }
+    if (a.g.n == 0) return 0;
+    for (int i = a.g.n; i <= SKG_GEMM_GROUP_MAX; ++i) a.g.start[i] = (int)blocks;
+    for (int i = a.g.n; i < SKG_GEMM_GROUP_MAX; ++i) a.w16[i] = nullptr;
+    skg_gemm_count(SKG_GEMM_PATH_BF16);
+    if (small) hipLaunchKernelGGL(skg_gemm_group_b16_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(skg_gemm_group_b16_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (r.n) {
+        for (int i = r.n; i <= SKG_GEMM_GROUP_MAX; ++i) r.start[i] = (int)rblocks;
+        hipLaunchKernelGGL(skg_splitk_reduce_group_kernel, dim3((unsigned)rblocks), dim3(256), 0, (hipStream_t)stream, r);
     }
     return skg_launch_status();
 }

@@ -218,6 +218,7 @@ class PackedWeights:
 
         self.device = device
         self.splits = SplitWeights()
+        self.bf16 = Bf16Weights()       # (both caches die with this object: a repack makes fresh twins)
         self.K = gh.num_cls
         self.bh1_w = pad_k(w(gh.box_head[1].weight)); self.bh1_b = w(gh.box_head[1].bias)
         self.bh1_k = gh.box_head[1].weight.shape[1]
@@ -308,6 +309,45 @@ class SplitWeights:
         return False
 
 
+def _active_bf16():
+    return getattr(_TLS, "bf16", None)
+
+
+class Bf16Weights:
+    """bf16 twins of the packed weights for skg_gemm_b16_f32 (inference_precision="bf16"): one twin per packed weight
+    tensor, with the tensor's element indexing (a column sub-view of the weight is the twin's base plus the same element
+    offset), made on first use -- before any capture: the eager pass ahead of a plan's capture makes them -- and kept with
+    the packed weights they mirror."""
+
+    def __init__(self):
+        self.twins = {}
+
+    def get(self, W, W_off):
+        """-> device address of the twin element that mirrors W.flatten()[W_off]."""
+        key = (W.data_ptr(), W.numel())
+        t = self.twins.get(key)
+        if t is None:
+            n = W.numel()
+            if n % 4 or not W.is_contiguous():
+                raise _capi.SkgError("bf16 twin of a weight of %d elements (needs a contiguous multiple of 4)" % n)
+            # + 8 zeros: the 16-byte loads of the last row may reach up to 4 elements past K (K % 8 == 4)
+            twin = torch.zeros(n + 8, dtype=torch.int16, device=W.device)
+            _capi.check(_capi.lib().skg_twin_bf16(W.data_ptr(), twin.data_ptr(), n, _stream()), "skg_twin_bf16")
+            torch.cuda.current_stream().synchronize()       # other streams may read it with no event in between
+            t = (twin, W)                                    # holding W keeps its address from being reused
+            self.twins[key] = t
+        return t[0].data_ptr() + 2 * W_off
+
+    def __enter__(self):
+        self._prev = _active_bf16()
+        _TLS.bf16 = self
+        return self
+
+    def __exit__(self, *a):
+        _TLS.bf16 = self._prev
+        return False
+
+
 def gemm_desc(A, W, bias, C_out, M, N, K, epilogue, lda=None, ldw=None, ldc=None, a_rows=None, out_rows=None, P=None,
               p_idx=None, ldp=0, Q=None, q_idx=None, ldq=0, mbias=None, C_raw=None, ldc_raw=0, dot_w=None,
               dot_partial=None, res=None, ldres=0, A_off=0, W_off=0, C_off=0, d=None, split_k=0, split_ws=None,
@@ -332,6 +372,13 @@ def gemm_desc(A, W, bias, C_out, M, N, K, epilogue, lda=None, ldw=None, ldc=None
         w_split, w_scale = splits.get(W, W_off, N, K, d.ldw)
     d.w_split = _ptr(w_split); d.w_scale = w_scale
     return d
+
+
+def weight_twin(W, W_off=0, w_split=None):
+    """Device address of the bf16 twin element mirroring W.flatten()[W_off] for skg_gemm_b16_f32 / skg_gemm_group_b16_f32
+    while a Bf16Weights context is active on this thread; 0 outside one or when the caller brings its own w_split."""
+    bf = _active_bf16()
+    return bf.get(W, W_off) if bf is not None and w_split is None else 0
 
 
 # ---- row exponents of the split-operand (fp16x2) GEMMs' A operands (power-of-two row scale, include/skghoi.h): one small
@@ -399,12 +446,17 @@ def dot_partials(M, N, K, lda, ldw):
 def gemm(A, W, bias, C_out, M, N, K, epilogue, **kw):
     """One skg_gemm_f32 launch (see gemm_desc for the keywords)."""
     d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
+    w16 = weight_twin(W, kw.get("W_off", 0), kw.get("w_split"))
     keep_exp = enqueue_row_exponents(d, A.device) if d.w_split else None
     timed = GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or epilogue in GEMM_TIMER_EPI)
     if timed:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-    _capi.check(_capi.lib().skg_gemm_f32(C.byref(d), _stream()), "skg_gemm_f32[%dx%dx%d epi %d]" % (M, N, K, epilogue))
+    if w16:
+        _capi.check(_capi.lib().skg_gemm_b16_f32(C.byref(d), w16, _stream()),
+                    "skg_gemm_b16_f32[%dx%dx%d epi %d]" % (M, N, K, epilogue))
+    else:
+        _capi.check(_capi.lib().skg_gemm_f32(C.byref(d), _stream()), "skg_gemm_f32[%dx%dx%d epi %d]" % (M, N, K, epilogue))
     if timed:
         e1.record()
         GEMM_TIMER.append((e0, e1, M, N, K, epilogue))
@@ -428,8 +480,10 @@ def gemm_group(specs):
     arr = (_capi.GemmDesc * n)()
     flops = 0.0
     keep_exp = []
+    w16 = (C.c_void_p * n)()
     for i, (a, kw) in enumerate(specs):
         gemm_desc(*a, d=arr[i], **kw)
+        w16[i] = weight_twin(a[1], kw.get("W_off", 0), kw.get("w_split")) or None
         if arr[i].w_split:
             keep_exp.append(enqueue_row_exponents(arr[i], a[0].device))
         flops += 2.0 * a[4] * a[5] * a[6]
@@ -450,7 +504,10 @@ def gemm_group(specs):
     if timed:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-    _capi.check(lib.skg_gemm_group_f32(arr, n, _stream()), "skg_gemm_group_f32[%d]" % n)
+    if any(w16):
+        _capi.check(lib.skg_gemm_group_b16_f32(arr, w16, n, _stream()), "skg_gemm_group_b16_f32[%d]" % n)
+    else:
+        _capi.check(lib.skg_gemm_group_f32(arr, n, _stream()), "skg_gemm_group_f32[%d]" % n)
     if timed:
         e1.record()
         GEMM_TIMER.append((e0, e1, int(flops // 2), 1, 1, 5))       # epilogue id 5 = grouped launch
@@ -577,6 +634,7 @@ class HeadEngine:
         self.n_streams = 2          # chunks alternate over this many side streams: one chunk's kernel tails and small
                                     # launches are filled by the other's GEMMs (+2.6 % at 256 images, measured); 1: off
         self.precision = "fp32"     # "fp32": exact fp32 MFMA; "fp16x2" (opt-in): fp16 matrix pipe from 2-way operand splits
+        self.inference_precision = None     # None, "fp32", "fp16x2", "bf16": see eval_precision()
         self._pw = None
         self._vt = None
         self._det_off_cache = {}
@@ -838,8 +896,17 @@ class HeadEngine:
         return self.pre_pack(self.pre_launch(detections, targets, append_gt, training, check_weights))
 
     # ------------------------------------------------------------------------------------------ graph head
+    def eval_precision(self):
+        """GEMM path of the target-less eval forward: inference_precision, or by default fp32 -> "fp32" (exact),
+        fp16x2 / bf16 -> "fp16x2"."""
+        if self.inference_precision is not None:
+            return self.inference_precision
+        return "fp16x2" if self.precision in ("fp16x2", "bf16") else "fp32"
+
     def _split_ctx(self, pw):
-        return pw.splits if self.precision in ("fp16x2", "bf16") else _NullCtx()
+        """Weight-twin context of the eval forward's GEMMs (fp16x2 planes, bf16 twins or none: the exact loop)."""
+        p = self.eval_precision()
+        return pw.splits if p == "fp16x2" else pw.bf16 if p == "bf16" else _NullCtx()
 
     def graph(self, feat3, image_shapes, pooled, pre, training=False, tables=None, want_scores=False):
         pw = self.weights(pre.device, wsum=getattr(pre, "wsum", None))

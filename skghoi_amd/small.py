@@ -44,7 +44,8 @@ import numpy as np
 import torch
 
 from . import _capi, layout, transh
-from .engine import Preprocessed, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_group, pick_split_k, _stream
+from .engine import Preprocessed, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_group, pick_split_k, _stream, \
+    weight_twin
 
 META_WORDS = layout.META_DTYPE.itemsize // 4
 
@@ -231,6 +232,7 @@ class SmallBatchRunner:
         p.sk = pick_split_k(NA, 1024, kp)
         p.ws = torch.empty(p.sk, NA, 1024, **f32) if p.sk > 1 else None
         p.bh1_desc = None                                # filled on first use (needs the weight-twin context)
+        p.bh1_w16 = 0
         p.pre = Preprocessed()
         p.pre.device = dev; p.pre.B = pre.B
         p.pre.boxes, p.pre.scores, p.pre.labels = p.boxes, p.scores, p.labels
@@ -460,7 +462,7 @@ class SmallBatchRunner:
                 bucket = (capacity(nh1, max(eng.max_human, nh1)),
                           capacity(n1, min(max(eng.max_human + eng.max_object, n1), _capi.TRANSH_ENT)))
         shape_key = ("bucket",) + bucket if bucket else (tuple(pre.n_h.tolist()), tuple(pre.n.tolist()))
-        key = shape_key + (tuple(feat3.shape[:2]), eng.precision, eng.gh.num_iter, eng.faithful_skip_offset,
+        key = shape_key + (tuple(feat3.shape[:2]), eng.precision, eng.eval_precision(), eng.gh.num_iter, eng.faithful_skip_offset,
                            eng.plan_epoch, dev.index)
         p = self.plans.get(key)
         if p is None and not bucket and eng.small_capture_after > 1:
@@ -541,11 +543,15 @@ class SmallBatchRunner:
             with eng._split_ctx(pw):
                 p.bh1_desc = gemm_desc(x0, pw.bh1_w, pw.bh1_b, p.enc1, lay.sum_all, 1024, x0.shape[1],
                                        _capi.EPI_BIAS_RELU, split_k=p.sk, split_ws=p.ws)
+                p.bh1_w16 = weight_twin(pw.bh1_w)    # bf16 eval path: the twin beside the descriptor (else 0)
         p.bh1_desc.A = x0.data_ptr()               # the fields that change from call to call: the caller's tensor and (bucket
         p.bh1_desc.M = n_act                       # plans) its row count
         if p.bh1_desc.w_split:
             p.bh1_exp = enqueue_row_exponents(p.bh1_desc, x0.device)
-        _capi.check(lib.skg_gemm_f32(C.byref(p.bh1_desc), _stream()), "skg_gemm_f32[box_head 1]")
+        if p.bh1_w16:
+            _capi.check(lib.skg_gemm_b16_f32(C.byref(p.bh1_desc), p.bh1_w16, _stream()), "skg_gemm_b16_f32[box_head 1]")
+        else:
+            _capi.check(lib.skg_gemm_f32(C.byref(p.bh1_desc), _stream()), "skg_gemm_f32[box_head 1]")
         # per-call records: meta (image sizes, result offsets), cell count, TransH entity tables
         if p.h2d_done is not None:
             p.h2d_done.synchronize()               # the staging block's previous copy (normally long finished)

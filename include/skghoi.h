@@ -145,6 +145,18 @@ int skg_roi_align_bwd_f32(float* const* dfeats_host, const int32_t* H_host, cons
                           const float* scales_host, int n_levels, int C, int k_min, int k_max, float canonical_scale,
                           int canonical_level, const float* boxes, const int32_t* box_image, int n_rois, int pooled,
                           int sampling, const float* dout, void* stream);
+/* Element types of skg_roi_align_x: the dtype codes of the SKGFC001 feature shard (skghoi_amd/cache.py).           */
+#define SKG_DTYPE_F32  0
+#define SKG_DTYPE_F16  1
+#define SKG_DTYPE_BF16 2
+/* skg_roi_align_f32 on maps of any of those types, into an output of any of them: feats_host[l] holds map_dtype
+ * elements, out out_dtype elements.  The arithmetic is that of skg_roi_align_f32: every map element is widened exactly
+ * to fp32 and the fp32 result is rounded once (round to nearest even) when out_dtype is a half type.  So half maps give
+ * the fp32 output of skg_roi_align_f32 on the widened maps bit for bit, and a half output is that output rounded.   */
+int skg_roi_align_x(const void* const* feats_host, int map_dtype, const int32_t* H_host, const int32_t* W_host,
+                    const float* scales_host, int n_levels, int C, int k_min, int k_max, float canonical_scale,
+                    int canonical_level, const float* boxes, const int32_t* box_image, int n_rois, int pooled,
+                    int sampling, void* out, int out_dtype, void* stream);
 
 /* AdaptiveAvgPool2d(1) of features['3'] (HEAD:811): in [B, C, HW] -> out [B, C]. */
 int skg_global_avgpool_f32(const float* in, int B, int C, int HW, float* out, void* stream);
@@ -239,6 +251,15 @@ int skg_gemm_group_tile(const skg_gemm_desc* descs_host, int n);
  * scale when queried with w_split = NULL.  Never routed to skg_gemmx_f32.  w16_host: one twin pointer per descriptor. */
 int skg_gemm_b16_f32(const skg_gemm_desc* desc_host, const uint16_t* w16, void* stream);
 int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uint16_t* const* w16_host, int n, void* stream);
+/* skg_gemm_b16_f32 with A given in bf16: a16 holds the M x K operand with row stride d.lda ELEMENTS; d.A is not read.
+ * a16 16-byte aligned (else SKG_E_ALIGN), d.lda % 8 == 0 and d.K % 8 == 0 (else SKG_E_ALIGN), d.a_rows == NULL (else
+ * SKG_E_ARG).  A is staged like W (global_load_lds_dwordx4); elements of a row from K up to d.lda are never read.  The
+ * result is bit-identical to skg_gemm_b16_f32 on the widened fp32 A with the same descriptor (rounding a bf16 value
+ * to bf16 is the identity); everything else -- epilogues, out_rows, split-K, tile scale, skg_gemm_dot_partials -- as
+ * there.  Counted as SKG_GEMM_PATH_BF16, and by skg_gemm_b16_a16_launches.                                           */
+int skg_gemm_b16_a16_f32(const skg_gemm_desc* desc_host, const uint16_t* a16, const uint16_t* w16, void* stream);
+/* Launches of skg_gemm_b16_a16_f32 since the last reset (reset != 0 zeroes the count after the read).  For tests.   */
+void skg_gemm_b16_a16_launches(int64_t* out_host, int reset);
 /* Launches per main loop of the skg_gemm_* entry points since the last reset (out_host: SKG_GEMM_PATHS counts, by
  * SKG_GEMM_PATH_*; reset != 0 zeroes them after the read).  Process-wide, for tests and profiles.                   */
 #define SKG_GEMM_PATH_EXACT  0          /* exact fp32 loops (register-staged, DMA-staged, 64 x 64 latency loops)      */

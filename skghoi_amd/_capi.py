@@ -7,6 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "csrc", "libskghoi_hip.so")   # SKG_LIB: kernel A/B builds
 
 EPI_BIAS, EPI_BIAS_RELU, EPI_MUL_RELU, EPI_RELU_DOT, EPI_BIAS_RES_RELU = range(5)
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(3)          # SKG_DTYPE_*: skg_roi_align_x, the feature shard's dtype field
 MAX_DET_PER_IMAGE = 1024
 MAX_NODES = 160
 SPATIAL_LD = 48
@@ -121,6 +122,8 @@ PROTOTYPES = {
                                     C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "skg_roi_align_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, C.c_int, _vp, _vp,
                                     C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "skg_roi_align_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, C.c_int, _vp,
+                                  _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "skg_global_avgpool_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "skg_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "skg_transh_draw_f32": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
@@ -133,6 +136,8 @@ PROTOTYPES = {
     "skg_gemm_b16_f32": (C.c_int, [C.POINTER(GemmDesc), _vp, _vp]),
     "skg_gemm_group_b16_f32": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(_vp), C.c_int, _vp]),
     "skg_gemm_path_counts": (None, [C.POINTER(_i64), C.c_int]),
+    "skg_gemm_b16_a16_f32": (C.c_int, [C.POINTER(GemmDesc), _vp, _vp, _vp]),
+    "skg_gemm_b16_a16_launches": (None, [C.POINTER(_i64), C.c_int]),
     "skg_row_exponents_f32": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, _vp]),
     "skg_adamw_f32": (C.c_int, [_vp, C.c_int] + [C.c_double] * 7 + [_vp, C.c_int, _vp]),
     "skg_ctx_set_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),

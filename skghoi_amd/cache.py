@@ -54,7 +54,11 @@ def _to_storage(x, dtype_code):
 
 def write_feature_shard(path, pooled_list, global_feats, image_hw, dtype="fp32"):
     """pooled_list: per-image arrays [N_i, C, p, p]; global_feats [n_images, gdim]; image_hw [n_images, 2]."""
-    code = {"fp32": 0, "fp16": 1, "bf16": 2}[dtype]
+    _write_shard(path, pooled_list, global_feats, image_hw, {"fp32": 0, "fp16": 1, "bf16": 2}[dtype], _to_storage)
+
+
+def _write_shard(path, pooled_list, global_feats, image_hw, code, to_storage):
+    """write_feature_shard with the payload conversion as a parameter (to_storage(array, code) -> storage array)."""
     n_img = len(pooled_list)
     C, p = (pooled_list[0].shape[1], pooled_list[0].shape[2]) if n_img else (0, 0)
     counts = [int(x.shape[0]) for x in pooled_list]
@@ -67,12 +71,13 @@ def write_feature_shard(path, pooled_list, global_feats, image_hw, dtype="fp32")
         pad = (-f.tell()) % 4096
         f.write(b"\0" * pad)
         for x in pooled_list:
-            f.write(_to_storage(np.asarray(x), code).tobytes())
+            f.write(to_storage(np.asarray(x), code).tobytes())
 
 
 class FeatureShard:
     """Memory-mapped reader.  `batch(lo, hi, device)` returns (pooled [sum N, C, p, p] fp32 on device, global
-    [hi-lo, gdim, 1, 1] fp32 -- usable as features['3'] --, image_hw list, boxes-per-image list)."""
+    [hi-lo, gdim, 1, 1] fp32 -- usable as features['3'] --, image_hw list, boxes-per-image list).  With keep_dtype=True
+    the pooled features come in the stored dtype (float32, float16 or bfloat16: the stored bits, not widened)."""
 
     def __init__(self, path):
         self.path = path
@@ -89,12 +94,17 @@ class FeatureShard:
         self.payload = np.memmap(path, dtype=_DT[self.code], mode="r", offset=self.payload_off,
                                  shape=(self.n_boxes, self.row))
 
-    def batch(self, lo, hi, device):
+    def batch(self, lo, hi, device, keep_dtype=False):
         b0, b1 = int(self.box_off[lo]), int(self.box_off[hi])
-        raw = torch.from_numpy(np.array(self.payload[b0:b1], copy=True))
+        host = np.array(self.payload[b0:b1], copy=True)
+        if keep_dtype and self.code == 2:
+            host = host.view(np.int16)                  # (torch views int16, not uint16, as bfloat16)
+        raw = torch.from_numpy(host)
         if device is not None and torch.device(device).type == "cuda":
             raw = raw.pin_memory().to(device, non_blocking=True)
-        if self.code == 0:
+        if keep_dtype:
+            x = raw.view(torch.bfloat16) if self.code == 2 else raw
+        elif self.code == 0:
             x = raw
         elif self.code == 1:
             x = raw.float()
@@ -106,10 +116,22 @@ class FeatureShard:
         return pooled, g, hw, np.diff(self.box_off[lo:hi + 1]).tolist()
 
 
+def _half_to_storage(pooled, dtype_code):
+    """Half-precision pooled features (fp16 / bf16) -> host array in the shard's storage type.  The stored dtype's own
+    bits are copied as they are; otherwise the values are widened exactly and (for the other half type) rounded on the
+    device, RNE -- for finite values the bytes _to_storage writes for the widened values."""
+    want = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype_code]
+    x = (pooled if pooled.dtype == want else pooled.float().to(want)).contiguous()
+    if want == torch.bfloat16:
+        return x.view(torch.int16).cpu().numpy().view(np.uint16)
+    return x.cpu().numpy()
+
+
 def produce_shard(head, features, detections, image_shapes, path, dtype="fp32", targets=None):
     """The feature-cache producer: runs the head's own preprocess (NMS / top-k on the device), its `box_roi_pool` on
     the kept boxes and the global average pool of features['3'], and writes one shard.  Returns the kept detections
-    (list of dicts) so that the caller can store them next to the shard (write_detections_json)."""
+    (list of dicts) so that the caller can store them next to the shard (write_detections_json).  The pool may return
+    fp32, fp16 or bf16 (MultiScaleRoIAlign(output_dtype=...))."""
     from . import _capi
     from .engine import _stream
     with torch.no_grad():
@@ -122,8 +144,13 @@ def produce_shard(head, features, detections, image_shapes, path, dtype="fp32", 
                                                        f3.shape[2] * f3.shape[3], g.data_ptr(), _stream()),
                     "skg_global_avgpool_f32")
     sizes = [len(c) for c in coords]
-    parts = [p.cpu().numpy() for p in pooled.split(sizes)]
-    write_feature_shard(path, parts, g.cpu().numpy(), image_shapes, dtype=dtype)
+    code = {"fp32": 0, "fp16": 1, "bf16": 2}[dtype]
+    if pooled.dtype in (torch.float16, torch.bfloat16):
+        _write_shard(path, [_half_to_storage(p, code) for p in pooled.split(sizes)], g.cpu().numpy(), image_shapes,
+                     code, lambda x, c: x)
+    else:                                           # fp32: rounded on the host, as always
+        _write_shard(path, [p.cpu().numpy() for p in pooled.split(sizes)], g.cpu().numpy(), image_shapes, code,
+                     _to_storage)
     return kept
 
 

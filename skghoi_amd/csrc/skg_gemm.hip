@@ -122,12 +122,13 @@ __device__ __forceinline__ const char* skg_uniform_ptr(const char* p) {
 // T = tile scale: block tile 64T x 64T, wave tile 32T x 32T = T x T MFMA tiles (T = 2: 128 x 128, the throughput
 // shape; T = 1: 64 x 64 for small M, four times the workgroups for the same problem).
 // MODE = main loop: 0 register-staged fp32 MFMA, 1 DMA-staged fp32 MFMA, 2 fp16x2-split operands on the fp16 MFMA,
-// 6 bf16 operands on the bf16 MFMA (3 / 4 / 5: the 64 x 64 latency loops).
+// 6 bf16 operands on the bf16 MFMA, 7 the same with A given in bf16 (3 / 4 / 5: the 64 x 64 latency loops).
 // MODE 6: bf16 operands (w16 = bf16 twin of W with W's element indexing), fp32 accumulation on the bf16 MFMA.
+// MODE 7: MODE 6 with A read from a16 (bf16, d.lda elements per row) instead of d.A, staged like W.
 template <int EPI_T, int MODE, int T>
 __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_id, float* smem,
-                                              const uint16_t* w16 = nullptr) {
-    static_assert(MODE == 1 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 6 || T == 2, "only the DMA-staged, the latency and the bf16 loops have a 64 x 64 variant");
+                                              const uint16_t* w16 = nullptr, const uint16_t* a16 = nullptr) {
+    static_assert(MODE == 1 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 6 || MODE == 7 || T == 2, "only the DMA-staged, the latency and the bf16 loops have a 64 x 64 variant");
     static_assert((MODE != 3 && MODE != 4 && MODE != 5) || T == 1, "the latency loops are 64 x 64 tiles");
     constexpr bool GLDS = MODE == 1;
     const int Kmap = d.K;
@@ -513,7 +514,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             cur = cur + 1 == NB4 ? 0 : cur + 1;
         }
         __syncthreads();                                        // the epilogue's transposition reuses the ring
-    } else if constexpr (MODE == 6) {
+    } else if constexpr (MODE == 6 || MODE == 7) {
         // ---- bf16 operands, fp32 accumulation (inference_precision "bf16"): every product is bf16(A) . bf16(W)^T on
         // v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate), bias / epilogue / stored activations stay fp32.  64 k per step,
         // two LDS buffers of [64T rows][64 k] bf16 per operand (128-byte rows; the 16-byte slot s of row r holds k-chunk
@@ -523,18 +524,21 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
         //   A: fp32 (gathers as in MODE 0), loaded into registers one step ahead and rounded to bf16 (RNE, a plain
         //      conversion: inf / nan propagate as on the exact loop) on its way into LDS; rows past M / negative rows and
         //      k past K are written as zeros.
+        //   A in bf16 (MODE 7, a16: no gathers, K % 8 == 0, lda % 8 == 0): staged exactly like W, into the same layout;
+        //      rows past M read row m0 and are never stored, chunks past K are zeroed in the fragments of the last step.
         // Fragment reads are inline asm with an explicit lgkmcnt wait (for a C++ LDS read hipcc waits vmcnt(0) on every
         // DMA in flight, which would also drain the A prefetch); one barrier per step.  The C/D layout of the bf16 MFMA is
         // that of v_mfma_f32_32x32x2_f32: the epilogue below takes the accumulators as they are.
         constexpr int BK6 = 64, RB = 128, OPB = TBM * RB, BUFB = 2 * OPB;
         constexpr int NPA = TBM / 32;                                 // A staging: rows (tid >> 3) + 32 p, k-chunk tid & 7
-        constexpr int NIW = 2 * T;                                    // W DMA instructions per wave (8 rows each)
+        constexpr int NIW = 2 * T;                                    // W (and bf16 A) DMA instructions per wave (8 rows each)
+        constexpr bool A16 = MODE == 7;
         char* lds = reinterpret_cast<char*>(smem);
         const int ch = tid & 7, rs = tid >> 3;
         const float* pa[NPA];
         bool va[NPA];
 #pragma unroll
-        for (int p = 0; p < NPA; ++p) {
+        for (int p = 0; p < NPA && !A16; ++p) {
             const int row = m0 + rs + 32 * p;
             int src = -1;
             if (row < d.M) src = d.a_rows ? d.a_rows[row] : row;
@@ -544,11 +548,13 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
         const uint32_t sa = (uint32_t)(rs * RB + ((ch ^ (rs & 7)) << 4));   // + p * 32 rows (row & 7 is rs & 7)
         const int wu = __builtin_amdgcn_readfirstlane(wid);           // wave-uniform: the DMA's LDS base stays scalar
         const uint16_t* wrow[NIW];
+        const uint16_t* arow[NIW];
         int wk[NIW];
 #pragma unroll
         for (int i = 0; i < NIW; ++i) {
             const int r = 16 * T * wid + 8 * i + (lane >> 3);        // lane -> row r, 16-byte slot lane & 7 of the LDS row
             wrow[i] = w16 + (int64_t)(n0 + r < d.N ? n0 + r : n0) * d.ldw;       // rows past N: a valid row, never stored
+            if constexpr (A16) arow[i] = a16 + (int64_t)(m0 + r < d.M ? m0 + r : m0) * d.lda;     // (the same for M)
             wk[i] = ((lane & 7) ^ (r & 7)) * 8;
         }
         int s_begin = 0, s_end = (d.K + BK6 - 1) / BK6;
@@ -559,6 +565,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
         }
         f32x4 ra[NPA][2];
         auto load_a = [&](int st) {
+            if constexpr (A16) return;
 #ifdef SKG_B16_NOLOAD                                 // (timing builds, tools/bf16_gemm_knockout.py: results are wrong)
             if (st > s_begin + 1) return;
 #endif
@@ -571,6 +578,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             }
         };
         auto store_a = [&](int st, int buf) {
+            if constexpr (A16) return;
             const int k = st * BK6 + ch * 8;
 #pragma unroll
             for (int p = 0; p < NPA; ++p) {
@@ -596,6 +604,20 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                                                  (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
             }
         };
+        auto issue_a = [&](int st, int buf) {                        // MODE 7: A like W, into the A half of the buffer
+            if constexpr (A16) {
+#ifdef SKG_B16_NOLOAD
+                if (st > s_begin + 1) return;
+#endif
+                char* dst = lds + buf * BUFB + wu * (16 * T * RB);
+#pragma unroll
+                for (int i = 0; i < NIW; ++i) {
+                    const int k = st * BK6 + wk[i];
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(arow[i] + (k < d.K ? k : 0)),
+                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+                }
+            }
+        };
         // fragment addresses: row (wr | wc) * 32T + 32 mi + li, k-chunk 2 ks + lh in slot (2 ks + lh) ^ (li & 7)
         const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
         uint32_t xo[4];
@@ -603,6 +625,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
         for (int ks = 0; ks < 4; ++ks) xo[ks] = (uint32_t)(((2 * ks + lh) ^ (li & 7)) << 4);
         const uint32_t ra0 = (uint32_t)((wr * 32 * T + li) * RB), rb0 = (uint32_t)(OPB + (wc * 32 * T + li) * RB);
         if (s_begin < s_end) {
+            issue_a(s_begin, 0);
             issue_w(s_begin, 0);
             load_a(s_begin);
             store_a(s_begin, 0);                                      // (waits for the A loads: the DMA issued before them has landed too)
@@ -626,7 +649,10 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
                 for (int i = 0; i < T; ++i) asm volatile("" : "+v"(fa[i][ks]), "+v"(fb[i][ks]));   // uses stay below the wait
-            if (st + 1 < s_end) issue_w(st + 1, cur ^ 1);
+            if (st + 1 < s_end) {
+                issue_a(st + 1, cur ^ 1);
+                issue_w(st + 1, cur ^ 1);
+            }
             if (st * BK6 + BK6 > d.K) {
                 // last step of a K that is not a multiple of 64: W chunks past K hold a clamped row start -- zero them (A is
                 // zero there, and 0 * inf would be nan)
@@ -636,7 +662,10 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
 #pragma unroll
-                        for (int i = 0; i < T; ++i) fb[i][ks][e] = kb + 2 * e < d.K ? fb[i][ks][e] : 0u;
+                        for (int i = 0; i < T; ++i) {
+                            fb[i][ks][e] = kb + 2 * e < d.K ? fb[i][ks][e] : 0u;
+                            if constexpr (A16) fa[i][ks][e] = kb + 2 * e < d.K ? fa[i][ks][e] : 0u;   // (as the fp32 A's zeros)
+                        }
                 }
             }
 #ifdef SKG_B16_NOMFMA                                 // (timing builds: the fragments are consumed by one add each)
@@ -658,7 +687,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
 #endif
             if (st + 1 < s_end) {
                 store_a(st + 1, cur ^ 1);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // W of step st + 1 landed (nothing else in flight)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // W (MODE 7: and A) of step st + 1 landed
                 if (st + 2 < s_end) load_a(st + 2);
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             }
@@ -1242,6 +1271,13 @@ __global__ __launch_bounds__(256, 2) void skg_gemm_b16_kernel(const skg_gemm_des
     skg_gemm_tile<EPI, 6, T>(d, blockIdx.x, smem, w16);
 }
 
+template <int EPI, int T>
+__global__ __launch_bounds__(256, 2) void skg_gemm_b16_a16_kernel(const skg_gemm_desc d, const uint16_t* a16,
+                                                                  const uint16_t* w16) {
+    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
+    skg_gemm_tile<EPI, 7, T>(d, blockIdx.x, smem, w16, a16);
+}
+
 struct skg_gemm_group_b16_args {
     skg_gemm_group_args g;
     const uint16_t* w16[SKG_GEMM_GROUP_MAX];
@@ -1624,6 +1660,50 @@ extern "C" int skg_gemm_b16_f32(const skg_gemm_desc* dh, const uint16_t* w16, vo
 #define SKG_LAUNCH(E)                                                                               \
     if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 1>), grid, block, 0, s, d, w16);         \
     else hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 2>), grid, block, 0, s, d, w16);
+    switch (d.epilogue) {
+        case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
+        case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;
+        case SKG_EPI_MUL_RELU:      SKG_LAUNCH(SKG_EPI_MUL_RELU) break;
+        case SKG_EPI_RELU_DOT:      SKG_LAUNCH(SKG_EPI_RELU_DOT) break;
+        case SKG_EPI_BIAS_RES_RELU: SKG_LAUNCH(SKG_EPI_BIAS_RES_RELU) break;
+    }
+#undef SKG_LAUNCH
+    if (d.split_k > 1) {
+        const int64_t total = (int64_t)d.M * d.N;
+        hipLaunchKernelGGL(skg_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d);
+    }
+    return skg_launch_status();
+}
+
+// bf16 A (MODE 7): the launch of skg_gemm_b16_f32 with A staged from a16 like W.  The checks run on a copy whose A is a16
+// (only skg_gemm_validate reads it there: non-null, aligned); the tile scale therefore follows the caller's descriptor.
+static std::atomic<long long> g_gemm_a16_launches;
+
+extern "C" void skg_gemm_b16_a16_launches(int64_t* out_host, int reset) {
+    if (out_host) *out_host = g_gemm_a16_launches.load(std::memory_order_relaxed);
+    if (reset) g_gemm_a16_launches.store(0, std::memory_order_relaxed);
+}
+
+extern "C" int skg_gemm_b16_a16_f32(const skg_gemm_desc* dh, const uint16_t* a16, const uint16_t* w16, void* stream) {
+    if (!dh || !a16) return SKG_E_ARG;
+    skg_gemm_desc d = *dh;
+    d.w_split = nullptr; d.a_exp = nullptr;                         // ignored here, as in skg_gemm_b16_f32
+    if (d.a_rows) return SKG_E_ARG;                                 // no gathers: A is staged by whole rows
+    if (!skg_aligned16(a16) || (d.lda & 7) || (d.K & 7)) return SKG_E_ALIGN;   // 16-byte DMA pieces of whole k-chunks
+    d.A = reinterpret_cast<const float*>(a16);
+    const int rc = skg_gemm_b16_check(d, w16);
+    if (rc) return rc;
+    if (d.M == 0) return 0;
+    const int T = skg_gemm_tile_scale(&d);
+    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
+    if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
+    dim3 grid((unsigned)nblk), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    skg_gemm_count(SKG_GEMM_PATH_BF16);
+    g_gemm_a16_launches.fetch_add(1, std::memory_order_relaxed);
+#define SKG_LAUNCH(E)                                                                                   \
+    if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 1>), grid, block, 0, s, d, a16, w16);    \
+    else hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 2>), grid, block, 0, s, d, a16, w16);
     switch (d.epilogue) {
         case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
         case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;

@@ -443,8 +443,22 @@ def dot_partials(M, N, K, lda, ldw):
     return n
 
 
+def bf16_rows(x, W):
+    """x ([M, ...] box features) as the bf16 A operand of a product with W for skg_gemm_b16_a16_f32, viewed [M, K]; None
+    unless x is a contiguous bf16 tensor whose rows are exactly W's width (no padding) and meet the entry's alignment."""
+    if x.dtype != torch.bfloat16 or not x.is_contiguous() or x.dim() < 2:
+        return None
+    x = x.reshape(x.shape[0], -1)
+    if x.shape[1] != W.shape[1] or x.shape[1] % 8 or x.data_ptr() % 16:
+        return None
+    return x
+
+
 def gemm(A, W, bias, C_out, M, N, K, epilogue, **kw):
-    """One skg_gemm_f32 launch (see gemm_desc for the keywords)."""
+    """One skg_gemm_f32 launch (see gemm_desc for the keywords).  A bf16 A (bf16_rows) goes to skg_gemm_b16_a16_f32, which
+    needs the bf16 weight twins (a Bf16Weights context)."""
+    if A.dtype == torch.bfloat16:
+        return _gemm_a16(A, W, bias, C_out, M, N, K, epilogue, **kw)
     d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
     w16 = weight_twin(W, kw.get("W_off", 0), kw.get("w_split"))
     keep_exp = enqueue_row_exponents(d, A.device) if d.w_split else None
@@ -468,6 +482,24 @@ def gemm(A, W, bias, C_out, M, N, K, epilogue, **kw):
 # re-swept at the end of round 4 (64-k steps, two stages in flight): 320 / 384 / 448 / 512 -> single 20 x 20 image 0.483-0.488 /
 # 0.474-0.482 / 0.502-0.504 / 0.498-0.499 ms, batches of 2 and 4 level, a stream of mixed shapes level (0.46-0.47 either way).
 SMALL_GROUP_BLOCKS = int(os.environ.get("SKG_SMALL_GROUP_BLOCKS") or 384)     # (the env override: developer sweeps)
+
+
+def _gemm_a16(A, W, bias, C_out, M, N, K, epilogue, **kw):
+    """gemm() with a bf16 A operand ([M, lda] bf16, lda % 8 == 0): one skg_gemm_b16_a16_f32 launch."""
+    w16 = weight_twin(W, kw.get("W_off", 0), kw.get("w_split"))
+    if not w16:
+        raise _capi.SkgError("a bf16 A operand needs the bf16 weight twins (inference_precision='bf16')")
+    d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
+    d.A = 0                                                  # (not read: the entry takes A from a16)
+    timed = GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or epilogue in GEMM_TIMER_EPI)
+    if timed:
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _capi.check(_capi.lib().skg_gemm_b16_a16_f32(C.byref(d), A.data_ptr(), w16, _stream()),
+                "skg_gemm_b16_a16_f32[%dx%dx%d epi %d]" % (M, N, K, epilogue))
+    if timed:
+        e1.record()
+        GEMM_TIMER.append((e0, e1, M, N, K, epilogue))
 
 
 def gemm_group(specs):
@@ -945,7 +977,10 @@ class HeadEngine:
         gfeat = torch.empty(Bf, Cf, **f32)
         _capi.check(lib.skg_global_avgpool_f32(feat3.data_ptr(), Bf, Cf, feat3.shape[2] * feat3.shape[3],
                                                gfeat.data_ptr(), st), "skg_global_avgpool_f32")
-        x0 = pooled.float().reshape(pooled.shape[0], -1)
+        # bf16 eval path: bf16 box features are box_head layer 1's A operand as they are (skg_gemm_b16_a16_f32, no fp32
+        # copy); everything else is widened to fp32 first
+        x16 = bf16_rows(pooled, pw.bh1_w) if (not training and self.eval_precision() == "bf16") else None
+        x0 = x16 if x16 is not None else pooled.float().reshape(pooled.shape[0], -1)
         if x0.shape[1] != pw.bh1_k:
             raise RuntimeError("mat1 and mat2 shapes cannot be multiplied (%dx%d and %dx%d)" % (
                 x0.shape[0], x0.shape[1], pw.bh1_k, 1024))

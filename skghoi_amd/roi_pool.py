@@ -8,10 +8,14 @@ torchvision is absent from the image; its published algorithm is restated (scale
 LevelMapper with canonical scale 224 / level 4 / eps 1e-6, roi_align with aligned=False).  Differentiable with respect to
 the feature maps (`skg_roi_align_bwd_f32`): the reference trains the detector's backbone and neck through this pooling
 (configures/hicodet/adamixer_transH_spatial_r50_main.py:109-127 gives them lr * 0.1).
+
+Half-precision maps (all levels bf16, or all fp16) are read in place by `skg_roi_align_x`, with the arithmetic of the
+fp32 kernel on the exactly widened values; `output_dtype` (default float32) picks the dtype of the pooled features, a half
+output being the fp32 result rounded once.  Any other mix of map dtypes is widened to fp32 first, as before.
 """
 import ctypes as C
 import math
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -19,6 +23,10 @@ from torch import nn, Tensor
 
 from . import _capi
 from .engine import _stream
+
+
+_HALF_CODES = {torch.float16: _capi.DTYPE_F16, torch.bfloat16: _capi.DTYPE_BF16}
+_OUT_CODES = {torch.float32: _capi.DTYPE_F32, torch.float16: _capi.DTYPE_F16, torch.bfloat16: _capi.DTYPE_BF16}
 
 
 def _level_args(feats, scales):
@@ -33,14 +41,26 @@ class _RoIAlignFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, rois, img, *feats):
-        scales, k_min, k_max, canon_s, canon_l, pooled, sampling = cfg
-        fs = [f.float().contiguous() for f in feats]
+        scales, k_min, k_max, canon_s, canon_l, pooled, sampling, out_dtype = cfg
+        dts = {f.dtype for f in feats}
+        map_code = _HALF_CODES.get(feats[0].dtype) if len(dts) == 1 else None
+        if map_code is None:                        # fp32, fp64, mixed: widened to fp32 first
+            map_code = _capi.DTYPE_F32
+            fs = [f.float().contiguous() for f in feats]
+        else:                                       # one half dtype: read in place (no fp32 copy of any level)
+            fs = [f.contiguous() for f in feats]
         n_rois, Cc = rois.shape[0], fs[0].shape[1]
-        out = torch.empty(n_rois, Cc, pooled, pooled, device=rois.device, dtype=torch.float32)
+        out = torch.empty(n_rois, Cc, pooled, pooled, device=rois.device, dtype=out_dtype)
         ptrs, Hs, Ws, sc = _level_args(fs, scales)
-        _capi.check(_capi.lib().skg_roi_align_f32(ptrs, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s), int(canon_l),
-                                                  rois.data_ptr(), img.data_ptr(), n_rois, pooled, sampling,
-                                                  out.data_ptr(), _stream()), "skg_roi_align_f32")
+        if map_code == _capi.DTYPE_F32 and out_dtype == torch.float32:
+            _capi.check(_capi.lib().skg_roi_align_f32(ptrs, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s),
+                                                      int(canon_l), rois.data_ptr(), img.data_ptr(), n_rois, pooled,
+                                                      sampling, out.data_ptr(), _stream()), "skg_roi_align_f32")
+        else:
+            _capi.check(_capi.lib().skg_roi_align_x(ptrs, map_code, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s),
+                                                    int(canon_l), rois.data_ptr(), img.data_ptr(), n_rois, pooled,
+                                                    sampling, out.data_ptr(), _OUT_CODES[out_dtype], _stream()),
+                        "skg_roi_align_x")
         ctx.cfg, ctx.rois, ctx.img = cfg, rois, img
         ctx.shapes = [tuple(f.shape) for f in fs]
         ctx.dtypes = [f.dtype for f in feats]
@@ -48,7 +68,7 @@ class _RoIAlignFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        scales, k_min, k_max, canon_s, canon_l, pooled, sampling = ctx.cfg
+        scales, k_min, k_max, canon_s, canon_l, pooled, sampling, _ = ctx.cfg
         dout = dout.float().contiguous()
         dfs = [torch.zeros(sh, device=dout.device, dtype=torch.float32) for sh in ctx.shapes]
         ptrs, Hs, Ws, sc = _level_args(dfs, scales)
@@ -61,8 +81,14 @@ class _RoIAlignFn(torch.autograd.Function):
 
 class MultiScaleRoIAlign(nn.Module):
     def __init__(self, featmap_names: List[str], output_size, sampling_ratio: int, *, canonical_scale: int = 224,
-                 canonical_level: int = 4):
+                 canonical_level: int = 4, output_dtype: Optional[torch.dtype] = None):
+        """output_dtype: dtype of the pooled features -- None (float32, the default), torch.float32, torch.bfloat16 or
+        torch.float16."""
         super().__init__()
+        if output_dtype is not None and output_dtype not in _OUT_CODES:
+            raise ValueError("output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16 (got %r)"
+                             % (output_dtype,))
+        self.output_dtype = output_dtype
         if isinstance(output_size, (tuple, list)):
             if output_size[0] != output_size[1]:
                 raise ValueError("only square outputs are supported (the reference uses 7x7)")
@@ -74,6 +100,10 @@ class MultiScaleRoIAlign(nn.Module):
         self.canonical_level = canonical_level
         self.scales = None
         self.k_min = self.k_max = None
+
+    def _out_dtype(self):
+        dt = getattr(self, "output_dtype", None)            # (modules pickled before the keyword existed: float32)
+        return torch.float32 if dt is None else dt
 
     @staticmethod
     def infer_scale(feature_hw, original_hw) -> float:
@@ -99,14 +129,14 @@ class MultiScaleRoIAlign(nn.Module):
         n_rois = sum(n_per)
         Cc = feats[0].shape[1]
         if n_rois == 0:
-            return torch.empty(0, Cc, self.output_size, self.output_size, device=dev, dtype=torch.float32)
+            return torch.empty(0, Cc, self.output_size, self.output_size, device=dev, dtype=self._out_dtype())
         rois = torch.cat([b.reshape(-1, 4) for b in boxes]).detach().float().contiguous()
         img = torch.repeat_interleave(torch.arange(len(boxes), dtype=torch.int32),
                                       torch.tensor(n_per)).to(dev, non_blocking=True)
         L = len(feats)
         k_min, k_max = (self.k_min, self.k_max) if L > 1 else (0, 0)
         cfg = (list(self.scales), k_min, k_max, self.canonical_scale, self.canonical_level, self.output_size,
-               self.sampling_ratio)
+               self.sampling_ratio, self._out_dtype())
         if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
             return _RoIAlignFn.apply(cfg, rois, img, *feats)
         return _RoIAlignFn.forward(_NoCtx(), cfg, rois, img, *feats)

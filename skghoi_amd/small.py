@@ -44,8 +44,8 @@ import numpy as np
 import torch
 
 from . import _capi, layout, transh
-from .engine import Preprocessed, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_group, pick_split_k, _stream, \
-    weight_twin
+from .engine import Preprocessed, bf16_rows, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_group, pick_split_k, \
+    _stream, weight_twin
 
 META_WORDS = layout.META_DTYPE.itemsize // 4
 
@@ -531,8 +531,11 @@ class SmallBatchRunner:
         f3 = feat3 if (feat3.dtype == torch.float32 and feat3.is_contiguous()) else feat3.float().contiguous()
         _capi.check(lib.skg_global_avgpool_f32(f3.data_ptr(), f3.shape[0], f3.shape[1], f3.shape[2] * f3.shape[3],
                                                p.gfeat.data_ptr(), _stream()), "skg_global_avgpool_f32")
-        x0 = pooled.reshape(pooled.shape[0], -1)
-        if x0.dtype != torch.float32:
+        # bf16 eval path: bf16 box features go to the bf16-A GEMM as they are (no fp32 copy); the choice follows each call's
+        # dtype (this launch runs eagerly, ahead of the replay: the plan key holds no dtype)
+        x16 = bf16_rows(pooled, pw.bh1_w) if eng.eval_precision() == "bf16" else None
+        x0 = pooled.reshape(pooled.shape[0], -1) if x16 is None else x16
+        if x0.dtype != torch.float32 and x16 is None:
             x0 = x0.float()
         if p.x0_pad is not None:
             p.x0_pad[:n_act, :x0.shape[1]] = x0
@@ -548,7 +551,10 @@ class SmallBatchRunner:
         p.bh1_desc.M = n_act                       # plans) its row count
         if p.bh1_desc.w_split:
             p.bh1_exp = enqueue_row_exponents(p.bh1_desc, x0.device)
-        if p.bh1_w16:
+        if p.bh1_w16 and x16 is not None:
+            _capi.check(lib.skg_gemm_b16_a16_f32(C.byref(p.bh1_desc), x16.data_ptr(), p.bh1_w16, _stream()),
+                        "skg_gemm_b16_a16_f32[box_head 1]")
+        elif p.bh1_w16:
             _capi.check(lib.skg_gemm_b16_f32(C.byref(p.bh1_desc), p.bh1_w16, _stream()), "skg_gemm_b16_f32[box_head 1]")
         else:
             _capi.check(lib.skg_gemm_f32(C.byref(p.bh1_desc), _stream()), "skg_gemm_f32[box_head 1]")

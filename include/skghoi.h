@@ -260,11 +260,33 @@ int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uint16_t* cons
 int skg_gemm_b16_a16_f32(const skg_gemm_desc* desc_host, const uint16_t* a16, const uint16_t* w16, void* stream);
 /* Launches of skg_gemm_b16_a16_f32 since the last reset (reset != 0 zeroes the count after the read).  For tests.   */
 void skg_gemm_b16_a16_launches(int64_t* out_host, int reset);
+/* bf16 activations (inference_activations "bf16"): the bf16 launches with an optional bf16 A and an optional bf16 output.
+ *   w16  required: the bf16 twin, rules of skg_gemm_b16_f32.
+ *   a16  optional: bf16 A, rules of skg_gemm_b16_a16_f32 (d.A is then not read).
+ *   c16  optional: wherever the launch stores a value v into C[orow, col] it stores RNE-bf16(v) into
+ *        c16[orow * ldc16 + col] (ldc16 >= d.N elements), by the conversion the A staging uses -- so a later launch that
+ *        reads the panel as a16 sees the operand bits it would have made from the fp32 panel.  out_rows applies as to C.
+ *        With c16 given d.C may be NULL (bf16 only) or not (both are written).  C_raw, dot_partial and split_ws stay fp32;
+ *        a split-K launch writes c16 from its reduce kernel, from the same fp32 sum.  ldc16 % 4 == 0 with an 8-byte
+ *        aligned c16 takes 8-byte stores, anything else the scalar path.  Not with SKG_EPI_RELU_DOT (SKG_E_ARG).
+ * Tile scale, split-K and dot_partial slab count depend on the descriptor only, exactly as for skg_gemm_b16_f32 /
+ * skg_gemm_group_b16_f32: the fp32 result of a launch does not depend on whether A or C is bf16.  Members of a group mix
+ * freely.  All checks return a negative status before anything is launched: NULL io / w16, neither C nor c16 (RELU_DOT apart, whose C is optional), c16 with
+ * RELU_DOT, ldc16 < N (SKG_E_ARG), the a16 rules.  Counted as SKG_GEMM_PATH_BF16 and by skg_gemm_b16_x_counts (launches,
+ * members with a16, members with c16; members of M == 0 are not counted); skg_gemm_b16_a16_launches does not move.  */
+typedef struct {
+    const uint16_t* w16;
+    const uint16_t* a16;
+    uint16_t*       c16; int64_t ldc16;
+} skg_gemm_b16_io;
+int  skg_gemm_b16_x(const skg_gemm_desc* desc_host, const skg_gemm_b16_io* io, void* stream);
+int  skg_gemm_group_b16_x(const skg_gemm_desc* descs_host, const skg_gemm_b16_io* ios, int n, void* stream);
+void skg_gemm_b16_x_counts(int64_t* out3, int reset);
 /* Launches per main loop of the skg_gemm_* entry points since the last reset (out_host: SKG_GEMM_PATHS counts, by
  * SKG_GEMM_PATH_*; reset != 0 zeroes them after the read).  Process-wide, for tests and profiles.                   */
 #define SKG_GEMM_PATH_EXACT  0          /* exact fp32 loops (register-staged, DMA-staged, 64 x 64 latency loops)      */
 #define SKG_GEMM_PATH_FP16X2 1          /* fp16x2 split-operand loop                                                  */
-#define SKG_GEMM_PATH_BF16   2          /* bf16 loop (skg_gemm_b16_f32, skg_gemm_group_b16_f32)                       */
+#define SKG_GEMM_PATH_BF16   2          /* bf16 loop (skg_gemm_b16_f32, _a16_f32, _b16_x and the grouped forms)       */
 #define SKG_GEMM_PATH_ROUTED 3          /* mid-size fp32 launches routed to skg_gemmx_f32                             */
 #define SKG_GEMM_PATHS       4
 void skg_gemm_path_counts(int64_t* out_host, int reset);
@@ -287,6 +309,13 @@ typedef struct { int32_t small_mode, small_tiles, route_tiles, khalves_blocks; }
 int skg_concat_entity_f32(const float* enc, int64_t ld_enc, const int32_t* enc_row, const float* ent,
                           const int32_t* ent_img, const int32_t* ent_row, int rows, float* out, int64_t out_ld,
                           void* stream);
+/* Output-dtype twins of the row-wise producers (this one, skg_rows_mul_relu_x, skg_graph_aggregate_x, skg_layernorm2_x):
+ * the arguments of the _f32 entry plus out_dtype = SKG_DTYPE_F32 (the _f32 entry itself: it is a wrapper of this one) or
+ * SKG_DTYPE_BF16 (out holds bf16 elements, 8-byte aligned, same leading dimension in elements: the fp32 result rounded
+ * once, round to nearest even); SKG_DTYPE_F16 returns SKG_E_ARG.  Inputs stay fp32.                                  */
+int skg_concat_entity_x(const float* enc, int64_t ld_enc, const int32_t* enc_row, const float* ent,
+                        const int32_t* ent_img, const int32_t* ent_row, int rows, void* out, int64_t out_ld,
+                        int out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * bf16 dense layer (training configuration "bf16"): C = act(A W^T + bias) with A [M,K], W [N,K] in bf16 (raw uint16
@@ -312,6 +341,9 @@ int skg_transpose_f32(const float* in, int64_t ld_in, int rows, int cols, float*
 int skg_rows_mul_relu_f32(const float* P, const int32_t* p_idx, int64_t ldp, const float* Q, const int32_t* q_idx,
                           int64_t ldq, const float* mbias, const float* F, const int32_t* f_idx, int64_t ldf,
                           int rows, int cols, float* out, int64_t ldo, void* stream);
+int skg_rows_mul_relu_x(const float* P, const int32_t* p_idx, int64_t ldp, const float* Q, const int32_t* q_idx,
+                        int64_t ldq, const float* mbias, const float* F, const int32_t* f_idx, int64_t ldf,
+                        int rows, int cols, void* out, int64_t ldo, int out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Bipartite message aggregation (HEAD:897-925).  adjacency logit of grid row r = adj_bias + sum_k dot_partial[k][r].
@@ -324,6 +356,11 @@ int skg_graph_aggregate_f32(const float* dot_partial, int n_partial, int64_t par
                             const skg_image_meta* meta, int n_active, const int32_t* hum_img, const int32_t* node_img,
                             int sum_h, int sum_n, const float* T_os, const float* T_so, int64_t ldt, int cols,
                             float* U, float* V, int64_t ldu, float* adj_out, void* stream);
+/* out_dtype: element type of U and V only; T_os / T_so, the softmax arithmetic and adj_out stay fp32.                */
+int skg_graph_aggregate_x(const float* dot_partial, int n_partial, int64_t partial_ld, float adj_bias,
+                          const skg_image_meta* meta, int n_active, const int32_t* hum_img, const int32_t* node_img,
+                          int sum_h, int sum_n, const float* T_os, const float* T_so, int64_t ldt, int cols,
+                          void* U, void* V, int64_t ldu, float* adj_out, int out_dtype, void* stream);
 
 /* out = LayerNorm(x) * gamma + beta over `cols` (= 1024) columns, eps 1e-5 (HEAD:658-659, 912-914, 923-925). */
 int skg_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const float* beta, int rows, int cols,
@@ -333,6 +370,9 @@ int skg_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const flo
 int skg_layernorm2_f32(const float* x0, int64_t ldx0, const float* gamma0, const float* beta0, int rows0, float* out0,
                        int64_t ldo0, const float* x1, int64_t ldx1, const float* gamma1, const float* beta1, int rows1,
                        float* out1, int64_t ldo1, int cols, float eps, void* stream);
+int skg_layernorm2_x(const float* x0, int64_t ldx0, const float* gamma0, const float* beta0, int rows0, void* out0,
+                     int64_t ldo0, const float* x1, int64_t ldx1, const float* gamma1, const float* beta1, int rows1,
+                     void* out1, int64_t ldo1, int cols, float eps, int out_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * compute_prior_scores (HEAD:721-767) + InteractionHead.postprocess (HEAD:237-337), table driven.

@@ -34,6 +34,11 @@ class GemmDesc(C.Structure):
                 ("a_exp", _vp)]
 
 
+class GemmB16Io(C.Structure):
+    """Mirror of skg_gemm_b16_io: bf16 twin of W, optional bf16 A, optional bf16 output (skg_gemm_b16_x)."""
+    _fields_ = [("w16", _vp), ("a16", _vp), ("c16", _vp), ("ldc16", _i64)]
+
+
 class GemmXDesc(C.Structure):
     """Mirror of skg_gemmx_desc."""
     _fields_ = [("A", _vp), ("a_sm", _i64), ("a_sk", _i64), ("B", _vp), ("b_sn", _i64), ("b_sk", _i64),
@@ -138,6 +143,9 @@ PROTOTYPES = {
     "skg_gemm_path_counts": (None, [C.POINTER(_i64), C.c_int]),
     "skg_gemm_b16_a16_f32": (C.c_int, [C.POINTER(GemmDesc), _vp, _vp, _vp]),
     "skg_gemm_b16_a16_launches": (None, [C.POINTER(_i64), C.c_int]),
+    "skg_gemm_b16_x": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmB16Io), _vp]),
+    "skg_gemm_group_b16_x": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmB16Io), C.c_int, _vp]),
+    "skg_gemm_b16_x_counts": (None, [C.POINTER(_i64), C.c_int]),
     "skg_row_exponents_f32": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, _vp]),
     "skg_adamw_f32": (C.c_int, [_vp, C.c_int] + [C.c_double] * 7 + [_vp, C.c_int, _vp]),
     "skg_ctx_set_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),
@@ -151,6 +159,13 @@ PROTOTYPES = {
     "skg_transpose_bf16": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _i64, _vp]),
     "skg_transpose_f32": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _i64, _vp]),
     "skg_concat_entity_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _i64, _vp]),
+    "skg_concat_entity_x": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _i64, C.c_int, _vp]),
+    "skg_rows_mul_relu_x": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp,
+                                      _i64, C.c_int, _vp]),
+    "skg_graph_aggregate_x": (C.c_int, [_vp, C.c_int, _i64, _f32, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp,
+                                        _vp, _i64, C.c_int, _vp, _vp, _i64, _vp, C.c_int, _vp]),
+    "skg_layernorm2_x": (C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _vp, _i64, _vp, _i64, _vp, _vp, C.c_int, _vp, _i64,
+                                   C.c_int, _f32, C.c_int, _vp]),
     "skg_rows_mul_relu_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _vp,
                                         _i64, _vp]),
     "skg_graph_aggregate_f32": (C.c_int, [_vp, C.c_int, _i64, _f32, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp,

@@ -314,6 +314,7 @@ class _Ready:
 
 
 _INFERENCE_PRECISIONS = (None, "fp32", "fp16x2", "bf16")
+_INFERENCE_ACTIVATIONS = (None, "fp32", "bf16")
 
 
 class InteractionHead(Module):
@@ -340,6 +341,15 @@ class InteractionHead(Module):
           weights carry bf16-grade error; index / prediction / object / boxes / prior do not depend on any GEMM and
           stay bit-identical to the exact path.
         Training and validation (eval with targets) are not affected.
+      inference_activations: Optional[str] = None -- storage type of the eval forward's intermediate panels that ONLY feed
+        the next matrix product (box_head / spatial_head hidden layers, S, X, the bf16 copy of GH / GO, T, U, V, h_node,
+        node, Tg, Tp: DESIGN.md section 6); a plain attribute like inference_precision:
+        None / "fp32" (default): fp32, as before, bit for bit and launch for launch.
+        "bf16": those panels are written and read as bf16 -- half their bytes in HBM, and the consuming product stages
+          them straight into LDS.  Needs an eval path that resolves to "bf16" (engine() raises ValueError otherwise).
+          Every result is bit-identical to inference_activations=None under inference_precision="bf16": the consumer
+          rounded these operands to bf16 anyway, and the producer stores them with the same conversion.
+        Training, validation (eval with targets), the fp32 / fp16x2 paths and engine.debug never take it.
       reference_quirks: bool = True -- reproduce (a) the node-offset bug on skipped images and (b) the
         eval-mode label-list zip with skipped images in a batch > 1 (HEAD:298-310: truncated results / IndexError).
         With False every image gets its own (possibly empty) result.
@@ -349,7 +359,7 @@ class InteractionHead(Module):
                  box_pair_predictor: Module, human_idx: int, num_classes: int, box_nms_thresh: float = 0.5,
                  box_score_thresh: float = 0.2, max_human: int = 15, max_object: int = 15,
                  distributed: bool = False, reference_quirks: bool = True, precision: str = "fp32",
-                 inference_precision: Optional[str] = None) -> None:
+                 inference_precision: Optional[str] = None, inference_activations: Optional[str] = None) -> None:
         super().__init__()
         self.box_roi_pool = box_roi_pool
         self.box_pair_head = box_pair_head
@@ -369,6 +379,9 @@ class InteractionHead(Module):
         if inference_precision not in _INFERENCE_PRECISIONS:
             raise ValueError("inference_precision must be None, 'fp32', 'fp16x2' or 'bf16'")
         self.inference_precision = inference_precision
+        if inference_activations not in _INFERENCE_ACTIVATIONS:
+            raise ValueError("inference_activations must be None, 'fp32' or 'bf16'")
+        self.inference_activations = inference_activations
         self.fused_training = True      # False: training through autograd over per-layer Functions (skghoi_amd/train_graph.py)
         self.grad_mode = "autograd"     # "direct": the fused step writes p.grad itself (skghoi_amd/train_fused.py, StepFn)
         self._engine = None
@@ -409,6 +422,13 @@ class InteractionHead(Module):
         if ip not in _INFERENCE_PRECISIONS:
             raise ValueError("inference_precision must be None, 'fp32', 'fp16x2' or 'bf16'")
         e.inference_precision = ip
+        ia = getattr(self, "inference_activations", None)
+        if ia not in _INFERENCE_ACTIVATIONS:
+            raise ValueError("inference_activations must be None, 'fp32' or 'bf16'")
+        if ia == "bf16" and e.eval_precision() != "bf16":
+            raise ValueError("inference_activations='bf16' needs the bf16 eval path (inference_precision='bf16'); "
+                             "inference_precision=%r with precision=%r resolves to %r" % (ip, self.precision, e.eval_precision()))
+        e.inference_activations = ia
         return e
 
     # ------------------------------------------------------------------------------------------ HEAD:92-151

@@ -21,6 +21,9 @@
 //     row gather; also instantiated with 64x64 tiles for grids that would leave most CUs idle.
 //   * MODE 0, exact, register staged (any K % 4 == 0, gathered A rows, grouped launches, MODE 2's fallback): rows padded
 //     to 20 dwords, loads unconditional and masked only when written to LDS.
+//   * MODE 6 / 7, bf16 operands on v_mfma_f32_32x32x16_bf16 (inference_precision "bf16"): W from its bf16 twin, A fp32
+//     rounded in registers (6) or given in bf16 and DMA-staged like W (7); with C16 the epilogue also stores RNE-bf16 of
+//     every output value (inference_activations "bf16": the next product's bf16 A).  See the comments at the loop.
 //   * Block -> tile map: XCD groups (see skg_gemm_map) keep a <= 2 MiB W slice in each XCD's private L2 and have the A
 //     panel fetched by NG XCDs instead of 8.
 //   * Epilogue: accumulators are transposed through LDS so that every lane owns 4 consecutive columns of a row; bias,
@@ -47,6 +50,11 @@ __device__ __forceinline__ uint32_t skg_pack_bf16x2(float a, float b) {
     const f32x2_t v = {a, b};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
+// four consecutive columns of a bf16 output row (p 8-byte aligned) / one element, by the same conversion
+__device__ __forceinline__ void skg_store_bf16x4(uint16_t* p, float a, float b, float c, float e) {
+    *reinterpret_cast<uint2*>(p) = make_uint2(skg_pack_bf16x2(a, b), skg_pack_bf16x2(c, e));
+}
+__device__ __forceinline__ void skg_store_bf16(uint16_t* p, float a) { *p = (uint16_t)(skg_pack_bf16x2(a, 0.f) & 0xffffu); }
 
 #define BM 128
 #define BN 128
@@ -125,9 +133,14 @@ __device__ __forceinline__ const char* skg_uniform_ptr(const char* p) {
 // 6 bf16 operands on the bf16 MFMA, 7 the same with A given in bf16 (3 / 4 / 5: the 64 x 64 latency loops).
 // MODE 6: bf16 operands (w16 = bf16 twin of W with W's element indexing), fp32 accumulation on the bf16 MFMA.
 // MODE 7: MODE 6 with A read from a16 (bf16, d.lda elements per row) instead of d.A, staged like W.
-template <int EPI_T, int MODE, int T>
+// C16 (MODE 6 / 7, skg_gemm_b16_x): every value stored into C[orow, col] is also -- with d.C == NULL: only -- stored as
+// RNE-bf16 into c16[orow * ldc16 + col], by the conversion the A staging uses (skg_pack_bf16x2): the next product's a16.
+// The C16 = false instantiations hold none of that code.
+template <int EPI_T, int MODE, int T, bool C16 = false>
 __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_id, float* smem,
-                                              const uint16_t* w16 = nullptr, const uint16_t* a16 = nullptr) {
+                                              const uint16_t* w16 = nullptr, const uint16_t* a16 = nullptr,
+                                              uint16_t* c16 = nullptr, int64_t ldc16 = 0) {
+    static_assert(!C16 || MODE == 6 || MODE == 7, "the bf16 output belongs to the bf16 loops");
     static_assert(MODE == 1 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 6 || MODE == 7 || T == 2, "only the DMA-staged, the latency and the bf16 loops have a 64 x 64 variant");
     static_assert((MODE != 3 && MODE != 4 && MODE != 5) || T == 1, "the latency loops are 64 x 64 tiles");
     constexpr bool GLDS = MODE == 1;
@@ -997,7 +1010,8 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                          (skg_aligned16_dev(d.P) && skg_aligned16_dev(d.Q) && skg_aligned16_dev(d.mbias) &&
                           skg_aligned16_dev(d.C_raw) && ((d.ldp | d.ldq | d.ldc_raw) & 3) == 0)) &&
                         (EPI != SKG_EPI_BIAS_RES_RELU || (skg_aligned16_dev(d.res) && (d.ldres & 3) == 0)) &&
-                        (EPI != SKG_EPI_RELU_DOT || skg_aligned16_dev(d.dot_w));
+                        (EPI != SKG_EPI_RELU_DOT || skg_aligned16_dev(d.dot_w)) &&
+                        (!C16 || ((ldc16 & 3) == 0 && (reinterpret_cast<uintptr_t>(c16) & 7u) == 0));
     // ---- fast path: tile entirely inside the matrix, everything 16-byte aligned, no split-K.  Column-dependent
     // operands (bias, multiplier bias, dot weights) are loaded once per lane; rows advance by pointer increments.
     const bool interior = vec_ok && d.split_k <= 1 && (m0 + TBM <= d.M) && (n0 + TBN <= d.N);
@@ -1063,8 +1077,9 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                         const float4 t = *reinterpret_cast<const float4*>(d.Q + (int64_t)qi * d.ldq + col);
                         m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
                     }
-                    *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) =
-                        make_float4(fmaxf(v.x * m.x, 0.f), fmaxf(v.y * m.y, 0.f), fmaxf(v.z * m.z, 0.f), fmaxf(v.w * m.w, 0.f));
+                    const float4 o = make_float4(fmaxf(v.x * m.x, 0.f), fmaxf(v.y * m.y, 0.f), fmaxf(v.z * m.z, 0.f), fmaxf(v.w * m.w, 0.f));
+                    if (!C16 || d.C) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = o;
+                    if constexpr (C16) { if (c16) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, o.x, o.y, o.z, o.w); }
                     continue;
                 }
                 if (orow < 0) continue;
@@ -1074,7 +1089,8 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                     const float4 t = *reinterpret_cast<const float4*>(d.res + (int64_t)row * d.ldres + col);
                     v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
                 }
-                *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = v;
+                if (!C16 || d.C) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = v;
+                if constexpr (C16) { if (c16) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, v.x, v.y, v.z, v.w); }
             }
         }
         return;
@@ -1152,8 +1168,9 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                     if (d.mbias) { const float4 t = *reinterpret_cast<const float4*>(d.mbias + col); m[0] = t.x; m[1] = t.y; m[2] = t.z; m[3] = t.w; }
                     if (d.P) { const float4 t = *reinterpret_cast<const float4*>(d.P + (int64_t)pi * d.ldp + col); m[0] += t.x; m[1] += t.y; m[2] += t.z; m[3] += t.w; }
                     if (d.Q) { const float4 t = *reinterpret_cast<const float4*>(d.Q + (int64_t)qi * d.ldq + col); m[0] += t.x; m[1] += t.y; m[2] += t.z; m[3] += t.w; }
-                    *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) =
-                        make_float4(fmaxf(v[0] * m[0], 0.f), fmaxf(v[1] * m[1], 0.f), fmaxf(v[2] * m[2], 0.f), fmaxf(v[3] * m[3], 0.f));
+                    const float4 o = make_float4(fmaxf(v[0] * m[0], 0.f), fmaxf(v[1] * m[1], 0.f), fmaxf(v[2] * m[2], 0.f), fmaxf(v[3] * m[3], 0.f));
+                    if constexpr (C16) { v[0] = o.x; v[1] = o.y; v[2] = o.z; v[3] = o.w; }
+                    else *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = o;
                 } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
@@ -1161,10 +1178,14 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                         float mm = d.mbias ? d.mbias[col + c] : 0.f;
                         if (d.P) mm += d.P[(int64_t)pi * d.ldp + col + c];
                         if (d.Q) mm += d.Q[(int64_t)qi * d.ldq + col + c];
-                        d.C[(int64_t)orow * d.ldc + col + c] = fmaxf(v[c] * mm, 0.f);
+                        const float o = fmaxf(v[c] * mm, 0.f);
+                        if constexpr (C16) v[c] = o;
+                        else d.C[(int64_t)orow * d.ldc + col + c] = o;
                     }
                 }
-                continue;
+                // C16: v now holds the outputs, and the stores at the end of the row (one copy of them keeps the
+                // run-time-epilogue body small enough to unroll) write C and c16
+                if constexpr (!C16) continue;
             }
             if (orow < 0) continue;
             if (EPI == SKG_EPI_BIAS_RELU || EPI == SKG_EPI_BIAS_RES_RELU) {
@@ -1180,10 +1201,20 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                     for (int c = 0; c < 4; ++c) if (col + c < d.N) v[c] += d.res[(int64_t)row * d.ldres + col + c];
                 }
             }
-            if (full) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
-            else
+            if (!C16 || d.C) {
+                if (full) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
+                else
 #pragma unroll
-                for (int c = 0; c < 4; ++c) if (col + c < d.N) d.C[(int64_t)orow * d.ldc + col + c] = v[c];
+                    for (int c = 0; c < 4; ++c) if (col + c < d.N) d.C[(int64_t)orow * d.ldc + col + c] = v[c];
+            }
+            if constexpr (C16) {
+                if (c16) {
+                    if (full) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, v[0], v[1], v[2], v[3]);
+                    else
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) if (col + c < d.N) skg_store_bf16(c16 + (int64_t)orow * ldc16 + col + c, v[c]);
+                }
+            }
         }
     }
 }
@@ -1294,7 +1325,9 @@ __global__ __launch_bounds__(256, 2) void skg_gemm_group_b16_kernel(const skg_ge
 }
 
 // Split-K reduction: adds the slices in slice order (deterministic) and applies the plain epilogues.
-__device__ __forceinline__ void skg_splitk_reduce_one(const skg_gemm_desc& d, int64_t i) {
+// c16 (skg_gemm_b16_x): the same fp32 sum also -- with d.C == NULL: only -- stored as RNE-bf16 into c16[orow * ldc16 + col]
+__device__ __forceinline__ void skg_splitk_reduce_one(const skg_gemm_desc& d, int64_t i, uint16_t* c16 = nullptr,
+                                                      int64_t ldc16 = 0) {
     const int64_t total = (int64_t)d.M * d.N;
     if (i >= total) return;
     const int row = (int)(i / d.N), col = (int)(i % d.N);
@@ -1314,7 +1347,9 @@ __device__ __forceinline__ void skg_splitk_reduce_one(const skg_gemm_desc& d, in
     if (d.epilogue == SKG_EPI_BIAS_RELU || d.epilogue == SKG_EPI_BIAS_RES_RELU) v = fmaxf(v, 0.f);
     if (d.epilogue == SKG_EPI_BIAS_RES_RELU) v += d.res[(int64_t)row * d.ldres + col];
     const int orow = d.out_rows ? d.out_rows[row] : row;
-    if (orow >= 0) d.C[(int64_t)orow * d.ldc + col] = v;
+    if (orow < 0) return;
+    if (d.C) d.C[(int64_t)orow * d.ldc + col] = v;
+    if (c16) skg_store_bf16(c16 + (int64_t)orow * ldc16 + col, v);
 }
 
 __global__ __launch_bounds__(256) void skg_splitk_reduce_kernel(const skg_gemm_desc d) {
@@ -1761,6 +1796,188 @@ extern "C" int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uin
     if (r.n) {
         for (int i = r.n; i <= SKG_GEMM_GROUP_MAX; ++i) r.start[i] = (int)rblocks;
         hipLaunchKernelGGL(skg_splitk_reduce_group_kernel, dim3((unsigned)rblocks), dim3(256), 0, (hipStream_t)stream, r);
+    }
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ bf16 activations (skg_gemm_b16_x)
+// The bf16 launches with an optional bf16 A (a16, MODE 7) and an optional bf16 output (c16, beside or instead of d.C): what
+// inference_activations = "bf16" stores the GEMM-only panels of the eval forward in.  The launch shape -- tile scale, block
+// map, split-K -- is that of skg_gemm_b16_f32 / skg_gemm_group_b16_f32 on the same descriptor: it never depends on whether A
+// or C is bf16, so a chain of these launches reproduces the fp32-panel chain bit for bit (the consumer would have rounded
+// the fp32 panel with the conversion the producer stored it with).
+template <int EPI, int MODE, int T>
+__global__ __launch_bounds__(256, 2) void skg_gemm_b16x_kernel(const skg_gemm_desc d, const uint16_t* a16, const uint16_t* w16,
+                                                               uint16_t* c16, int64_t ldc16) {
+    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
+    skg_gemm_tile<EPI, MODE, T, true>(d, blockIdx.x, smem, w16, a16, c16, ldc16);
+}
+
+struct skg_gemm_group_b16x_args {
+    skg_gemm_group_args g;
+    const uint16_t* w16[SKG_GEMM_GROUP_MAX];
+    const uint16_t* a16[SKG_GEMM_GROUP_MAX];
+    uint16_t* c16[SKG_GEMM_GROUP_MAX];
+    int64_t ldc16[SKG_GEMM_GROUP_MAX];
+};
+
+// members mix freely: the main loop (MODE 6 / 7) is picked per member on a workgroup-uniform flag
+template <int T>
+__global__ __launch_bounds__(256, 2) void skg_gemm_group_b16x_kernel(const skg_gemm_group_b16x_args a) {
+    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
+    int k = 0;
+#pragma unroll
+    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
+        if (t < a.g.n && (int)blockIdx.x >= a.g.start[t]) k = t;
+    if (a.a16[k]) skg_gemm_tile<-1, 7, T, true>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k], a.a16[k], a.c16[k], a.ldc16[k]);
+    else skg_gemm_tile<-1, 6, T, true>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k], nullptr, a.c16[k], a.ldc16[k]);
+}
+
+__global__ __launch_bounds__(256) void skg_splitk_reduce_x_kernel(const skg_gemm_desc d, uint16_t* c16, int64_t ldc16) {
+    skg_splitk_reduce_one(d, (int64_t)blockIdx.x * 256 + threadIdx.x, c16, ldc16);
+}
+
+struct skg_splitk_reduce_group_x_args {
+    skg_gemm_group_args g;
+    uint16_t* c16[SKG_GEMM_GROUP_MAX];
+    int64_t ldc16[SKG_GEMM_GROUP_MAX];
+};
+
+__global__ __launch_bounds__(256) void skg_splitk_reduce_group_x_kernel(const skg_splitk_reduce_group_x_args a) {
+    int k = 0;
+#pragma unroll
+    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
+        if (t < a.g.n && (int)blockIdx.x >= a.g.start[t]) k = t;
+    skg_splitk_reduce_one(a.g.d[k], (int64_t)(blockIdx.x - a.g.start[k]) * 256 + threadIdx.x, a.c16[k], a.ldc16[k]);
+}
+
+// launches, members with a16, members with c16 (members of M == 0 launch nothing and are not counted)
+static std::atomic<long long> g_gemm_b16x[3];
+
+extern "C" void skg_gemm_b16_x_counts(int64_t* out3, int reset) {
+    for (int i = 0; i < 3; ++i) {
+        if (out3) out3[i] = g_gemm_b16x[i].load(std::memory_order_relaxed);
+        if (reset) g_gemm_b16x[i].store(0, std::memory_order_relaxed);
+    }
+}
+
+// Checks one member and prepares the descriptor the kernels get: w_split / a_exp cleared, as in skg_gemm_b16_f32.  The
+// generic checks run on a copy whose A is a16 and whose C is c16 where those stand in (only non-null / aligned is asked).
+static int skg_gemm_b16x_check(skg_gemm_desc& d, const skg_gemm_b16_io* io) {
+    if (!io || !io->w16) return SKG_E_ARG;
+    d.w_split = nullptr; d.a_exp = nullptr;
+    if (!d.C && !io->c16 && d.epilogue != SKG_EPI_RELU_DOT) return SKG_E_ARG;     // (RELU_DOT: C is optional, as ever)
+    if (io->c16 && (d.epilogue == SKG_EPI_RELU_DOT || io->ldc16 < d.N)) return SKG_E_ARG;
+    skg_gemm_desc v = d;
+    if (io->a16) {
+        if (d.a_rows) return SKG_E_ARG;                                 // no gathers: A is staged by whole rows
+        if (!skg_aligned16(io->a16) || (d.lda & 7) || (d.K & 7)) return SKG_E_ALIGN;
+        v.A = reinterpret_cast<const float*>(io->a16);
+    }
+    if (!v.C) v.C = reinterpret_cast<float*>(io->c16);
+    return skg_gemm_b16_check(v, io->w16);
+}
+
+extern "C" int skg_gemm_b16_x(const skg_gemm_desc* dh, const skg_gemm_b16_io* io, void* stream) {
+    if (!dh) return SKG_E_ARG;
+    skg_gemm_desc d = *dh;
+    const int rc = skg_gemm_b16x_check(d, io);
+    if (rc) return rc;
+    if (d.M == 0) return 0;
+    const uint16_t* a16 = io->a16;
+    const uint16_t* w16 = io->w16;
+    uint16_t* c16 = io->c16;
+    const int64_t ldc16 = io->ldc16;
+    if (a16) d.A = reinterpret_cast<const float*>(a16);                 // (not read by MODE 7; as skg_gemm_b16_a16_f32 passes it)
+    const int T = skg_gemm_tile_scale(&d);
+    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
+    if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
+    dim3 grid((unsigned)nblk), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    skg_gemm_count(SKG_GEMM_PATH_BF16);
+    g_gemm_b16x[0].fetch_add(1, std::memory_order_relaxed);
+    if (a16) g_gemm_b16x[1].fetch_add(1, std::memory_order_relaxed);
+    if (c16) g_gemm_b16x[2].fetch_add(1, std::memory_order_relaxed);
+    // a split-K main kernel writes split_ws only, and a launch without c16 stores fp32 only: the kernels of
+    // skg_gemm_b16_f32 / skg_gemm_b16_a16_f32 serve both
+    const bool plain = !c16 || d.split_k > 1;
+#define SKG_LAUNCH(E)                                                                                                   \
+    if (plain && a16 && T == 1) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 1>), grid, block, 0, s, d, a16, w16);       \
+    else if (plain && a16) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 2>), grid, block, 0, s, d, a16, w16);            \
+    else if (plain && T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 1>), grid, block, 0, s, d, w16);                  \
+    else if (plain) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 2>), grid, block, 0, s, d, w16);                            \
+    else if (a16 && T == 1) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 7, 1>), grid, block, 0, s, d, a16, w16, c16, ldc16); \
+    else if (a16) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 7, 2>), grid, block, 0, s, d, a16, w16, c16, ldc16);         \
+    else if (T == 1) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 6, 1>), grid, block, 0, s, d, a16, w16, c16, ldc16);      \
+    else hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 6, 2>), grid, block, 0, s, d, a16, w16, c16, ldc16);
+    switch (d.epilogue) {
+        case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
+        case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;
+        case SKG_EPI_MUL_RELU:      SKG_LAUNCH(SKG_EPI_MUL_RELU) break;
+        case SKG_EPI_BIAS_RES_RELU: SKG_LAUNCH(SKG_EPI_BIAS_RES_RELU) break;
+        case SKG_EPI_RELU_DOT:                                          // (never with c16: checked above)
+            if (a16 && T == 1) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<SKG_EPI_RELU_DOT, 1>), grid, block, 0, s, d, a16, w16);
+            else if (a16) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<SKG_EPI_RELU_DOT, 2>), grid, block, 0, s, d, a16, w16);
+            else if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<SKG_EPI_RELU_DOT, 1>), grid, block, 0, s, d, w16);
+            else hipLaunchKernelGGL((skg_gemm_b16_kernel<SKG_EPI_RELU_DOT, 2>), grid, block, 0, s, d, w16);
+            break;
+    }
+#undef SKG_LAUNCH
+    if (d.split_k > 1) {
+        const int64_t total = (int64_t)d.M * d.N;
+        hipLaunchKernelGGL(skg_splitk_reduce_x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d, c16, ldc16);
+    }
+    return skg_launch_status();
+}
+
+extern "C" int skg_gemm_group_b16_x(const skg_gemm_desc* descs_host, const skg_gemm_b16_io* ios, int n, void* stream) {
+    if (!descs_host || !ios || n < 1 || n > SKG_GEMM_GROUP_MAX) return SKG_E_ARG;
+    skg_gemm_desc descs[SKG_GEMM_GROUP_MAX];
+    for (int i = 0; i < n; ++i) {
+        descs[i] = descs_host[i];
+        const int rc = skg_gemm_b16x_check(descs[i], &ios[i]);
+        if (rc) return rc;
+    }
+    const bool small = skg_gemm_group_small(descs, n);                 // (reads M, N, K, lda, ldw, a_rows: not A / C)
+    skg_gemm_group_b16x_args a;
+    skg_splitk_reduce_group_x_args r;
+    a.g.n = r.g.n = 0;
+    int64_t blocks = 0, rblocks = 0;
+    int n_a16 = 0, n_c16 = 0;
+    for (int i = 0; i < n; ++i) {
+        const skg_gemm_desc& d = descs[i];
+        if (d.split_k > 1 && !small) return SKG_E_ARG;                     // split-K only with the 64 x 64 tiles
+        if (d.M == 0) continue;
+        const int64_t nb = skg_gemm_blocks(d.M, d.N, d.K, small ? 1 : 2) * (d.split_k > 1 ? d.split_k : 1);
+        if (blocks + nb > 0x7fffffffLL) return SKG_E_LIMIT;
+        const int m = a.g.n;
+        a.g.d[m] = d;
+        a.w16[m] = ios[i].w16; a.a16[m] = ios[i].a16; a.c16[m] = ios[i].c16; a.ldc16[m] = ios[i].ldc16;
+        a.g.start[m] = (int)blocks;
+        blocks += nb;
+        ++a.g.n;
+        n_a16 += ios[i].a16 != nullptr; n_c16 += ios[i].c16 != nullptr;
+        if (d.split_k > 1) {
+            r.g.d[r.g.n] = d;
+            r.c16[r.g.n] = ios[i].c16; r.ldc16[r.g.n] = ios[i].ldc16;
+            r.g.start[r.g.n] = (int)rblocks;
+            rblocks += ((int64_t)d.M * d.N + 255) / 256;
+            ++r.g.n;
+        }
+    }
+    if (a.g.n == 0) return 0;
+    for (int i = a.g.n; i <= SKG_GEMM_GROUP_MAX; ++i) a.g.start[i] = (int)blocks;
+    for (int i = a.g.n; i < SKG_GEMM_GROUP_MAX; ++i) { a.w16[i] = nullptr; a.a16[i] = nullptr; a.c16[i] = nullptr; a.ldc16[i] = 0; }
+    skg_gemm_count(SKG_GEMM_PATH_BF16);
+    g_gemm_b16x[0].fetch_add(1, std::memory_order_relaxed);
+    g_gemm_b16x[1].fetch_add(n_a16, std::memory_order_relaxed);
+    g_gemm_b16x[2].fetch_add(n_c16, std::memory_order_relaxed);
+    if (small) hipLaunchKernelGGL(skg_gemm_group_b16x_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(skg_gemm_group_b16x_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (r.g.n) {
+        for (int i = r.g.n; i <= SKG_GEMM_GROUP_MAX; ++i) r.g.start[i] = (int)rblocks;
+        for (int i = r.g.n; i < SKG_GEMM_GROUP_MAX; ++i) { r.c16[i] = nullptr; r.ldc16[i] = 0; }
+        hipLaunchKernelGGL(skg_splitk_reduce_group_x_kernel, dim3((unsigned)rblocks), dim3(256), 0, (hipStream_t)stream, r);
     }
     return skg_launch_status();
 }

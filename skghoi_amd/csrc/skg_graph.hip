@@ -63,7 +63,8 @@ __global__ __launch_bounds__(256) void skg_graph_aggregate_kernel(
         for (int t = tid; t < cnt; t += 256) wout[row0 + t * rstep] = sw[t] * inv;
 
     const float* T = to_human ? T_os : T_so;
-    float* out = (to_human ? U : V) + (int64_t)dst * ldu;
+    float* out = to_human ? U : V;                            // (NULL: bf16 outputs only, skg_graph_aggregate_x)
+    if (out) out += (int64_t)dst * ldu;
     uint16_t* out16 = to_human ? U16 : V16;
     if (out16) out16 += (int64_t)dst * ldu;
     for (int c = tid * 4; c < cols; c += 1024) {
@@ -74,9 +75,33 @@ __global__ __launch_bounds__(256) void skg_graph_aggregate_kernel(
             const float4 v = *reinterpret_cast<const float4*>(p + (int64_t)t * rstep * ldt);
             acc.x += wt * v.x; acc.y += wt * v.y; acc.z += wt * v.z; acc.w += wt * v.w;
         }
-        *reinterpret_cast<float4*>(out + c) = acc;
+        if (out) *reinterpret_cast<float4*>(out + c) = acc;
         if (out16) skg_store_twin4(out16 + c, acc);
     }
+}
+
+// out_dtype: element type of U and V only (SKG_DTYPE_F32, or SKG_DTYPE_BF16: the fp32 sums rounded once, 8-byte aligned
+// outputs); the inputs and adj_out stay fp32.
+extern "C" int skg_graph_aggregate_x(const float* dot_partial, int n_partial, int64_t partial_ld, float adj_bias,
+                                     const skg_image_meta* meta, int n_active, const int32_t* hum_img,
+                                     const int32_t* node_img, int sum_h, int sum_n, const float* T_os, const float* T_so,
+                                     int64_t ldt, int cols, void* U, void* V, int64_t ldu, float* adj_out, int out_dtype,
+                                     void* stream) {
+    if (n_active < 0 || sum_h < 0 || sum_n < 0 || n_partial <= 0 || cols <= 0 || (cols & 3)) return SKG_E_ARG;
+    if (out_dtype != SKG_DTYPE_F32 && out_dtype != SKG_DTYPE_BF16) return SKG_E_ARG;
+    if (sum_h + sum_n == 0) return 0;
+    if (!dot_partial || !meta || !hum_img || !node_img || !T_os || !T_so || !U || !V) return SKG_E_ARG;
+    const bool half = out_dtype == SKG_DTYPE_BF16;
+    const uintptr_t amask = half ? 7u : 15u;
+    if ((ldt & 3) || (ldu & 3) || !skg_aligned16(T_os) || !skg_aligned16(T_so) || (((uintptr_t)U) & amask) ||
+        (((uintptr_t)V) & amask))
+        return SKG_E_ALIGN;
+    hipLaunchKernelGGL(skg_graph_aggregate_kernel, dim3(sum_h + sum_n), dim3(256), 0, (hipStream_t)stream, dot_partial,
+                       n_partial, partial_ld, adj_bias, meta, hum_img, node_img, sum_h, T_os, T_so, ldt, cols,
+                       half ? (float*)nullptr : (float*)U, half ? (float*)nullptr : (float*)V, ldu, adj_out,
+                       (float*)nullptr, (float*)nullptr, half ? (uint16_t*)U : (uint16_t*)nullptr,
+                       half ? (uint16_t*)V : (uint16_t*)nullptr);
+    return skg_launch_status();
 }
 
 extern "C" int skg_graph_aggregate_f32(const float* dot_partial, int n_partial, int64_t partial_ld, float adj_bias,
@@ -84,16 +109,8 @@ extern "C" int skg_graph_aggregate_f32(const float* dot_partial, int n_partial, 
                                        const int32_t* node_img, int sum_h, int sum_n, const float* T_os,
                                        const float* T_so, int64_t ldt, int cols, float* U, float* V, int64_t ldu,
                                        float* adj_out, void* stream) {
-    if (n_active < 0 || sum_h < 0 || sum_n < 0 || n_partial <= 0 || cols <= 0 || (cols & 3)) return SKG_E_ARG;
-    if (sum_h + sum_n == 0) return 0;
-    if (!dot_partial || !meta || !hum_img || !node_img || !T_os || !T_so || !U || !V) return SKG_E_ARG;
-    if ((ldt & 3) || (ldu & 3) || !skg_aligned16(T_os) || !skg_aligned16(T_so) || !skg_aligned16(U) ||
-        !skg_aligned16(V))
-        return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_graph_aggregate_kernel, dim3(sum_h + sum_n), dim3(256), 0, (hipStream_t)stream, dot_partial,
-                       n_partial, partial_ld, adj_bias, meta, hum_img, node_img, sum_h, T_os, T_so, ldt, cols, U, V,
-                       ldu, adj_out, (float*)nullptr, (float*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr);
-    return skg_launch_status();
+    return skg_graph_aggregate_x(dot_partial, n_partial, partial_ld, adj_bias, meta, n_active, hum_img, node_img, sum_h,
+                                 sum_n, T_os, T_so, ldt, cols, U, V, ldu, adj_out, SKG_DTYPE_F32, stream);
 }
 
 // The same aggregation for the training step: also returns the softmax weights alpha[sumG] (over the senders of every
@@ -145,7 +162,8 @@ __global__ __launch_bounds__(256) void skg_layernorm_kernel(const float* __restr
 
 // Two LayerNorms in one launch (norm_h on the human rows, norm_o on the node rows: HEAD:912-914, 923-925): workgroups
 // [0, rows0) take the first, the rest the second; per row the same arithmetic as skg_layernorm_kernel, bit for bit.
-struct skg_ln_seg { const float* x; int64_t ldx; const float* gamma; const float* beta; float* out; int64_t ldo; int rows; };
+// out16 (skg_layernorm2_x with a bf16 output): the row goes there, rounded once, instead of to out
+struct skg_ln_seg { const float* x; int64_t ldx; const float* gamma; const float* beta; float* out; int64_t ldo; int rows; uint16_t* out16; };
 
 __global__ __launch_bounds__(256) void skg_layernorm2_kernel(const skg_ln_seg a, const skg_ln_seg b, int cols, float eps) {
     __shared__ float sred[4];
@@ -164,25 +182,39 @@ __global__ __launch_bounds__(256) void skg_layernorm2_kernel(const skg_ln_seg a,
     if (in) {
         const float4 gm = *reinterpret_cast<const float4*>(g.gamma + c);
         const float4 bb = *reinterpret_cast<const float4*>(g.beta + c);
-        *reinterpret_cast<float4*>(g.out + (int64_t)r * g.ldo + c) =
-            make_float4(dlt.x * rstd * gm.x + bb.x, dlt.y * rstd * gm.y + bb.y, dlt.z * rstd * gm.z + bb.z,
-                        dlt.w * rstd * gm.w + bb.w);
+        const float4 y = make_float4(dlt.x * rstd * gm.x + bb.x, dlt.y * rstd * gm.y + bb.y, dlt.z * rstd * gm.z + bb.z,
+                                     dlt.w * rstd * gm.w + bb.w);
+        if (g.out16) skg_store_twin4(g.out16 + (int64_t)r * g.ldo + c, y);
+        else *reinterpret_cast<float4*>(g.out + (int64_t)r * g.ldo + c) = y;
     }
+}
+
+// out_dtype: element type of out0 and out1 (SKG_DTYPE_F32, or SKG_DTYPE_BF16: the fp32 row rounded once, 8-byte aligned)
+extern "C" int skg_layernorm2_x(const float* x0, int64_t ldx0, const float* gamma0, const float* beta0, int rows0,
+                                void* out0, int64_t ldo0, const float* x1, int64_t ldx1, const float* gamma1,
+                                const float* beta1, int rows1, void* out1, int64_t ldo1, int cols, float eps,
+                                int out_dtype, void* stream) {
+    if (rows0 < 0 || rows1 < 0 || cols <= 0 || cols > 1024 || (cols & 3)) return SKG_E_ARG;
+    if (out_dtype != SKG_DTYPE_F32 && out_dtype != SKG_DTYPE_BF16) return SKG_E_ARG;
+    if (rows0 + rows1 == 0) return 0;
+    if ((rows0 && (!x0 || !gamma0 || !beta0 || !out0)) || (rows1 && (!x1 || !gamma1 || !beta1 || !out1))) return SKG_E_ARG;
+    const bool half = out_dtype == SKG_DTYPE_BF16;
+    const uintptr_t amask = half ? 7u : 15u;
+    if ((ldx0 & 3) || (ldo0 & 3) || (ldx1 & 3) || (ldo1 & 3)) return SKG_E_ALIGN;
+    if (rows0 && (!skg_aligned16(x0) || (((uintptr_t)out0) & amask) || !skg_aligned16(gamma0) || !skg_aligned16(beta0))) return SKG_E_ALIGN;
+    if (rows1 && (!skg_aligned16(x1) || (((uintptr_t)out1) & amask) || !skg_aligned16(gamma1) || !skg_aligned16(beta1))) return SKG_E_ALIGN;
+    const skg_ln_seg a{x0, ldx0, gamma0, beta0, half ? nullptr : (float*)out0, ldo0, rows0, half ? (uint16_t*)out0 : nullptr},
+                     b{x1, ldx1, gamma1, beta1, half ? nullptr : (float*)out1, ldo1, rows1, half ? (uint16_t*)out1 : nullptr};
+    hipLaunchKernelGGL(skg_layernorm2_kernel, dim3(rows0 + rows1), dim3(256), 0, (hipStream_t)stream, a, b, cols, eps);
+    return skg_launch_status();
 }
 
 extern "C" int skg_layernorm2_f32(const float* x0, int64_t ldx0, const float* gamma0, const float* beta0, int rows0,
                                   float* out0, int64_t ldo0, const float* x1, int64_t ldx1, const float* gamma1,
                                   const float* beta1, int rows1, float* out1, int64_t ldo1, int cols, float eps,
                                   void* stream) {
-    if (rows0 < 0 || rows1 < 0 || cols <= 0 || cols > 1024 || (cols & 3)) return SKG_E_ARG;
-    if (rows0 + rows1 == 0) return 0;
-    if ((rows0 && (!x0 || !gamma0 || !beta0 || !out0)) || (rows1 && (!x1 || !gamma1 || !beta1 || !out1))) return SKG_E_ARG;
-    if ((ldx0 & 3) || (ldo0 & 3) || (ldx1 & 3) || (ldo1 & 3)) return SKG_E_ALIGN;
-    if (rows0 && (!skg_aligned16(x0) || !skg_aligned16(out0) || !skg_aligned16(gamma0) || !skg_aligned16(beta0))) return SKG_E_ALIGN;
-    if (rows1 && (!skg_aligned16(x1) || !skg_aligned16(out1) || !skg_aligned16(gamma1) || !skg_aligned16(beta1))) return SKG_E_ALIGN;
-    const skg_ln_seg a{x0, ldx0, gamma0, beta0, out0, ldo0, rows0}, b{x1, ldx1, gamma1, beta1, out1, ldo1, rows1};
-    hipLaunchKernelGGL(skg_layernorm2_kernel, dim3(rows0 + rows1), dim3(256), 0, (hipStream_t)stream, a, b, cols, eps);
-    return skg_launch_status();
+    return skg_layernorm2_x(x0, ldx0, gamma0, beta0, rows0, out0, ldo0, x1, ldx1, gamma1, beta1, rows1, out1, ldo1, cols,
+                            eps, SKG_DTYPE_F32, stream);
 }
 
 extern "C" int skg_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const float* beta, int rows,

@@ -181,26 +181,37 @@ __global__ __launch_bounds__(256) void skg_concat_entity_kernel(const float* __r
     float* dst = out + (int64_t)r * out_ld;
     const int t = threadIdx.x;
     const float4 v = reinterpret_cast<const float4*>(src)[t];
-    reinterpret_cast<float4*>(dst)[t] = v;                                                 // 256 x 4 = 1024 columns
+    if (out) reinterpret_cast<float4*>(dst)[t] = v;                                        // 256 x 4 = 1024 columns
     if (out16) skg_store_twin4(out16 + (int64_t)r * out_ld + 4 * t, v);
     if (t < 64) {
         const float* e = ent + ((int64_t)ent_img[r] * SKG_TRANSH_ENT + ent_row[r]) * SKG_TRANSH_DIM;
         const float x = (t < SKG_TRANSH_DIM) ? e[t] : 0.f;
-        dst[1024 + t] = x;                                                                 // 1024..1087
+        if (out) dst[1024 + t] = x;                                                        // 1024..1087
         if (out16) out16[(int64_t)r * out_ld + 1024 + t] = (uint16_t)skg_pack_bf16(x, 0.f);
     }
+}
+
+// out_dtype SKG_DTYPE_F32: out is float (plus its bf16 twin inside a training-plan call); SKG_DTYPE_BF16: out is bf16 only
+// (8-byte aligned), every element the fp32 result rounded once.
+extern "C" int skg_concat_entity_x(const float* enc, int64_t ld_enc, const int32_t* enc_row, const float* ent,
+                                   const int32_t* ent_img, const int32_t* ent_row, int rows, void* out, int64_t out_ld,
+                                   int out_dtype, void* stream) {
+    if (rows < 0 || (out_dtype != SKG_DTYPE_F32 && out_dtype != SKG_DTYPE_BF16)) return SKG_E_ARG;
+    if (rows == 0) return 0;
+    if (!enc || !enc_row || !ent || !ent_img || !ent_row || !out || out_ld < 1088) return SKG_E_ARG;
+    const bool half = out_dtype == SKG_DTYPE_BF16;
+    if (!skg_aligned16(enc) || (half ? (((uintptr_t)out) & 7u) != 0 : !skg_aligned16(out)) || (ld_enc & 3) || (out_ld & 3))
+        return SKG_E_ALIGN;
+    float* o32 = half ? nullptr : (float*)out;
+    hipLaunchKernelGGL(skg_concat_entity_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, enc, ld_enc, enc_row,
+                       ent, ent_img, ent_row, o32, out_ld, half ? (uint16_t*)out : skg_twin(o32));
+    return skg_launch_status();
 }
 
 extern "C" int skg_concat_entity_f32(const float* enc, int64_t ld_enc, const int32_t* enc_row, const float* ent,
                                      const int32_t* ent_img, const int32_t* ent_row, int rows, float* out,
                                      int64_t out_ld, void* stream) {
-    if (rows < 0) return SKG_E_ARG;
-    if (rows == 0) return 0;
-    if (!enc || !enc_row || !ent || !ent_img || !ent_row || !out || out_ld < 1088) return SKG_E_ARG;
-    if (!skg_aligned16(enc) || !skg_aligned16(out) || (ld_enc & 3) || (out_ld & 3)) return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_concat_entity_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, enc, ld_enc, enc_row,
-                       ent, ent_img, ent_row, out, out_ld, skg_twin(out));
-    return skg_launch_status();
+    return skg_concat_entity_x(enc, ld_enc, enc_row, ent, ent_img, ent_row, rows, out, out_ld, SKG_DTYPE_F32, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ read-out fc_1 * fc_2
@@ -217,7 +228,7 @@ __global__ __launch_bounds__(256) void skg_rows_mul_relu_kernel(const float* __r
     const float* p = P + (int64_t)(p_idx ? p_idx[r] : r) * ldp;
     const float* q = Q ? Q + (int64_t)(q_idx ? q_idx[r] : r) * ldq : nullptr;
     const float* f = F + (int64_t)(f_idx ? f_idx[r] : r) * ldf;
-    float* o = out + (int64_t)r * ldo;
+    float* o = out ? out + (int64_t)r * ldo : nullptr;
     uint16_t* o16 = out16 ? out16 + (int64_t)r * ldo : nullptr;
     for (int c = threadIdx.x * 4; c < cols; c += 1024) {
         float4 m = *reinterpret_cast<const float4*>(p + c);
@@ -231,7 +242,7 @@ __global__ __launch_bounds__(256) void skg_rows_mul_relu_kernel(const float* __r
         }
         const float4 v = *reinterpret_cast<const float4*>(f + c);
         const float4 res = make_float4(fmaxf(m.x * v.x, 0.f), fmaxf(m.y * v.y, 0.f), fmaxf(m.z * v.z, 0.f), fmaxf(m.w * v.w, 0.f));
-        *reinterpret_cast<float4*>(o + c) = res;
+        if (o) *reinterpret_cast<float4*>(o + c) = res;
         if (o16) skg_store_twin4(o16 + c, res);
     }
 }
@@ -284,20 +295,31 @@ int skg_rows_mul_relu_multi(const skg_rows_mul_args* calls, int n, void* stream)
     return skg_launch_status();
 }
 
+// out_dtype as in skg_concat_entity_x
+extern "C" int skg_rows_mul_relu_x(const float* P, const int32_t* p_idx, int64_t ldp, const float* Q,
+                                   const int32_t* q_idx, int64_t ldq, const float* mbias, const float* F,
+                                   const int32_t* f_idx, int64_t ldf, int rows, int cols, void* out, int64_t ldo,
+                                   int out_dtype, void* stream) {
+    if (rows < 0 || cols <= 0 || (cols & 3) || (out_dtype != SKG_DTYPE_F32 && out_dtype != SKG_DTYPE_BF16)) return SKG_E_ARG;
+    if (rows == 0) return 0;
+    if (!P || !F || !out) return SKG_E_ARG;
+    const bool half = out_dtype == SKG_DTYPE_BF16;
+    if ((ldp & 3) || (ldf & 3) || (ldo & 3) || (Q && (ldq & 3))) return SKG_E_ALIGN;
+    if (!skg_aligned16(P) || !skg_aligned16(F) || (half ? (((uintptr_t)out) & 7u) != 0 : !skg_aligned16(out)) ||
+        (Q && !skg_aligned16(Q)) || (mbias && !skg_aligned16(mbias)))
+        return SKG_E_ALIGN;
+    float* o32 = half ? nullptr : (float*)out;
+    hipLaunchKernelGGL(skg_rows_mul_relu_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, p_idx, ldp, Q,
+                       q_idx, ldq, mbias, F, f_idx, ldf, cols, o32, ldo, half ? (uint16_t*)out : skg_twin(o32));
+    return skg_launch_status();
+}
+
 extern "C" int skg_rows_mul_relu_f32(const float* P, const int32_t* p_idx, int64_t ldp, const float* Q,
                                      const int32_t* q_idx, int64_t ldq, const float* mbias, const float* F,
                                      const int32_t* f_idx, int64_t ldf, int rows, int cols, float* out, int64_t ldo,
                                      void* stream) {
-    if (rows < 0 || cols <= 0 || (cols & 3)) return SKG_E_ARG;
-    if (rows == 0) return 0;
-    if (!P || !F || !out) return SKG_E_ARG;
-    if ((ldp & 3) || (ldf & 3) || (ldo & 3) || (Q && (ldq & 3))) return SKG_E_ALIGN;
-    if (!skg_aligned16(P) || !skg_aligned16(F) || !skg_aligned16(out) || (Q && !skg_aligned16(Q)) ||
-        (mbias && !skg_aligned16(mbias)))
-        return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_rows_mul_relu_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, p_idx, ldp, Q,
-                       q_idx, ldq, mbias, F, f_idx, ldf, cols, out, ldo, skg_twin(out));
-    return skg_launch_status();
+    return skg_rows_mul_relu_x(P, p_idx, ldp, Q, q_idx, ldq, mbias, F, f_idx, ldf, rows, cols, out, ldo, SKG_DTYPE_F32,
+                               stream);
 }
 
 // ------------------------------------------------------------------------------------------------ transpose

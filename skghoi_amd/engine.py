@@ -351,13 +351,16 @@ class Bf16Weights:
 def gemm_desc(A, W, bias, C_out, M, N, K, epilogue, lda=None, ldw=None, ldc=None, a_rows=None, out_rows=None, P=None,
               p_idx=None, ldp=0, Q=None, q_idx=None, ldq=0, mbias=None, C_raw=None, ldc_raw=0, dot_w=None,
               dot_partial=None, res=None, ldres=0, A_off=0, W_off=0, C_off=0, d=None, split_k=0, split_ws=None,
-              w_split=None, w_scale=0.0):
-    """Fills a skg_gemm_desc.  *_off are element offsets into A / W / C (column sub-views)."""
+              w_split=None, w_scale=0.0, C16=None):
+    """Fills a skg_gemm_desc.  *_off are element offsets into A / W / C (column sub-views).  A bf16 A or C_out is not
+    part of the descriptor (d.A / d.C stay 0; strides are in elements either way): gemm_io() hands its address, and that of
+    a second, bf16 output C16, to skg_gemm_b16_x."""
     d = _capi.GemmDesc() if d is None else d
-    d.A = A.data_ptr() + 4 * A_off; d.lda = lda if lda is not None else A.stride(0)
+    d.A = (A.data_ptr() + 4 * A_off) if A.dtype != torch.bfloat16 else 0
+    d.lda = lda if lda is not None else A.stride(0)
     d.W = W.data_ptr() + 4 * W_off; d.ldw = ldw if ldw is not None else W.stride(0)
     d.bias = _ptr(bias)
-    d.C = (C_out.data_ptr() + 4 * C_off) if C_out is not None else 0
+    d.C = (C_out.data_ptr() + 4 * C_off) if (C_out is not None and C_out.dtype != torch.bfloat16) else 0
     d.ldc = ldc if ldc is not None else (C_out.stride(0) if C_out is not None else 0)
     d.M, d.N, d.K, d.epilogue = M, N, K, epilogue
     d.a_rows = _ptr(a_rows); d.out_rows = _ptr(out_rows)
@@ -379,6 +382,50 @@ def weight_twin(W, W_off=0, w_split=None):
     while a Bf16Weights context is active on this thread; 0 outside one or when the caller brings its own w_split."""
     bf = _active_bf16()
     return bf.get(W, W_off) if bf is not None and w_split is None else 0
+
+
+def uses_b16_io(A, C_out, kw):
+    """Whether a product goes through skg_gemm_b16_x / skg_gemm_group_b16_x: it has a bf16 output (C_out in bf16, or a second
+    output C16), or a bf16 A inside an activations16() block.  (A bf16 A alone -- bf16 box features on the default path --
+    keeps its skg_gemm_b16_a16_f32 launch.)"""
+    return (C_out is not None and C_out.dtype == torch.bfloat16) or kw.get("C16") is not None or \
+        (A.dtype == torch.bfloat16 and getattr(_TLS, "act16", False))
+
+
+def gemm_io(A, W, C_out, kw, io=None):
+    """Fills the skg_gemm_b16_io of a product described as for gemm_desc: the weight twin, the bf16 A and the bf16 output
+    (C_out itself, or the C16 keyword beside an fp32 C_out; same shape, so C_off and the leading dimension carry over)."""
+    io = _capi.GemmB16Io() if io is None else io
+    io.w16 = weight_twin(W, kw.get("W_off", 0), kw.get("w_split")) or None
+    if not io.w16:
+        raise _capi.SkgError("a bf16 operand needs the bf16 weight twins (inference_precision='bf16')")
+    io.a16 = (A.data_ptr() + 2 * kw.get("A_off", 0)) if A.dtype == torch.bfloat16 else None
+    c16 = C_out if (C_out is not None and C_out.dtype == torch.bfloat16) else kw.get("C16")
+    if c16 is not None:
+        if c16.dtype != torch.bfloat16:
+            raise _capi.SkgError("C16 must be a bf16 tensor")
+        io.c16 = c16.data_ptr() + 2 * kw.get("C_off", 0)
+        io.ldc16 = kw["ldc"] if (c16 is C_out and kw.get("ldc") is not None) else c16.stride(0)
+    else:
+        io.c16 = None; io.ldc16 = 0
+    return io
+
+
+class activations16:
+    """While active on this thread, products whose A is a bf16 panel are launched through skg_gemm_b16_x (the eval forward
+    under inference_activations='bf16').  Results do not depend on it: only which entry point, and so which counter."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self._prev = getattr(_TLS, "act16", False)
+        _TLS.act16 = self.on
+        return self
+
+    def __exit__(self, *a):
+        _TLS.act16 = self._prev
+        return False
 
 
 # ---- row exponents of the split-operand (fp16x2) GEMMs' A operands (power-of-two row scale, include/skghoi.h): one small
@@ -457,6 +504,8 @@ def bf16_rows(x, W):
 def gemm(A, W, bias, C_out, M, N, K, epilogue, **kw):
     """One skg_gemm_f32 launch (see gemm_desc for the keywords).  A bf16 A (bf16_rows) goes to skg_gemm_b16_a16_f32, which
     needs the bf16 weight twins (a Bf16Weights context)."""
+    if uses_b16_io(A, C_out, kw):
+        return _gemm_b16x(A, W, bias, C_out, M, N, K, epilogue, **kw)
     if A.dtype == torch.bfloat16:
         return _gemm_a16(A, W, bias, C_out, M, N, K, epilogue, **kw)
     d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
@@ -502,6 +551,21 @@ def _gemm_a16(A, W, bias, C_out, M, N, K, epilogue, **kw):
         GEMM_TIMER.append((e0, e1, M, N, K, epilogue))
 
 
+def _gemm_b16x(A, W, bias, C_out, M, N, K, epilogue, **kw):
+    """gemm() with a bf16 A and / or a bf16 output: one skg_gemm_b16_x launch (same launch shape as skg_gemm_b16_f32)."""
+    io = gemm_io(A, W, C_out, kw)
+    d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
+    timed = GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or epilogue in GEMM_TIMER_EPI)
+    if timed:
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _capi.check(_capi.lib().skg_gemm_b16_x(C.byref(d), C.byref(io), _stream()),
+                "skg_gemm_b16_x[%dx%dx%d epi %d]" % (M, N, K, epilogue))
+    if timed:
+        e1.record()
+        GEMM_TIMER.append((e0, e1, M, N, K, epilogue))
+
+
 def gemm_group(specs):
     """Independent small GEMMs in one launch: specs = [(args, kwargs), ...] as for gemm().
 
@@ -513,8 +577,12 @@ def gemm_group(specs):
     flops = 0.0
     keep_exp = []
     w16 = (C.c_void_p * n)()
+    b16x = any(uses_b16_io(a[0], a[3], kw) for a, kw in specs)      # any member with a bf16 panel: skg_gemm_group_b16_x
+    ios = (_capi.GemmB16Io * n)() if b16x else None
     for i, (a, kw) in enumerate(specs):
         gemm_desc(*a, d=arr[i], **kw)
+        if b16x:
+            gemm_io(a[0], a[1], a[3], kw, io=ios[i])
         w16[i] = weight_twin(a[1], kw.get("W_off", 0), kw.get("w_split")) or None
         if arr[i].w_split:
             keep_exp.append(enqueue_row_exponents(arr[i], a[0].device))
@@ -536,7 +604,9 @@ def gemm_group(specs):
     if timed:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-    if any(w16):
+    if b16x:
+        _capi.check(lib.skg_gemm_group_b16_x(arr, ios, n, _stream()), "skg_gemm_group_b16_x[%d]" % n)
+    elif any(w16):
         _capi.check(lib.skg_gemm_group_b16_f32(arr, w16, n, _stream()), "skg_gemm_group_b16_f32[%d]" % n)
     else:
         _capi.check(lib.skg_gemm_group_f32(arr, n, _stream()), "skg_gemm_group_f32[%d]" % n)
@@ -667,6 +737,7 @@ class HeadEngine:
                                     # launches are filled by the other's GEMMs (+2.6 % at 256 images, measured); 1: off
         self.precision = "fp32"     # "fp32": exact fp32 MFMA; "fp16x2" (opt-in): fp16 matrix pipe from 2-way operand splits
         self.inference_precision = None     # None, "fp32", "fp16x2", "bf16": see eval_precision()
+        self.inference_activations = None   # None / "fp32", "bf16": see act16()
         self._pw = None
         self._vt = None
         self._det_off_cache = {}
@@ -935,6 +1006,18 @@ class HeadEngine:
             return self.inference_precision
         return "fp16x2" if self.precision in ("fp16x2", "bf16") else "fp32"
 
+    def act16(self, training=False):
+        """Whether the target-less eval forward stores its GEMM-only panels in bf16 (inference_activations="bf16" on the
+        bf16 eval path; never in debug mode, whose kept intermediates are fp32)."""
+        return (not training and self.inference_activations == "bf16" and self.eval_precision() == "bf16"
+                and not self.debug)
+
+    @staticmethod
+    def _adt(a16, cols=8):
+        """Element type of a GEMM-only panel of `cols` columns: bf16 when the a16 rules hold for it (cols % 8 == 0; panels
+        come 16-byte aligned from the allocator), else fp32 for that panel only."""
+        return torch.bfloat16 if (a16 and cols % 8 == 0) else torch.float32
+
     def _split_ctx(self, pw):
         """Weight-twin context of the eval forward's GEMMs (fp16x2 planes, bf16 twins or none: the exact loop)."""
         p = self.eval_precision()
@@ -942,7 +1025,7 @@ class HeadEngine:
 
     def graph(self, feat3, image_shapes, pooled, pre, training=False, tables=None, want_scores=False):
         pw = self.weights(pre.device, wsum=getattr(pre, "wsum", None))
-        with self._split_ctx(pw):
+        with self._split_ctx(pw), activations16(self.act16(training)):
             return self._graph(feat3, image_shapes, pooled, pre, training, tables, want_scores, pw)
 
     def classify(self, pair_features, checked=False):
@@ -989,7 +1072,8 @@ class HeadEngine:
             xp[:, :x0.shape[1]] = x0
             x0 = xp
         NA = lay.sum_all
-        enc1 = torch.empty(max(NA, 1), 1024, **f32)
+        a16 = self.act16(training)      # GEMM-only panels in bf16 (which, and why results do not change)
+        enc1 = torch.empty(max(NA, 1), 1024, device=dev, dtype=self._adt(a16, 1024))
         enc = torch.empty(max(NA, 1), 1024, **f32)
         G1 = torch.empty(Bf, 1024, **f32)                       # attention_head_g fc_1(global) per image (HEAD:971)
         if NA:
@@ -1046,7 +1130,7 @@ class HeadEngine:
             def phase_a(ci):
                 a0, a1 = bounds[ci]
                 with on_stream(ci):
-                    ctxs[ci] = self._chunk_phase_a(layout.chunk(lay, a0, a1), pw, pre, G1, x_keep, y_keep, PF)
+                    ctxs[ci] = self._chunk_phase_a(layout.chunk(lay, a0, a1), pw, pre, G1, x_keep, y_keep, PF, a16=a16)
 
             for ci in range(min(lookahead, len(bounds))):
                 phase_a(ci)
@@ -1081,10 +1165,10 @@ class HeadEngine:
                 out[k] = torch.cat(v)
         return out
 
-    def _chunk_phase_a(self, ch, pw, pre, G1, x_keep, y_keep, PF, ibuf=None, offs=None, meta=None, caps=None):
+    def _chunk_phase_a(self, ch, pw, pre, G1, x_keep, y_keep, PF, ibuf=None, offs=None, meta=None, caps=None, a16=False):
         """Pairs, spatial encoding, spatial head and the global read-out branch of one chunk: everything that does not
         depend on the TransH tables.  ibuf / offs / meta: index arrays already on the device (captured-graph path:
-        they are part of the launch plan, `meta` is its per-call record array)."""
+        they are part of the launch plan, `meta` is its per-call record array).  a16: GEMM-only panels in bf16 (act16())."""
         lib = _capi.lib()
         dev = pre.device
         st = _stream()
@@ -1116,13 +1200,15 @@ class HeadEngine:
                                                      pair_h.data_ptr(), pair_o.data_ptr(), sp48.data_ptr(), 1, gcap, pcap,
                                                      st), "skg_pairs_spatial_padded_f32")
         # ---- spatial_head (HEAD:662-669, 888)
-        s1 = torch.empty(Mg, 128, **f32); s2 = torch.empty(Mg, 256, **f32); S = torch.empty(Mg, 1024, **f32)
+        s1 = torch.empty(Mg, 128, device=dev, dtype=self._adt(a16, 128))
+        s2 = torch.empty(Mg, 256, device=dev, dtype=self._adt(a16, 256))
+        S = torch.empty(Mg, 1024, device=dev, dtype=self._adt(a16, 1024))
         gemm(sp48, pw.sp0_w, pw.sp0_b, s1, Mg, 128, _capi.SPATIAL_LD, _capi.EPI_BIAS_RELU)
         gemm(s1, pw.sp2_w, pw.sp2_b, s2, Mg, 256, 128, _capi.EPI_BIAS_RELU)
         gemm(s2, pw.sp4_w, pw.sp4_b, S, Mg, 1024, 256, _capi.EPI_BIAS_RELU)
         del s1, s2
         cx = dict(ch=ch, isl=isl, meta=meta, grid_h=grid_h, grid_o=grid_o, grid_img=grid_img, grid_pair=grid_pair,
-                  pair_grid=pair_grid, pair_h=pair_h, pair_o=pair_o, sp48=sp48, S=S, ibuf=ibuf)
+                  pair_grid=pair_grid, pair_h=pair_h, pair_o=pair_o, sp48=sp48, S=S, ibuf=ibuf, a16=a16)
         if G1 is not None:
             self._chunk_phase_a2(cx, pw, pre, G1, PF)
         return cx
@@ -1132,7 +1218,7 @@ class HeadEngine:
         (HEAD:971-972).  (Split off phase A so that a captured plan can run it beside the message-passing chain.)"""
         ch = cx["ch"]
         Mg, Mp = ch.sum_g, ch.sum_p
-        Tg = torch.empty(max(Mp, 1), 1024, device=pre.device, dtype=torch.float32)
+        Tg = torch.empty(max(Mp, 1), 1024, device=pre.device, dtype=self._adt(cx.get("a16", False), 1024))
         if Mp:
             gemm(cx["S"], pw.att_g["w2"], pw.att_g["b2"], Tg, Mg, 1024, 1024, _capi.EPI_MUL_RELU, P=G1,
                  p_idx=cx["grid_img"], ldp=1024, out_rows=cx["grid_pair"])
@@ -1156,27 +1242,42 @@ class HeadEngine:
         Mh, Mn, Mg, Mp = ch.sum_h, ch.sum_n, ch.sum_g, ch.sum_p
         ent, rel, nrm = tabs
         ent_d = ent.to(dev, non_blocking=True)
+        a16 = cx.get("a16", False)
+        adt = self._adt(a16, 1024)                             # the GEMM-only panels of this phase are 1024 / 1088 wide
+        odt = _capi.DTYPE_BF16 if adt == torch.bfloat16 else _capi.DTYPE_F32
+        a16 = adt == torch.bfloat16
         F2 = torch.empty(Mg, 1024, **f32)
         if gh.num_iter > 0:
             # ---- fc_head / fc_tail on unique rows (HEAD:884-885)
-            X = torch.empty(Mh + Mn, 1088, **f32)
+            X = torch.empty(Mh + Mn, 1088, device=dev, dtype=adt)
             rows, eimg, erow = isl("enc_row_hn"), isl("img_hn"), isl("ent_row_hn")
-            _capi.check(lib.skg_concat_entity_f32(enc.data_ptr(), 1024, rows.data_ptr(), ent_d.data_ptr(),
-                                                  eimg.data_ptr(), erow.data_ptr(), Mh + Mn, X.data_ptr(), 1088, st),
-                        "skg_concat_entity_f32")
+            if a16:
+                _capi.check(lib.skg_concat_entity_x(enc.data_ptr(), 1024, rows.data_ptr(), ent_d.data_ptr(),
+                                                    eimg.data_ptr(), erow.data_ptr(), Mh + Mn, X.data_ptr(), 1088, odt, st),
+                            "skg_concat_entity_x")
+            else:
+                _capi.check(lib.skg_concat_entity_f32(enc.data_ptr(), 1024, rows.data_ptr(), ent_d.data_ptr(),
+                                                      eimg.data_ptr(), erow.data_ptr(), Mh + Mn, X.data_ptr(), 1088, st),
+                            "skg_concat_entity_f32")
             GH = torch.empty(Mh, 1024, **f32); GO = torch.empty(Mn, 1024, **f32)
-            gemm_group([((X, pw.fh_w, pw.fh_b, GH, Mh, 1024, 1088, _capi.EPI_BIAS_RELU), {}),
-                        ((X, pw.ft_w, pw.ft_b, GO, Mn, 1024, 1088, _capi.EPI_BIAS_RELU), dict(A_off=Mh * 1088))])
+            # GH / GO: fp32 as the residual of the message fc_3; a second, bf16 copy is the A operand of the four fc_1 products
+            GHa = torch.empty(Mh, 1024, device=dev, dtype=adt) if a16 else GH
+            GOa = torch.empty(Mn, 1024, device=dev, dtype=adt) if a16 else GO
+            gemm_group([((X, pw.fh_w, pw.fh_b, GH, Mh, 1024, 1088, _capi.EPI_BIAS_RELU), dict(C16=GHa) if a16 else {}),
+                        ((X, pw.ft_w, pw.ft_b, GO, Mn, 1024, 1088, _capi.EPI_BIAS_RELU),
+                         dict(A_off=Mh * 1088, C16=GOa) if a16 else dict(A_off=Mh * 1088))])
             # ---- attention_head fc_1, separable over [human | object] halves (HEAD:894-896)
             A1h = torch.empty(Mh, 1024, **f32); A1o = torch.empty(Mn, 1024, **f32)
             # message fc_1 on node rows (HEAD:514, 524)
             C1o = torch.empty(Mn, 1024, **f32); C1h = torch.empty(Mh, 1024, **f32)
-            gemm_group([((GH, pw.att["w1"], None, A1h, Mh, 1024, 1024, _capi.EPI_BIAS), dict(ldw=2048)),
-                        ((GO, pw.att["w1"], None, A1o, Mn, 1024, 1024, _capi.EPI_BIAS), dict(ldw=2048, W_off=1024)),
-                        ((GO, pw.os["w1"], pw.os["b1"], C1o, Mn, 1024, 1024, _capi.EPI_BIAS), {}),
-                        ((GH, pw.so["w1"], pw.so["b1"], C1h, Mh, 1024, 1024, _capi.EPI_BIAS), {})])
+            gemm_group([((GHa, pw.att["w1"], None, A1h, Mh, 1024, 1024, _capi.EPI_BIAS), dict(ldw=2048)),
+                        ((GOa, pw.att["w1"], None, A1o, Mn, 1024, 1024, _capi.EPI_BIAS), dict(ldw=2048, W_off=1024)),
+                        ((GOa, pw.os["w1"], pw.os["b1"], C1o, Mn, 1024, 1024, _capi.EPI_BIAS), {}),
+                        ((GHa, pw.so["w1"], pw.so["b1"], C1h, Mh, 1024, 1024, _capi.EPI_BIAS), {})])
+            del GHa, GOa
             # ---- fc_2 GEMMs over the grid rows with the fc_1*fc_2 -> ReLU product fused
-            T = torch.empty(Mg, 1024, **f32); Tos = torch.empty(Mg, 1024, **f32); Tso = torch.empty(Mg, 1024, **f32)
+            T = torch.empty(Mg, 1024, device=dev, dtype=adt)
+            Tos = torch.empty(Mg, 1024, **f32); Tso = torch.empty(Mg, 1024, **f32)
             fc2 = [((S, pw.att["w2"], pw.att["b2"], T, Mg, 1024, 1024, _capi.EPI_MUL_RELU),
                     dict(P=A1h, p_idx=grid_h, ldp=1024, Q=A1o, q_idx=grid_o, ldq=1024, mbias=pw.att["b1"], C_raw=F2,
                          ldc_raw=1024)),
@@ -1197,24 +1298,38 @@ class HeadEngine:
             gemm(T, pw.att["w3"], pw.att["b3"], None, Mg, 1024, 1024, _capi.EPI_RELU_DOT, dot_w=pw.adj_w,
                  dot_partial=part)
             # ---- softmax-weighted aggregation before fc_3 (HEAD:907-922)
-            U = torch.empty(Mh, 1024, **f32); V = torch.empty(Mn, 1024, **f32); adj = torch.empty(Mg, **f32)
-            _capi.check(lib.skg_graph_aggregate_f32(part.data_ptr(), n_part, Mg, pw.adj_b, meta.data_ptr(), A,
-                                                    isl("hum_img").data_ptr(), isl("node_img").data_ptr(), Mh, Mn,
-                                                    Tos.data_ptr(), Tso.data_ptr(), 1024, 1024, U.data_ptr(),
-                                                    V.data_ptr(), 1024, adj.data_ptr(), st),
-                        "skg_graph_aggregate_f32")
+            U = torch.empty(Mh, 1024, device=dev, dtype=adt); V = torch.empty(Mn, 1024, device=dev, dtype=adt)
+            adj = torch.empty(Mg, **f32)
+            if a16:
+                _capi.check(lib.skg_graph_aggregate_x(part.data_ptr(), n_part, Mg, pw.adj_b, meta.data_ptr(), A,
+                                                      isl("hum_img").data_ptr(), isl("node_img").data_ptr(), Mh, Mn,
+                                                      Tos.data_ptr(), Tso.data_ptr(), 1024, 1024, U.data_ptr(),
+                                                      V.data_ptr(), 1024, adj.data_ptr(), odt, st),
+                            "skg_graph_aggregate_x")
+            else:
+                _capi.check(lib.skg_graph_aggregate_f32(part.data_ptr(), n_part, Mg, pw.adj_b, meta.data_ptr(), A,
+                                                        isl("hum_img").data_ptr(), isl("node_img").data_ptr(), Mh, Mn,
+                                                        Tos.data_ptr(), Tso.data_ptr(), 1024, 1024, U.data_ptr(),
+                                                        V.data_ptr(), 1024, adj.data_ptr(), st),
+                            "skg_graph_aggregate_f32")
             del T, Tos, Tso
             Hp = torch.empty(Mh, 1024, **f32); Op = torch.empty(Mn, 1024, **f32)
             gemm_group([((U, pw.os["w3"], pw.os["b3"], Hp, Mh, 1024, 1024, _capi.EPI_BIAS_RES_RELU),
                          dict(res=GH, ldres=1024)),
                         ((V, pw.so["w3"], pw.so["b3"], Op, Mn, 1024, 1024, _capi.EPI_BIAS_RES_RELU),
                          dict(res=GO, ldres=1024))])
-            h_node = torch.empty(Mh, 1024, **f32); node = torch.empty(Mn, 1024, **f32)
+            h_node = torch.empty(Mh, 1024, device=dev, dtype=adt); node = torch.empty(Mn, 1024, device=dev, dtype=adt)
             # norm_h and norm_o (HEAD:912-914, 923-925) as one launch
-            _capi.check(lib.skg_layernorm2_f32(Hp.data_ptr(), 1024, pw.nh_g.data_ptr(), pw.nh_b.data_ptr(), Mh,
-                                               h_node.data_ptr(), 1024, Op.data_ptr(), 1024, pw.no_g.data_ptr(),
-                                               pw.no_b.data_ptr(), Mn, node.data_ptr(), 1024, 1024, EPS_LN, st),
-                        "skg_layernorm2_f32")
+            if a16:
+                _capi.check(lib.skg_layernorm2_x(Hp.data_ptr(), 1024, pw.nh_g.data_ptr(), pw.nh_b.data_ptr(), Mh,
+                                                 h_node.data_ptr(), 1024, Op.data_ptr(), 1024, pw.no_g.data_ptr(),
+                                                 pw.no_b.data_ptr(), Mn, node.data_ptr(), 1024, 1024, EPS_LN, odt, st),
+                            "skg_layernorm2_x")
+            else:
+                _capi.check(lib.skg_layernorm2_f32(Hp.data_ptr(), 1024, pw.nh_g.data_ptr(), pw.nh_b.data_ptr(), Mh,
+                                                   h_node.data_ptr(), 1024, Op.data_ptr(), 1024, pw.no_g.data_ptr(),
+                                                   pw.no_b.data_ptr(), Mn, node.data_ptr(), 1024, 1024, EPS_LN, st),
+                            "skg_layernorm2_f32")
         else:
             # num_iter == 0: the raw box_head encodings reach the read-out (HEAD:843-845)
             if need_S is not None:
@@ -1231,10 +1346,16 @@ class HeadEngine:
             if need_Tg is not None:
                 need_Tg()
             Tp = cx["Tg"]                                        # the global branch has consumed this buffer
-            _capi.check(lib.skg_rows_mul_relu_f32(B1h.data_ptr(), pair_h.data_ptr(), 1024, B1o.data_ptr(),
-                                                  pair_o.data_ptr(), 1024, pw.att["b1"].data_ptr(), F2.data_ptr(),
-                                                  pair_grid.data_ptr(), 1024, Mp, 1024, Tp.data_ptr(), 1024, st),
-                        "skg_rows_mul_relu_f32")
+            if Tp.dtype == torch.bfloat16:
+                _capi.check(lib.skg_rows_mul_relu_x(B1h.data_ptr(), pair_h.data_ptr(), 1024, B1o.data_ptr(),
+                                                    pair_o.data_ptr(), 1024, pw.att["b1"].data_ptr(), F2.data_ptr(),
+                                                    pair_grid.data_ptr(), 1024, Mp, 1024, Tp.data_ptr(), 1024,
+                                                    _capi.DTYPE_BF16, st), "skg_rows_mul_relu_x")
+            else:
+                _capi.check(lib.skg_rows_mul_relu_f32(B1h.data_ptr(), pair_h.data_ptr(), 1024, B1o.data_ptr(),
+                                                      pair_o.data_ptr(), 1024, pw.att["b1"].data_ptr(), F2.data_ptr(),
+                                                      pair_grid.data_ptr(), 1024, Mp, 1024, Tp.data_ptr(), 1024, st),
+                            "skg_rows_mul_relu_f32")
             gemm(Tp, pw.att["w3"], pw.att["b3"], PF, Mp, 1024, 1024, _capi.EPI_BIAS_RELU, ldc=2048,
                  C_off=ch.P0 * 2048)
         if sc is not None:

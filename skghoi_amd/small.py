@@ -44,8 +44,8 @@ import numpy as np
 import torch
 
 from . import _capi, layout, transh
-from .engine import Preprocessed, bf16_rows, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_group, pick_split_k, \
-    _stream, weight_twin
+from .engine import Preprocessed, activations16, bf16_rows, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_group, \
+    gemm_io, pick_split_k, _stream, weight_twin
 
 META_WORDS = layout.META_DTYPE.itemsize // 4
 
@@ -226,13 +226,15 @@ class SmallBatchRunner:
         p.labels = torch.zeros(max(NA, 1), dtype=torch.int64, device=dev)[:NA]
         p.sel_off = eng._det_offsets(pre.sizes, dev)
         p.gfeat = torch.zeros(feat3.shape[0], feat3.shape[1], **f32)
-        p.enc1 = torch.zeros(max(NA, 1), 1024, **f32)
+        p.a16 = eng.act16()                  # (part of the plan key) GEMM-only panels in bf16: this persistent one too
+        p.enc1 = torch.zeros(max(NA, 1), 1024, device=dev, dtype=eng._adt(p.a16, 1024))
         kp = pw.bh1_w.shape[1]
         p.x0_pad = torch.zeros(NA, kp, **f32) if pooled[0].numel() != kp else None
         p.sk = pick_split_k(NA, 1024, kp)
         p.ws = torch.empty(p.sk, NA, 1024, **f32) if p.sk > 1 else None
         p.bh1_desc = None                                # filled on first use (needs the weight-twin context)
         p.bh1_w16 = 0
+        p.bh1_io = None                                  # skg_gemm_b16_io of that launch under bf16 activations
         p.pre = Preprocessed()
         p.pre.device = dev; p.pre.B = pre.B
         p.pre.boxes, p.pre.scores, p.pre.labels = p.boxes, p.scores, p.labels
@@ -270,7 +272,7 @@ class SmallBatchRunner:
         side = self.side
         if not eng.small_two_branches:
             side = main                        # one chain: the captured graph needs no stream of its own beside the caller's
-        with eng._split_ctx(pw):
+        with eng._split_ctx(pw), activations16(p.a16):
             enc = torch.empty(max(NA, 1), 1024, **f32)
             Bf, Cf = p.gfeat.shape
             G1 = torch.empty(Bf, 1024, **f32)
@@ -292,7 +294,7 @@ class SmallBatchRunner:
                     side.wait_event(fork)
                     gemm_group([g1])
                     cx = eng._chunk_phase_a(p.ch, pw, p.pre, None, x_keep, y_keep, PF, ibuf=p.ibuf, offs=p.offs,
-                                            meta=p.meta_dev, caps=p.caps)
+                                            meta=p.meta_dev, caps=p.caps, a16=p.a16)
                     s_ready = torch.cuda.Event(); s_ready.record(side)
                     eng._chunk_phase_a2(cx, pw, p.pre, G1, PF)
                     g_done = torch.cuda.Event(); g_done.record(side)
@@ -302,7 +304,7 @@ class SmallBatchRunner:
                 with torch.cuda.stream(side):
                     side.wait_event(fork)
                     cx = eng._chunk_phase_a(p.ch, pw, p.pre, None, x_keep, y_keep, PF, ibuf=p.ibuf, offs=p.offs,
-                                            meta=p.meta_dev, caps=p.caps)
+                                            meta=p.meta_dev, caps=p.caps, a16=p.a16)
                     s_ready = torch.cuda.Event(); s_ready.record(side)
                 # box_head layer 2 and attention_head_g's fc_1 on the global features: independent, one launch
                 gemm_group([bh3, g1])
@@ -463,7 +465,7 @@ class SmallBatchRunner:
                           capacity(n1, min(max(eng.max_human + eng.max_object, n1), _capi.TRANSH_ENT)))
         shape_key = ("bucket",) + bucket if bucket else (tuple(pre.n_h.tolist()), tuple(pre.n.tolist()))
         key = shape_key + (tuple(feat3.shape[:2]), eng.precision, eng.eval_precision(), eng.gh.num_iter, eng.faithful_skip_offset,
-                           eng.plan_epoch, dev.index)
+                           eng.plan_epoch, dev.index, eng.act16())
         p = self.plans.get(key)
         if p is None and not bucket and eng.small_capture_after > 1:
             # exact-shape plans (batches of 2..8 images, single images without buckets): a capture costs 10-20 ms -- an eager
@@ -547,11 +549,16 @@ class SmallBatchRunner:
                 p.bh1_desc = gemm_desc(x0, pw.bh1_w, pw.bh1_b, p.enc1, lay.sum_all, 1024, x0.shape[1],
                                        _capi.EPI_BIAS_RELU, split_k=p.sk, split_ws=p.ws)
                 p.bh1_w16 = weight_twin(pw.bh1_w)    # bf16 eval path: the twin beside the descriptor (else 0)
+                if p.enc1.dtype == torch.bfloat16:   # bf16 activations: the output goes through skg_gemm_b16_x's c16
+                    p.bh1_io = gemm_io(x0, pw.bh1_w, p.enc1, {})
         p.bh1_desc.A = x0.data_ptr()               # the fields that change from call to call: the caller's tensor and (bucket
         p.bh1_desc.M = n_act                       # plans) its row count
         if p.bh1_desc.w_split:
             p.bh1_exp = enqueue_row_exponents(p.bh1_desc, x0.device)
-        if p.bh1_w16 and x16 is not None:
+        if p.bh1_io is not None:
+            p.bh1_io.a16 = x16.data_ptr() if x16 is not None else None
+            _capi.check(lib.skg_gemm_b16_x(C.byref(p.bh1_desc), C.byref(p.bh1_io), _stream()), "skg_gemm_b16_x[box_head 1]")
+        elif p.bh1_w16 and x16 is not None:
             _capi.check(lib.skg_gemm_b16_a16_f32(C.byref(p.bh1_desc), x16.data_ptr(), p.bh1_w16, _stream()),
                         "skg_gemm_b16_a16_f32[box_head 1]")
         elif p.bh1_w16:

@@ -157,6 +157,25 @@ int skg_roi_align_x(const void* const* feats_host, int map_dtype, const int32_t*
                     const float* scales_host, int n_levels, int C, int k_min, int k_max, float canonical_scale,
                     int canonical_level, const float* boxes, const int32_t* box_image, int n_rois, int pooled,
                     int sampling, void* out, int out_dtype, void* stream);
+/* The same two on CHANNELS-LAST maps (what a backbone run with memory_format = channels_last hands over), read and
+ * written in place: feats_host[l] / dfeats_host[l] point at [B, H_l, W_l, C] memory (map_dtype elements forward, ZEROED
+ * fp32 gradient maps backward); out / dout keep the [n_rois, C, pooled, pooled] layout.  All nine map x output dtype pairs.
+ * The arithmetic per output element is that of skg_roi_align_x (only the tap addresses differ), so the forward equals
+ * skg_roi_align_x on the same values laid out [B, C, H_l, W_l] bit for bit; the backward uses the same float atomics
+ * (order not fixed).  Limits: C % 8 == 0 and pooled <= 8 (else SKG_E_ARG); every level base, boxes and out / dout 16-byte
+ * aligned (else SKG_E_ALIGN); n_rois * ceil(C / 64) <= 2^31 - 1 (else SKG_E_LIMIT).                                   */
+int skg_roi_align_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host, const int32_t* W_host,
+                         const float* scales_host, int n_levels, int C, int k_min, int k_max, float canonical_scale,
+                         int canonical_level, const float* boxes, const int32_t* box_image, int n_rois, int pooled,
+                         int sampling, void* out, int out_dtype, void* stream);
+int skg_roi_align_bwd_nhwc_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                               const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                               float canonical_scale, int canonical_level, const float* boxes,
+                               const int32_t* box_image, int n_rois, int pooled, int sampling, const float* dout,
+                               void* stream);
+/* Statistics: RoIAlign launches since the last reset -- out4 = forward [B,C,H,W], forward channels-last, backward
+ * [B,C,H,W], backward channels-last (skg_roi_align_f32 counts as skg_roi_align_x); reset != 0 zeroes them after the read. */
+void skg_roi_align_layout_counts(int64_t out4[4], int reset);
 
 /* AdaptiveAvgPool2d(1) of features['3'] (HEAD:811): in [B, C, HW] -> out [B, C]. */
 int skg_global_avgpool_f32(const float* in, int B, int C, int HW, float* out, void* stream);

@@ -8,6 +8,17 @@
 //   averages sampling_ratio^2 bilinear samples; samples outside [-1, size] contribute 0.
 // One thread per output element with the bin column fastest: neighbouring lanes read neighbouring feature pixels;
 // the 16 taps of a bin hit L2.  HBM-bound on the [rois, C, 7, 7] write.
+//
+// Channels-last maps ([B, H_l, W_l, C] memory, what a channels_last backbone hands over) are read in place by the *_nhwc
+// kernels further down: a workgroup owns one RoI x a slab of SKG_ROI_NHWC_SLAB (64) channels, a lane owns 16 bytes of
+// consecutive channels (8 half / 4 fp32) of one bin, so every tap of a (bin, sample) is one contiguous row segment; the
+// [slab][pooled^2] fp32 result tile is transposed through LDS and leaves as 16-byte stores (the backward stages d out the
+// same way and issues its float atomics on consecutive addresses).  The arithmetic per output element is that of the NCHW
+// kernels, operation for operation: only the tap addresses differ.
+// Limits of the *_nhwc entries: C % 8 == 0 and pooled <= SKG_ROI_NHWC_MAX_POOLED (8: the 64 x (pooled^2 | 1) fp32 tile is
+// static LDS, 16.25 KiB) else SKG_E_ARG; every level base, boxes, out / dout 16-byte aligned else SKG_E_ALIGN;
+// n_rois * ceil(C / 64) workgroups <= 2^31 - 1 else SKG_E_LIMIT.
+#include <atomic>
 #include "skg_common.h"
 
 struct skg_roi_levels {
@@ -146,6 +157,187 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_kernel(const skg_roi_le
     }
 }
 
+// ------------------------------------------------------------------------------------------------ channels-last maps
+#define SKG_ROI_NHWC_SLAB 64
+#define SKG_ROI_NHWC_MAX_POOLED 8
+#define SKG_ROI_NHWC_TILE (SKG_ROI_NHWC_SLAB * (SKG_ROI_NHWC_MAX_POOLED * SKG_ROI_NHWC_MAX_POOLED + 1))
+
+// Level and bin grid of one RoI: the expressions of skg_roi_align_kernel, once per thread instead of once per element.
+struct skg_roi_geom {
+    int l, H, W, gh, gw;
+    float x1, y1, bw, bh, cnt;
+};
+__device__ __forceinline__ skg_roi_geom skg_roi_box_geom(const skg_roi_levels& L, const float4 b, int pooled, int sampling) {
+    skg_roi_geom g;
+    const float s = sqrtf((b.z - b.x) * (b.w - b.y));
+    float lv = floorf((float)L.canonical_level + log2f(s / L.canonical_scale) + 1e-6f);
+    lv = fminf(fmaxf(lv, (float)L.k_min), (float)L.k_max);
+    g.l = (int)lv - L.k_min;
+    g.H = L.H[g.l]; g.W = L.W[g.l];
+    const float sc = L.scale[g.l];
+    const float x1 = b.x * sc, y1 = b.y * sc, x2 = b.z * sc, y2 = b.w * sc;
+    const float rw = fmaxf(x2 - x1, 1.f), rh = fmaxf(y2 - y1, 1.f);
+    g.x1 = x1; g.y1 = y1;
+    g.bw = rw / (float)pooled; g.bh = rh / (float)pooled;
+    g.gh = sampling > 0 ? sampling : (int)ceilf(rh / pooled);
+    g.gw = sampling > 0 ? sampling : (int)ceilf(rw / pooled);
+    g.cnt = fmaxf((float)(g.gh * g.gw), 1.f);
+    return g;
+}
+
+// The four taps of one sample and their weights (skg_bilinear's clamps); false: the sample lies outside and adds 0.
+struct skg_roi_taps {
+    int y_low, y_high, x_low, x_high;
+    float w1, w2, w3, w4;
+};
+__device__ __forceinline__ bool skg_roi_sample(int H, int W, float y, float x, skg_roi_taps& t) {
+    if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return false;
+    if (y <= 0.f) y = 0.f;
+    if (x <= 0.f) x = 0.f;
+    int y_low = (int)y, x_low = (int)x, y_high, x_high;
+    if (y_low >= H - 1) { y_high = y_low = H - 1; y = (float)y_low; } else y_high = y_low + 1;
+    if (x_low >= W - 1) { x_high = x_low = W - 1; x = (float)x_low; } else x_high = x_low + 1;
+    const float ly = y - y_low, lx = x - x_low, hy = 1.f - ly, hx = 1.f - lx;
+    t.y_low = y_low; t.y_high = y_high; t.x_low = x_low; t.x_high = x_high;
+    t.w1 = hy * hx; t.w2 = hy * lx; t.w3 = ly * hx; t.w4 = ly * lx;
+    return true;
+}
+
+// 16 bytes of consecutive elements of dtype DT
+template <int DT> union skg_roi_vec {
+    uint4 q;
+    typename skg_roi_elem<DT>::T e[16 / sizeof(typename skg_roi_elem<DT>::T)];
+};
+
+// grid = n_rois * n_slabs workgroups of 256: thread -> (bin group, 16-byte channel vector of the slab).
+template <int MDT, int ODT>
+__global__ __launch_bounds__(256) void skg_roi_align_nhwc_kernel(const skg_roi_levels L, const float* __restrict__ boxes,
+                                                                 const int32_t* __restrict__ box_image, int n_slabs,
+                                                                 int pooled, int sampling,
+                                                                 typename skg_roi_elem<ODT>::T* __restrict__ out) {
+    typedef skg_roi_elem<MDT> EM;
+    typedef skg_roi_elem<ODT> EO;
+    typedef typename EM::T TM;
+    typedef typename EO::T TO;
+    constexpr int VM = 16 / (int)sizeof(TM);                   // channels per lane
+    constexpr int NV = SKG_ROI_NHWC_SLAB / VM;                 // lanes per bin
+    constexpr int NG = 256 / NV;                               // bins in flight per workgroup
+    constexpr int VO = 16 / (int)sizeof(TO);
+    __shared__ float tile[SKG_ROI_NHWC_TILE];                  // [channel of the slab][pp | 1]
+    const int n = (int)(blockIdx.x / (unsigned)n_slabs);
+    const int c0 = (int)(blockIdx.x % (unsigned)n_slabs) * SKG_ROI_NHWC_SLAB;
+    const int cs = min(SKG_ROI_NHWC_SLAB, L.C - c0);           // channels of this slab (a multiple of 8)
+    const int pp = pooled * pooled, S = pp | 1;
+    const skg_roi_geom g = skg_roi_box_geom(L, *reinterpret_cast<const float4*>(boxes + 4 * (int64_t)n), pooled, sampling);
+    const int H = g.H, W = g.W;
+    const int cl = ((int)threadIdx.x % NV) * VM;
+    if (cl < cs) {
+        const TM* f = static_cast<const TM*>(L.feat[g.l]) + (int64_t)box_image[n] * H * W * L.C + c0 + cl;
+        for (int bin = (int)threadIdx.x / NV; bin < pp; bin += NG) {
+            const int ph = bin / pooled, pw = bin - ph * pooled;
+            float acc[VM];
+#pragma unroll
+            for (int j = 0; j < VM; ++j) acc[j] = 0.f;
+            for (int iy = 0; iy < g.gh; ++iy) {
+                const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
+                for (int ix = 0; ix < g.gw; ++ix) {
+                    const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
+                    skg_roi_taps t;
+                    if (!skg_roi_sample(H, W, y, x, t)) {
+#pragma unroll
+                        for (int j = 0; j < VM; ++j) acc[j] += 0.f;
+                        continue;
+                    }
+                    skg_roi_vec<MDT> v1, v2, v3, v4;
+                    v1.q = *reinterpret_cast<const uint4*>(f + ((int64_t)t.y_low * W + t.x_low) * L.C);
+                    v2.q = *reinterpret_cast<const uint4*>(f + ((int64_t)t.y_low * W + t.x_high) * L.C);
+                    v3.q = *reinterpret_cast<const uint4*>(f + ((int64_t)t.y_high * W + t.x_low) * L.C);
+                    v4.q = *reinterpret_cast<const uint4*>(f + ((int64_t)t.y_high * W + t.x_high) * L.C);
+#pragma unroll
+                    for (int j = 0; j < VM; ++j)
+                        acc[j] += t.w1 * EM::ld(v1.e, j) + t.w2 * EM::ld(v2.e, j) + t.w3 * EM::ld(v3.e, j) +
+                                  t.w4 * EM::ld(v4.e, j);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < VM; ++j) tile[(cl + j) * S + bin] = acc[j] / g.cnt;
+        }
+    }
+    __syncthreads();
+    // the slab's cs * pp outputs are contiguous in [rois, C, pooled, pooled]: 16-byte stores
+    TO* o = out + ((int64_t)n * L.C + c0) * pp;
+    const int nvec = cs * pp / VO;
+    for (int v = (int)threadIdx.x; v < nvec; v += 256) {
+        skg_roi_vec<ODT> r;
+#pragma unroll
+        for (int j = 0; j < VO; ++j) {
+            const int i = v * VO + j, c = i / pp;
+            EO::st(r.e, j, tile[c * S + (i - c * pp)]);
+        }
+        *reinterpret_cast<uint4*>(o + (int64_t)v * VO) = r.q;
+    }
+}
+
+// Backward into channels-last fp32 gradient maps: d out of the slab staged through LDS (16-byte loads); then a lane owns
+// one channel and a wave one bin at a time (waves take the bins round-robin, the bin geometry is wave-uniform), so every
+// atomic instruction of a full slab adds 256 contiguous bytes.  Same products as skg_roi_align_bwd_kernel.
+__global__ __launch_bounds__(256) void skg_roi_align_bwd_nhwc_kernel(const skg_roi_levels L, const float* __restrict__ boxes,
+                                                                     const int32_t* __restrict__ box_image, int n_slabs,
+                                                                     int pooled, int sampling,
+                                                                     const float* __restrict__ dout) {
+    constexpr int VM = 1, NV = SKG_ROI_NHWC_SLAB / VM, NG = 256 / NV;       // channels per lane, lanes per bin, bins in flight
+    __shared__ float tile[SKG_ROI_NHWC_TILE];
+    const int n = (int)(blockIdx.x / (unsigned)n_slabs);
+    const int c0 = (int)(blockIdx.x % (unsigned)n_slabs) * SKG_ROI_NHWC_SLAB;
+    const int cs = min(SKG_ROI_NHWC_SLAB, L.C - c0);
+    const int pp = pooled * pooled, S = pp | 1;
+    const float* d = dout + ((int64_t)n * L.C + c0) * pp;
+    for (int v = (int)threadIdx.x; v < cs * pp / 4; v += 256) {
+        const float4 q = *reinterpret_cast<const float4*>(d + (int64_t)v * 4);
+        const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = v * 4 + j, c = i / pp;
+            tile[c * S + (i - c * pp)] = e[j];
+        }
+    }
+    __syncthreads();
+    const skg_roi_geom g = skg_roi_box_geom(L, *reinterpret_cast<const float4*>(boxes + 4 * (int64_t)n), pooled, sampling);
+    const int H = g.H, W = g.W;
+    const int cl = ((int)threadIdx.x % NV) * VM;
+    if (cl >= cs) return;
+    float* f = static_cast<float*>(const_cast<void*>(L.feat[g.l])) + (int64_t)box_image[n] * H * W * L.C + c0 + cl;
+    for (int bin = (int)threadIdx.x / NV; bin < pp; bin += NG) {
+        const int ph = bin / pooled, pw = bin - ph * pooled;
+        float gr[VM];
+#pragma unroll
+        for (int j = 0; j < VM; ++j) gr[j] = tile[(cl + j) * S + bin] / g.cnt;
+        for (int iy = 0; iy < g.gh; ++iy) {
+            const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
+            for (int ix = 0; ix < g.gw; ++ix) {
+                const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
+                skg_roi_taps t;
+                if (!skg_roi_sample(H, W, y, x, t)) continue;
+                float* p1 = f + ((int64_t)t.y_low * W + t.x_low) * L.C;
+                float* p2 = f + ((int64_t)t.y_low * W + t.x_high) * L.C;
+                float* p3 = f + ((int64_t)t.y_high * W + t.x_low) * L.C;
+                float* p4 = f + ((int64_t)t.y_high * W + t.x_high) * L.C;
+#pragma unroll
+                for (int j = 0; j < VM; ++j) atomicAdd(p1 + j, t.w1 * gr[j]);
+#pragma unroll
+                for (int j = 0; j < VM; ++j) atomicAdd(p2 + j, t.w2 * gr[j]);
+#pragma unroll
+                for (int j = 0; j < VM; ++j) atomicAdd(p3 + j, t.w3 * gr[j]);
+#pragma unroll
+                for (int j = 0; j < VM; ++j) atomicAdd(p4 + j, t.w4 * gr[j]);
+            }
+        }
+    }
+}
+
+// launches since the last reset: forward NCHW, forward NHWC, backward NCHW, backward NHWC (skg_roi_align_layout_counts)
+static std::atomic<long long> g_roi_layout_counts[4];
+
 static int skg_roi_levels_fill(skg_roi_levels& L, const void* const* feats_host, const int32_t* H_host,
                                const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
                                float canonical_scale, int canonical_level) {
@@ -177,6 +369,7 @@ extern "C" int skg_roi_align_bwd_f32(float* const* dfeats_host, const int32_t* H
     const int64_t total = (int64_t)n_rois * C * pooled * pooled;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 64) blocks = 256 * 64;
+    g_roi_layout_counts[2].fetch_add(1, std::memory_order_relaxed);
     hipLaunchKernelGGL(skg_roi_align_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, L, boxes,
                        box_image, n_rois, pooled, sampling, dout);
     return skg_launch_status();
@@ -209,6 +402,7 @@ extern "C" int skg_roi_align_x(const void* const* feats_host, int map_dtype, con
     const int rc = skg_roi_levels_fill(L, feats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
                                        canonical_scale, canonical_level);
     if (rc) return rc;
+    g_roi_layout_counts[0].fetch_add(1, std::memory_order_relaxed);
     hipStream_t s = (hipStream_t)stream;
 #define SKG_ROI_OUT(M)                                                                                           \
     switch (out_dtype) {                                                                                         \
@@ -233,4 +427,95 @@ extern "C" int skg_roi_align_f32(const float* const* feats_host, const int32_t* 
     return skg_roi_align_x(reinterpret_cast<const void* const*>(feats_host), SKG_DTYPE_F32, H_host, W_host, scales_host,
                            n_levels, C, k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois,
                            pooled, sampling, out, SKG_DTYPE_F32, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ channels-last entries
+extern "C" void skg_roi_align_layout_counts(int64_t* out4, int reset) {
+    for (int i = 0; i < 4; ++i) {
+        if (out4) out4[i] = g_roi_layout_counts[i].load(std::memory_order_relaxed);
+        if (reset) g_roi_layout_counts[i].store(0, std::memory_order_relaxed);
+    }
+}
+
+// what both *_nhwc entries ask of the shape (header comment of this file)
+static int skg_roi_nhwc_check(int n_levels, int C, int k_min, int k_max, int pooled, int n_rois) {
+    if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
+        return SKG_E_ARG;
+    if ((C & 7) || pooled > SKG_ROI_NHWC_MAX_POOLED) return SKG_E_ARG;
+    return 0;
+}
+
+static int skg_roi_nhwc_levels(skg_roi_levels& L, const void* const* feats_host, const int32_t* H_host,
+                               const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                               float canonical_scale, int canonical_level, int n_rois, int64_t* blocks) {
+    const int rc = skg_roi_levels_fill(L, feats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
+                                       canonical_scale, canonical_level);
+    if (rc) return rc;
+    for (int l = 0; l < n_levels; ++l)
+        if (!skg_aligned16(L.feat[l])) return SKG_E_ALIGN;
+    *blocks = (int64_t)n_rois * ((C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB);
+    return *blocks > 0x7fffffffLL ? SKG_E_LIMIT : 0;
+}
+
+template <int MDT, int ODT>
+static void skg_roi_align_nhwc_launch(const skg_roi_levels& L, const float* boxes, const int32_t* box_image, int64_t blocks,
+                                      int pooled, int sampling, void* out, hipStream_t stream) {
+    hipLaunchKernelGGL((skg_roi_align_nhwc_kernel<MDT, ODT>), dim3((unsigned)blocks), dim3(256), 0, stream, L, boxes,
+                       box_image, (L.C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB, pooled, sampling,
+                       static_cast<typename skg_roi_elem<ODT>::T*>(out));
+}
+
+extern "C" int skg_roi_align_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
+                                    const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                                    int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                                    const int32_t* box_image, int n_rois, int pooled, int sampling, void* out,
+                                    int out_dtype, void* stream) {
+    int rc = skg_roi_nhwc_check(n_levels, C, k_min, k_max, pooled, n_rois);
+    if (rc) return rc;
+    if (map_dtype < SKG_DTYPE_F32 || map_dtype > SKG_DTYPE_BF16 || out_dtype < SKG_DTYPE_F32 || out_dtype > SKG_DTYPE_BF16)
+        return SKG_E_ARG;
+    if (n_rois == 0) return 0;
+    if (!feats_host || !H_host || !W_host || !scales_host || !boxes || !box_image || !out) return SKG_E_ARG;
+    if (!skg_aligned16(boxes) || !skg_aligned16(out)) return SKG_E_ALIGN;
+    skg_roi_levels L;
+    int64_t blocks = 0;
+    rc = skg_roi_nhwc_levels(L, feats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
+                             canonical_level, n_rois, &blocks);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    g_roi_layout_counts[1].fetch_add(1, std::memory_order_relaxed);
+#define SKG_ROI_OUT(M)                                                                                           \
+    switch (out_dtype) {                                                                                         \
+        case SKG_DTYPE_F32: skg_roi_align_nhwc_launch<M, SKG_DTYPE_F32>(L, boxes, box_image, blocks, pooled, sampling, out, s); break; \
+        case SKG_DTYPE_F16: skg_roi_align_nhwc_launch<M, SKG_DTYPE_F16>(L, boxes, box_image, blocks, pooled, sampling, out, s); break; \
+        default: skg_roi_align_nhwc_launch<M, SKG_DTYPE_BF16>(L, boxes, box_image, blocks, pooled, sampling, out, s); break;          \
+    }
+    switch (map_dtype) {
+        case SKG_DTYPE_F32: SKG_ROI_OUT(SKG_DTYPE_F32) break;
+        case SKG_DTYPE_F16: SKG_ROI_OUT(SKG_DTYPE_F16) break;
+        default: SKG_ROI_OUT(SKG_DTYPE_BF16) break;
+    }
+#undef SKG_ROI_OUT
+    return skg_launch_status();
+}
+
+extern "C" int skg_roi_align_bwd_nhwc_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                                          const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                          float canonical_scale, int canonical_level, const float* boxes,
+                                          const int32_t* box_image, int n_rois, int pooled, int sampling,
+                                          const float* dout, void* stream) {
+    int rc = skg_roi_nhwc_check(n_levels, C, k_min, k_max, pooled, n_rois);
+    if (rc) return rc;
+    if (n_rois == 0) return 0;
+    if (!dfeats_host || !H_host || !W_host || !scales_host || !boxes || !box_image || !dout) return SKG_E_ARG;
+    if (!skg_aligned16(boxes) || !skg_aligned16(dout)) return SKG_E_ALIGN;
+    skg_roi_levels L;
+    int64_t blocks = 0;
+    rc = skg_roi_nhwc_levels(L, reinterpret_cast<const void* const*>(dfeats_host), H_host, W_host, scales_host, n_levels,
+                             C, k_min, k_max, canonical_scale, canonical_level, n_rois, &blocks);
+    if (rc) return rc;
+    g_roi_layout_counts[3].fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(skg_roi_align_bwd_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, L, boxes,
+                       box_image, (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB, pooled, sampling, dout);
+    return skg_launch_status();
 }

@@ -12,6 +12,10 @@ the feature maps (`skg_roi_align_bwd_f32`): the reference trains the detector's 
 Half-precision maps (all levels bf16, or all fp16) are read in place by `skg_roi_align_x`, with the arithmetic of the
 fp32 kernel on the exactly widened values; `output_dtype` (default float32) picks the dtype of the pooled features, a half
 output being the fp32 result rounded once.  Any other mix of map dtypes is widened to fp32 first, as before.
+
+Channels-last maps (what a backbone run with memory_format=torch.channels_last hands over) are read in place too
+(`skg_roi_align_nhwc_x`, `channels_last_route` below says when), with bit-identical results; their gradients come back
+channels-last (`skg_roi_align_bwd_nhwc_f32`).  Every other layout is made [B, C, H, W]-contiguous first, as before.
 """
 import ctypes as C
 import math
@@ -26,6 +30,7 @@ from .engine import _stream
 
 
 _HALF_CODES = {torch.float16: _capi.DTYPE_F16, torch.bfloat16: _capi.DTYPE_BF16}
+_NHWC_MAX_POOLED = 8                                    # skg_roi_align_nhwc_x: larger outputs take the [B, C, H, W] route
 _OUT_CODES = {torch.float32: _capi.DTYPE_F32, torch.float16: _capi.DTYPE_F16, torch.bfloat16: _capi.DTYPE_BF16}
 
 
@@ -36,6 +41,20 @@ def _level_args(feats, scales):
             (C.c_float * L)(*scales))
 
 
+def channels_last_route(feats) -> bool:
+    """True when the maps are read in place as [B, H, W, C] memory: every level channels-last and NOT also plain
+    contiguous (C = 1 or H = W = 1 satisfy both: they stay on the [B, C, H, W] route), one dtype of fp32 / bf16 / fp16 for
+    all levels, C % 8 == 0 and every base address 16-byte aligned (the limits of skg_roi_align_nhwc_x).  Needs no device."""
+    if not feats or any(f.dim() != 4 for f in feats):
+        return False
+    if len({f.dtype for f in feats}) != 1 or feats[0].dtype not in _OUT_CODES:
+        return False
+    if feats[0].shape[1] % 8 != 0:
+        return False
+    return all(f.is_contiguous(memory_format=torch.channels_last) and not f.is_contiguous() and f.data_ptr() % 16 == 0
+               for f in feats)
+
+
 class _RoIAlignFn(torch.autograd.Function):
     """out = MultiScaleRoIAlign(feats...); backward scatters d out into zeroed feature gradients (float atomics)."""
 
@@ -43,8 +62,12 @@ class _RoIAlignFn(torch.autograd.Function):
     def forward(ctx, cfg, rois, img, *feats):
         scales, k_min, k_max, canon_s, canon_l, pooled, sampling, out_dtype = cfg
         dts = {f.dtype for f in feats}
+        nhwc = pooled <= _NHWC_MAX_POOLED and channels_last_route(feats)
         map_code = _HALF_CODES.get(feats[0].dtype) if len(dts) == 1 else None
-        if map_code is None:                        # fp32, fp64, mixed: widened to fp32 first
+        if nhwc:                                    # channels-last: the tensors' own storage, no copy of any level
+            map_code = _OUT_CODES[feats[0].dtype]
+            fs = list(feats)
+        elif map_code is None:                        # fp32, fp64, mixed: widened to fp32 first
             map_code = _capi.DTYPE_F32
             fs = [f.float().contiguous() for f in feats]
         else:                                       # one half dtype: read in place (no fp32 copy of any level)
@@ -52,7 +75,12 @@ class _RoIAlignFn(torch.autograd.Function):
         n_rois, Cc = rois.shape[0], fs[0].shape[1]
         out = torch.empty(n_rois, Cc, pooled, pooled, device=rois.device, dtype=out_dtype)
         ptrs, Hs, Ws, sc = _level_args(fs, scales)
-        if map_code == _capi.DTYPE_F32 and out_dtype == torch.float32:
+        if nhwc:
+            _capi.check(_capi.lib().skg_roi_align_nhwc_x(ptrs, map_code, Hs, Ws, sc, len(fs), Cc, k_min, k_max,
+                                                         float(canon_s), int(canon_l), rois.data_ptr(), img.data_ptr(),
+                                                         n_rois, pooled, sampling, out.data_ptr(), _OUT_CODES[out_dtype],
+                                                         _stream()), "skg_roi_align_nhwc_x")
+        elif map_code == _capi.DTYPE_F32 and out_dtype == torch.float32:
             _capi.check(_capi.lib().skg_roi_align_f32(ptrs, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s),
                                                       int(canon_l), rois.data_ptr(), img.data_ptr(), n_rois, pooled,
                                                       sampling, out.data_ptr(), _stream()), "skg_roi_align_f32")
@@ -64,12 +92,22 @@ class _RoIAlignFn(torch.autograd.Function):
         ctx.cfg, ctx.rois, ctx.img = cfg, rois, img
         ctx.shapes = [tuple(f.shape) for f in fs]
         ctx.dtypes = [f.dtype for f in feats]
+        ctx.nhwc = nhwc
         return out
 
     @staticmethod
     def backward(ctx, dout):
         scales, k_min, k_max, canon_s, canon_l, pooled, sampling, _ = ctx.cfg
         dout = dout.float().contiguous()
+        if ctx.nhwc:                                # gradients of channels-last maps stay channels-last
+            dfs = [torch.empty(sh, device=dout.device, dtype=torch.float32, memory_format=torch.channels_last).zero_()
+                   for sh in ctx.shapes]
+            ptrs, Hs, Ws, sc = _level_args(dfs, scales)
+            _capi.check(_capi.lib().skg_roi_align_bwd_nhwc_f32(ptrs, Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min, k_max,
+                                                               float(canon_s), int(canon_l), ctx.rois.data_ptr(),
+                                                               ctx.img.data_ptr(), ctx.rois.shape[0], pooled, sampling,
+                                                               dout.data_ptr(), _stream()), "skg_roi_align_bwd_nhwc_f32")
+            return (None, None, None) + tuple(d.to(t) for d, t in zip(dfs, ctx.dtypes))
         dfs = [torch.zeros(sh, device=dout.device, dtype=torch.float32) for sh in ctx.shapes]
         ptrs, Hs, Ws, sc = _level_args(dfs, scales)
         _capi.check(_capi.lib().skg_roi_align_bwd_f32(ptrs, Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min, k_max,
@@ -143,4 +181,4 @@ class MultiScaleRoIAlign(nn.Module):
 
 
 class _NoCtx:
-    """Stand-in for the autograd context on the no-gradient path (the forward stores three attributes on it)."""
+    """Stand-in for the autograd context on the no-gradient path (the forward stores a few attributes on it)."""

@@ -1,0 +1,127 @@
+"""CPU tests of RoIAlign on channels-last maps: the C ABI of skg_roi_align_nhwc_x / skg_roi_align_bwd_nhwc_f32 /
+skg_roi_align_layout_counts (argument validation returns before any GPU call) and the module's routing predicate."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+
+from skghoi_amd import _capi
+from skghoi_amd.roi_pool import channels_last_route
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("skg_roi_align_nhwc_x", "skg_roi_align_bwd_nhwc_f32", "skg_roi_align_layout_counts")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _capi.lib()
+
+
+def test_new_symbols_exported_with_prototypes(lib):
+    hdr = open(os.path.join(ROOT, "include", "skghoi.h")).read()
+    declared = set(re.findall(r"\b(skg_[a-z0-9_]+)\s*\(", hdr))
+    for name in NEW:
+        assert name in declared and name in _capi.PROTOTYPES, name
+        assert getattr(lib, name) is not None
+    assert _capi.PROTOTYPES["skg_roi_align_nhwc_x"] == _capi.PROTOTYPES["skg_roi_align_x"]
+    assert _capi.PROTOTYPES["skg_roi_align_bwd_nhwc_f32"] == _capi.PROTOTYPES["skg_roi_align_bwd_f32"]
+    assert lib.skg_abi_version() == 19
+
+
+def _levels(n, base=16):
+    """n levels of fake (never dereferenced) device addresses with real host size / scale arrays."""
+    return ((C.c_void_p * max(n, 1))(*[base + 256 * i for i in range(max(n, 1))]),
+            (C.c_int32 * max(n, 1))(*[8] * max(n, 1)), (C.c_int32 * max(n, 1))(*[8] * max(n, 1)),
+            (C.c_float * max(n, 1))(*[0.25] * max(n, 1)))
+
+
+def _fwd(lib, p, H, W, sc, n_levels=1, Cc=8, k_min=0, k_max=0, boxes=16, img=16, n_rois=2, pooled=7, out=16, map_dt=2,
+         out_dt=2):
+    return lib.skg_roi_align_nhwc_x(p, map_dt, H, W, sc, n_levels, Cc, k_min, k_max, 224.0, 4, boxes, img, n_rois, pooled, 2,
+                                    out, out_dt, None)
+
+
+def _bwd(lib, p, H, W, sc, n_levels=1, Cc=8, k_min=0, k_max=0, boxes=16, img=16, n_rois=2, pooled=7, dout=16):
+    return lib.skg_roi_align_bwd_nhwc_f32(p, H, W, sc, n_levels, Cc, k_min, k_max, 224.0, 4, boxes, img, n_rois, pooled, 2,
+                                          dout, None)
+
+
+@pytest.mark.parametrize("call", [_fwd, _bwd], ids=["forward", "backward"])
+def test_nhwc_entries_reject_before_any_gpu_call(lib, call):
+    p, H, W, sc = _levels(1)
+    last = "out" if call is _fwd else "dout"
+    for Cc in (6, 12, 0, -8):
+        assert call(lib, p, H, W, sc, Cc=Cc) < 0, Cc
+    p8 = _levels(1, base=8)[0]
+    assert call(lib, p8, H, W, sc) == -2                               # a level base at address 8: SKG_E_ALIGN
+    p4 = _levels(4)
+    bad = (C.c_void_p * 4)(16, 32, 40, 64)                             # a later level misaligned
+    assert call(lib, bad, *p4[1:], n_levels=4, k_min=2, k_max=5) == -2
+    assert call(lib, p, H, W, sc, boxes=8) == -2
+    assert call(lib, p, H, W, sc, **{last: 8}) == -2
+    p9 = _levels(9)
+    assert call(lib, p, H, W, sc, n_levels=0, k_min=0, k_max=-1) < 0
+    assert call(lib, *p9, n_levels=9, k_min=0, k_max=8) < 0
+    assert call(lib, *p4, n_levels=4, k_min=2, k_max=4) < 0           # k_max - k_min + 1 != n_levels
+    assert call(lib, *p4, n_levels=4, k_min=2, k_max=6) < 0
+    for pooled in (0, -1, 9):                                          # 9: beyond the LDS tile
+        assert call(lib, p, H, W, sc, pooled=pooled) < 0, pooled
+    assert call(lib, None, H, W, sc) < 0
+    assert call(lib, p, None, W, sc) < 0
+    assert call(lib, p, H, None, sc) < 0
+    assert call(lib, p, H, W, None) < 0
+    assert call(lib, p, H, W, sc, boxes=None) < 0
+    assert call(lib, p, H, W, sc, img=None) < 0
+    assert call(lib, p, H, W, sc, **{last: None}) < 0
+    assert call(lib, (C.c_void_p * 1)(None), H, W, sc) < 0             # a null level
+    assert call(lib, p, H, W, sc, n_rois=-1) < 0
+    assert call(lib, p, H, W, sc, n_rois=0) == 0
+    assert call(lib, *p4, n_levels=4, k_min=2, k_max=5, n_rois=0) == 0
+
+
+def test_nhwc_forward_rejects_unknown_dtypes(lib):
+    p, H, W, sc = _levels(1)
+    for map_dt, out_dt in ((3, 0), (-1, 0), (0, 3), (2, -1)):
+        assert _fwd(lib, p, H, W, sc, map_dt=map_dt, out_dt=out_dt) < 0
+        assert _fwd(lib, p, H, W, sc, map_dt=map_dt, out_dt=out_dt, n_rois=0) < 0
+    for map_dt in range(3):
+        for out_dt in range(3):
+            assert _fwd(lib, p, H, W, sc, map_dt=map_dt, out_dt=out_dt, n_rois=0) == 0
+
+
+def test_layout_counts_read_and_reset(lib):
+    out = (C.c_int64 * 4)(-1, -1, -1, -1)
+    lib.skg_roi_align_layout_counts(out, 1)
+    assert all(v >= 0 for v in out)
+    lib.skg_roi_align_layout_counts(out, 0)
+    assert list(out) == [0, 0, 0, 0]
+    p, H, W, sc = _levels(1)
+    assert _fwd(lib, p, H, W, sc, Cc=6) < 0 and _bwd(lib, p, H, W, sc, n_rois=0) == 0   # neither launches
+    lib.skg_roi_align_layout_counts(out, 1)
+    assert list(out) == [0, 0, 0, 0]
+    lib.skg_roi_align_layout_counts(None, 0)                           # a null buffer is only a reset request
+
+
+def _cl(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype).contiguous(memory_format=torch.channels_last)
+
+
+def test_routing_predicate_on_cpu_tensors():
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        assert channels_last_route([_cl(2, 8, 5, 7, dtype=dt)])
+        assert channels_last_route([_cl(2, 8, 10, 14, dtype=dt), _cl(2, 8, 5, 7, dtype=dt)])
+    assert not channels_last_route([_cl(2, 6, 5, 7)])                  # C % 8
+    assert not channels_last_route([_cl(2, 12, 5, 7)])
+    assert not channels_last_route([_cl(2, 8, 10, 14), torch.zeros(2, 8, 5, 7)])           # mixed layouts
+    assert not channels_last_route([_cl(2, 8, 10, 14), _cl(2, 8, 5, 7, dtype=torch.bfloat16)])   # mixed dtypes
+    assert not channels_last_route([torch.zeros(2, 8, 5, 7)])          # plain contiguous
+    assert not channels_last_route([_cl(2, 1, 5, 7)])                  # [B, 1, H, W]: both layouts at once
+    assert not channels_last_route([_cl(2, 8, 1, 1)])                  # H = W = 1 too
+    assert not channels_last_route([_cl(2, 8, 5, 7, dtype=torch.float64)])
+    assert not channels_last_route([_cl(2, 8, 10, 14), _cl(2, 8, 10, 14)[:, :, ::2, ::2]])  # a strided view
+    off = torch.zeros(2 * 8 * 5 * 7 + 1, dtype=torch.bfloat16)[1:].view(2, 5, 7, 8).permute(0, 3, 1, 2)
+    assert off.is_contiguous(memory_format=torch.channels_last) and off.data_ptr() % 16 != 0
+    assert not channels_last_route([off])                              # base not 16-byte aligned
+    assert not channels_last_route([])

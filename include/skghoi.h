@@ -176,6 +176,40 @@ int skg_roi_align_bwd_nhwc_f32(float* const* dfeats_host, const int32_t* H_host,
 /* Statistics: RoIAlign launches since the last reset -- out4 = forward [B,C,H,W], forward channels-last, backward
  * [B,C,H,W], backward channels-last (skg_roi_align_f32 counts as skg_roi_align_x); reset != 0 zeroes them after the read. */
 void skg_roi_align_layout_counts(int64_t out4[4], int reset);
+/* DETERMINISTIC backward of skg_roi_align_x with respect to the feature maps: an owner-computes gather without atomics.
+ * dfeats_host[l] points at an UNINITIALISED [n_images, C, H_l, W_l] gradient map of grad_dtype elements (SKG_DTYPE_*).
+ * Write-every-element rule: every element of every map is stored exactly once, by one thread -- also the elements no RoI
+ * touches and the images without boxes (they get 0), so n_rois == 0 is NOT a no-op: it writes zeros to every map.  A RoI
+ * whose box_image lies outside [0, n_images) contributes nothing.
+ * Summation order of a gradient element (l, b, c, y, x), independent of layout, tiling and grid: acc = 0.f; RoIs in
+ * ascending index; within a RoI the sample rows sy = ph * gh + iy ascending, then the sample columns sx = pw * gw + ix
+ * ascending; within a sample its four bilinear taps in the order (y_low, x_low), (y_low, x_high), (y_high, x_low),
+ * (y_high, x_high); a tap counts only when its coordinates equal (y, x), so a sample clamped at a border can hit one pixel
+ * with two taps; every term is (wy * wx) * (dout[r, c, ph, pw] / count), the product of skg_roi_align_bwd_f32; fp32
+ * accumulation without contraction; one store, rounded to nearest even when grad_dtype is a half type.  So a half gradient
+ * is the fp32 gradient rounded once, and both layouts give the same bits.
+ * Errors, all before any GPU call: SKG_E_ARG for a bad argument (grad_dtype outside 0..2, n_images <= 0, a null pointer;
+ * boxes / box_image / dout may be null only when n_rois == 0), SKG_E_ALIGN for boxes not 16-byte aligned, SKG_E_LIMIT for
+ * more than 2^31 - 1 workgroups (one per level x image x 32 x 8 pixels x 16 channels).  No workspace.               */
+int skg_roi_align_bwd_det_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host, const int32_t* W_host,
+                            const float* scales_host, int n_levels, int C, int k_min, int k_max, float canonical_scale,
+                            int canonical_level, const float* boxes, const int32_t* box_image, int n_rois, int n_images,
+                            int pooled, int sampling, const float* dout, void* stream);
+/* The same on CHANNELS-LAST gradient maps: dfeats_host[l] points at UNINITIALISED [n_images, H_l, W_l, C] memory of
+ * grad_dtype elements.  Same write-every-element rule (n_rois == 0 writes zeros) and the same summation order -- acc = 0.f,
+ * RoIs ascending, sample rows then sample columns ascending, taps 1..4, terms (wy * wx) * (dout / count), one rounding -- so
+ * the result equals skg_roi_align_bwd_det_x on [n_images, C, H_l, W_l] maps bit for bit.  Limits, those of
+ * skg_roi_align_bwd_nhwc_f32: C % 8 == 0 and pooled <= 8 (else SKG_E_ARG: 16-byte channel vectors, the LDS tile of d out);
+ * every level base, boxes and dout 16-byte aligned (else SKG_E_ALIGN); at most 2^31 - 1 workgroups (one per level x image x
+ * 8 x 8 pixels x 64 channels, else SKG_E_LIMIT).                                                                     */
+int skg_roi_align_bwd_det_nhwc_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host, const int32_t* W_host,
+                                 const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                 float canonical_scale, int canonical_level, const float* boxes,
+                                 const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling,
+                                 const float* dout, void* stream);
+/* Statistics: deterministic backward launches since the last reset -- out2 = [B,C,H,W], channels-last.  They do not count
+ * in skg_roi_align_layout_counts; reset != 0 zeroes them after the read.                                            */
+void skg_roi_align_det_counts(int64_t out2[2], int reset);
 
 /* AdaptiveAvgPool2d(1) of features['3'] (HEAD:811): in [B, C, HW] -> out [B, C]. */
 int skg_global_avgpool_f32(const float* in, int B, int C, int HW, float* out, void* stream);

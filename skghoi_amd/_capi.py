@@ -134,6 +134,11 @@ PROTOTYPES = {
     "skg_roi_align_bwd_nhwc_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, C.c_int, _vp,
                                              _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "skg_roi_align_layout_counts": (None, [C.POINTER(_i64), C.c_int]),
+    "skg_roi_align_bwd_det_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, C.c_int,
+                                          _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "skg_roi_align_bwd_det_nhwc_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32,
+                                               C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "skg_roi_align_det_counts": (None, [C.POINTER(_i64), C.c_int]),
     "skg_global_avgpool_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "skg_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "skg_transh_draw_f32": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),

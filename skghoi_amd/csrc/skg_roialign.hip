@@ -519,3 +519,319 @@ extern "C" int skg_roi_align_bwd_nhwc_f32(float* const* dfeats_host, const int32
                        box_image, (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB, pooled, sampling, dout);
     return skg_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------ deterministic backward
+// Owner-computes gather, no atomics: one workgroup per (level, image, pixel tile, channel slab), all levels in one launch.
+// Every gradient element (l, b, c, y, x) is produced by exactly one thread and stored exactly once -- also the elements no
+// RoI touches (0) and the images without boxes -- so the maps need no zero fill and hold the maps' dtype directly.
+// The sum of an element, in this fixed order whatever the layout, tile, slab or grid:
+//     acc = 0.f; RoIs in ascending index; within a RoI the sample rows sy = ph * gh + iy ascending, then the sample columns
+//     sx = pw * gw + ix ascending; within a sample its taps in the order 1..4 of skg_roi_taps; a tap counts when its
+//     coordinates equal (y, x) (a clamped sample can hit one pixel with two taps); term = (wy * wx) * (dout[r, c, ph, pw] / cnt),
+//     the product t.wK * gr of the atomics kernels; fp32 accumulation, one store through skg_roi_elem<DT>::st.
+// A workgroup's threads each take a RoI of a chunk of SKG_ROI_DET_CHUNK, recompute its geometry (skg_roi_box_geom: the
+// forward's level bit for bit), test a superset of its tap rectangle against the tile and compact the hits in ascending RoI
+// index into an LDS list; the chunks follow each other, so n_rois is unbounded and no workspace is needed.  The per-pixel
+// tap tests walk the 1-D sample rows and columns with the forward's expressions (skg_roi_sample's rules per axis): the
+// sampling is never inverted analytically, and the walk indexes no memory by a tap coordinate.
+#define SKG_ROI_DET_CHUNK 256
+#define SKG_ROI_DET_TW 32                      // [B, C, H, W]: 32 x 8 pixels, lanes along x, 16 channels per slab
+#define SKG_ROI_DET_TH 8
+#define SKG_ROI_DET_CS 16
+#define SKG_ROI_DET_NT 8                       // channels-last: 8 x 8 pixels, lanes along channels, SKG_ROI_NHWC_SLAB channels
+
+struct skg_roi_det_grid {
+    int tiles_x[SKG_ROI_MAX_LEVELS], tiles_y[SKG_ROI_MAX_LEVELS];
+    unsigned start[SKG_ROI_MAX_LEVELS + 1];    // first workgroup of a level; per level: image slowest, tile, slab fastest
+    int n_slabs;
+};
+
+// a listed RoI: what the tap walk needs of skg_roi_geom
+struct skg_roi_det_item {
+    int r, gh, gw;
+    float x1, y1, bw, bh, cnt;
+};
+
+// One axis of skg_roi_sample: false when the sample lies outside on this axis; l / h are ly / hy (lx / hx).
+struct skg_roi_axis {
+    int low, high;
+    float l, h;
+};
+__device__ __forceinline__ bool skg_roi_axis_sample(int size, float v, skg_roi_axis& a) {
+    if (v < -1.0f || v > (float)size) return false;
+    if (v <= 0.f) v = 0.f;
+    int low = (int)v, high;
+    if (low >= size - 1) { high = low = size - 1; v = (float)low; } else high = low + 1;
+    a.low = low; a.high = high;
+    a.l = v - low; a.h = 1.f - a.l;
+    return true;
+}
+
+// The taps of RoI `it` that land on pixel (py, px), in the contract's order: add(bin, wy * wx) per tap.
+template <class F>
+__device__ __forceinline__ void skg_roi_det_walk(const skg_roi_det_item& it, int H, int W, int pooled, int py, int px, F add) {
+    for (int ph = 0; ph < pooled; ++ph)
+        for (int iy = 0; iy < it.gh; ++iy) {
+            const float y = it.y1 + ph * it.bh + (iy + 0.5f) * it.bh / (float)it.gh;
+            skg_roi_axis ay;
+            if (!skg_roi_axis_sample(H, y, ay)) continue;
+            const bool yl = ay.low == py, yh = ay.high == py;
+            if (!yl && !yh) continue;
+            for (int pw = 0; pw < pooled; ++pw)
+                for (int ix = 0; ix < it.gw; ++ix) {
+                    const float x = it.x1 + pw * it.bw + (ix + 0.5f) * it.bw / (float)it.gw;
+                    skg_roi_axis ax;
+                    if (!skg_roi_axis_sample(W, x, ax)) continue;
+                    const bool xl = ax.low == px, xh = ax.high == px;
+                    if (!xl && !xh) continue;
+#pragma unroll 1
+                    for (int k = 0; k < 4; ++k) {                      // taps 1..4: (low, low) (low, high) (high, low) (high, high)
+                        if (!((k < 2 ? yl : yh) && ((k & 1) ? xh : xl))) continue;
+                        add(ph * pooled + pw, (k < 2 ? ay.h : ay.l) * ((k & 1) ? ax.l : ax.h));
+                    }
+                }
+        }
+}
+
+// RoIs chunk0 .. chunk0 + 255 of image b on level l whose taps can reach the tile [ty0, ty1] x [tx0, tx1]: compacted in
+// ascending index into s_item, their number in *s_n (valid after the call, which ends in a barrier).  The rectangle test is
+// a superset (first / last sample of each axis, a pixel of margin for the rounding of the coordinates): a listed RoI without
+// a tap on a pixel adds nothing there.  Compared in float, so no box value is converted to an integer.
+__device__ __forceinline__ int skg_roi_det_list(const skg_roi_levels& L, const float* __restrict__ boxes,
+                                                const int32_t* __restrict__ box_image, int n_rois, int chunk0, int l, int b,
+                                                int ty0, int ty1, int tx0, int tx1, int pooled, int sampling,
+                                                uint32_t* s_hit, skg_roi_det_item* s_item, int* s_n) {
+    const int tid = (int)threadIdx.x, r = chunk0 + tid;
+    unsigned char* hb = reinterpret_cast<unsigned char*>(s_hit);
+    bool hit = false;
+    skg_roi_det_item it;
+    if (r < n_rois && box_image[r] == b) {
+        const skg_roi_geom g = skg_roi_box_geom(L, *reinterpret_cast<const float4*>(boxes + 4 * (int64_t)r), pooled, sampling);
+        if (g.l == l) {
+            const float yf = g.y1 + 0 * g.bh + (0 + 0.5f) * g.bh / (float)g.gh;
+            const float ye = g.y1 + (pooled - 1) * g.bh + ((g.gh - 1) + 0.5f) * g.bh / (float)g.gh;
+            const float xf = g.x1 + 0 * g.bw + (0 + 0.5f) * g.bw / (float)g.gw;
+            const float xe = g.x1 + (pooled - 1) * g.bw + ((g.gw - 1) + 0.5f) * g.bw / (float)g.gw;
+            hit = !(floorf(fmaxf(ye, 0.f)) + 2.f < (float)ty0) && !(floorf(fmaxf(yf, 0.f)) - 1.f > (float)ty1) &&
+                  !(floorf(fmaxf(xe, 0.f)) + 2.f < (float)tx0) && !(floorf(fmaxf(xf, 0.f)) - 1.f > (float)tx1);
+            it.r = r; it.gh = g.gh; it.gw = g.gw;
+            it.x1 = g.x1; it.y1 = g.y1; it.bw = g.bw; it.bh = g.bh; it.cnt = g.cnt;
+        }
+    }
+    hb[tid] = hit ? 1 : 0;
+    __syncthreads();
+    int pos = 0;                                                       // hits of the threads below this one
+    for (int w = 0; w < tid / 4; ++w) pos += (int)((s_hit[w] * 0x01010101u) >> 24);
+    for (int k = tid & ~3; k < tid; ++k) pos += hb[k];
+    if (hit) s_item[pos] = it;
+    if (tid == SKG_ROI_DET_CHUNK - 1) *s_n = pos + (hit ? 1 : 0);
+    __syncthreads();
+    return *s_n;
+}
+
+// workgroup -> (level, image, tile, slab)
+__device__ __forceinline__ void skg_roi_det_item_of_block(const skg_roi_levels& L, const skg_roi_det_grid& G, int& l, int& b,
+                                                          int& tile_y, int& tile_x, int& slab) {
+    l = 0;
+    while (l + 1 < L.n_levels && blockIdx.x >= G.start[l + 1]) ++l;
+    unsigned rem = blockIdx.x - G.start[l];
+    slab = (int)(rem % (unsigned)G.n_slabs); rem /= (unsigned)G.n_slabs;
+    const unsigned nt = (unsigned)(G.tiles_x[l] * G.tiles_y[l]);
+    const unsigned t = rem % nt;
+    b = (int)(rem / nt);
+    tile_y = (int)(t / (unsigned)G.tiles_x[l]); tile_x = (int)(t % (unsigned)G.tiles_x[l]);
+}
+
+// [B, C, H, W] gradient maps of dtype DT: a thread owns one pixel of the 32 x 8 tile (lanes along x) and the slab's channels.
+template <int DT>
+__global__ __launch_bounds__(256) void skg_roi_align_bwd_det_kernel(const skg_roi_levels L, const skg_roi_det_grid G,
+                                                                    const float* __restrict__ boxes,
+                                                                    const int32_t* __restrict__ box_image, int n_rois,
+                                                                    int pooled, int sampling, const float* __restrict__ dout) {
+    typedef skg_roi_elem<DT> E;
+    typedef typename E::T T;
+    constexpr int CS = SKG_ROI_DET_CS;
+    __shared__ uint32_t s_hit[SKG_ROI_DET_CHUNK / 4];
+    __shared__ skg_roi_det_item s_item[SKG_ROI_DET_CHUNK];
+    __shared__ int s_n;
+    int l, b, tile_y, tile_x, slab;
+    skg_roi_det_item_of_block(L, G, l, b, tile_y, tile_x, slab);
+    const int H = L.H[l], W = L.W[l];
+    const int ty0 = tile_y * SKG_ROI_DET_TH, tx0 = tile_x * SKG_ROI_DET_TW;
+    const int ty1 = min(ty0 + SKG_ROI_DET_TH, H) - 1, tx1 = min(tx0 + SKG_ROI_DET_TW, W) - 1;
+    const int py = ty0 + (int)threadIdx.x / SKG_ROI_DET_TW, px = tx0 + (int)threadIdx.x % SKG_ROI_DET_TW;
+    const bool own = py < H && px < W;
+    const int c0 = slab * CS, cs = min(CS, L.C - c0), pp = pooled * pooled;
+    float acc[CS];
+#pragma unroll
+    for (int j = 0; j < CS; ++j) acc[j] = 0.f;
+    for (int chunk0 = 0; chunk0 < n_rois; chunk0 += SKG_ROI_DET_CHUNK) {
+        const int n = skg_roi_det_list(L, boxes, box_image, n_rois, chunk0, l, b, ty0, ty1, tx0, tx1, pooled, sampling, s_hit,
+                                       s_item, &s_n);
+        if (!own) continue;
+        for (int i = 0; i < n; ++i) {
+            const skg_roi_det_item it = s_item[i];
+            const float* d = dout + ((int64_t)it.r * L.C + c0) * pp;
+            skg_roi_det_walk(it, H, W, pooled, py, px, [&](int bin, float w) {
+#pragma unroll
+                for (int j = 0; j < CS; ++j)
+                    if (j < cs) acc[j] += w * (d[(int64_t)j * pp + bin] / it.cnt);
+            });
+        }
+    }
+    if (!own) return;
+    T* f = static_cast<T*>(const_cast<void*>(L.feat[l])) + ((int64_t)b * L.C + c0) * H * W + (int64_t)py * W + px;
+#pragma unroll
+    for (int j = 0; j < CS; ++j)
+        if (j < cs) E::st(f, (int64_t)j * H * W, acc[j]);
+}
+
+// Channels-last gradient maps of dtype DT: a lane owns 16 bytes of consecutive channels (4 fp32 / 8 half) of the slab for
+// 64 / NG pixels of the 8 x 8 tile; d out of a listed RoI's slab is staged through LDS with 16-byte loads (divided by the
+// sample count on the way: the gr of the atomics kernel) and the gradient leaves as 16-byte stores.
+template <int DT>
+__global__ __launch_bounds__(256) void skg_roi_align_bwd_det_nhwc_kernel(const skg_roi_levels L, const skg_roi_det_grid G,
+                                                                         const float* __restrict__ boxes,
+                                                                         const int32_t* __restrict__ box_image, int n_rois,
+                                                                         int pooled, int sampling,
+                                                                         const float* __restrict__ dout) {
+    typedef skg_roi_elem<DT> E;
+    typedef typename E::T T;
+    constexpr int VG = 16 / (int)sizeof(T);                    // channels per lane
+    constexpr int NV = SKG_ROI_NHWC_SLAB / VG;                 // lanes per pixel
+    constexpr int NG = 256 / NV;                               // pixels in flight
+    constexpr int NP = SKG_ROI_DET_NT * SKG_ROI_DET_NT / NG;   // pixels per thread
+    __shared__ float tile[SKG_ROI_NHWC_TILE];                  // [channel of the slab][pp | 1] of d out / cnt
+    __shared__ uint32_t s_hit[SKG_ROI_DET_CHUNK / 4];
+    __shared__ skg_roi_det_item s_item[SKG_ROI_DET_CHUNK];
+    __shared__ int s_n;
+    int l, b, tile_y, tile_x, slab;
+    skg_roi_det_item_of_block(L, G, l, b, tile_y, tile_x, slab);
+    const int H = L.H[l], W = L.W[l];
+    const int ty0 = tile_y * SKG_ROI_DET_NT, tx0 = tile_x * SKG_ROI_DET_NT;
+    const int ty1 = min(ty0 + SKG_ROI_DET_NT, H) - 1, tx1 = min(tx0 + SKG_ROI_DET_NT, W) - 1;
+    const int c0 = slab * SKG_ROI_NHWC_SLAB, cs = min(SKG_ROI_NHWC_SLAB, L.C - c0);    // cs: a multiple of 8
+    const int pp = pooled * pooled, S = pp | 1;
+    const int cl = ((int)threadIdx.x % NV) * VG, grp = (int)threadIdx.x / NV;
+    int py[NP], px[NP];
+    bool own[NP];
+    float acc[NP][VG];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        const int p = grp + k * NG;
+        py[k] = ty0 + p / SKG_ROI_DET_NT; px[k] = tx0 + p % SKG_ROI_DET_NT;
+        own[k] = cl < cs && py[k] < H && px[k] < W;
+#pragma unroll
+        for (int j = 0; j < VG; ++j) acc[k][j] = 0.f;
+    }
+    for (int chunk0 = 0; chunk0 < n_rois; chunk0 += SKG_ROI_DET_CHUNK) {
+        const int n = skg_roi_det_list(L, boxes, box_image, n_rois, chunk0, l, b, ty0, ty1, tx0, tx1, pooled, sampling, s_hit,
+                                       s_item, &s_n);
+        for (int i = 0; i < n; ++i) {
+            const skg_roi_det_item it = s_item[i];
+            const float* d = dout + ((int64_t)it.r * L.C + c0) * pp;
+            for (int v = (int)threadIdx.x; v < cs * pp / 4; v += 256) {
+                const float4 q = *reinterpret_cast<const float4*>(d + (int64_t)v * 4);
+                const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int t = v * 4 + j, c = t / pp;
+                    tile[c * S + (t - c * pp)] = e[j] / it.cnt;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                if (!own[k]) continue;
+                skg_roi_det_walk(it, H, W, pooled, py[k], px[k], [&](int bin, float w) {
+#pragma unroll
+                    for (int j = 0; j < VG; ++j) acc[k][j] += w * tile[(cl + j) * S + bin];
+                });
+            }
+            __syncthreads();
+        }
+    }
+    T* f = static_cast<T*>(const_cast<void*>(L.feat[l])) + (int64_t)b * H * W * L.C + c0 + cl;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        if (!own[k]) continue;
+        skg_roi_vec<DT> r;
+#pragma unroll
+        for (int j = 0; j < VG; ++j) E::st(r.e, j, acc[k][j]);
+        *reinterpret_cast<uint4*>(f + ((int64_t)py[k] * W + px[k]) * L.C) = r.q;
+    }
+}
+
+// deterministic backward launches since the last reset: [B, C, H, W], channels-last (skg_roi_align_det_counts)
+static std::atomic<long long> g_roi_det_counts[2];
+
+extern "C" void skg_roi_align_det_counts(int64_t* out2, int reset) {
+    for (int i = 0; i < 2; ++i) {
+        if (out2) out2[i] = g_roi_det_counts[i].load(std::memory_order_relaxed);
+        if (reset) g_roi_det_counts[i].store(0, std::memory_order_relaxed);
+    }
+}
+
+// both deterministic entries: every check, then one launch
+static int skg_roi_align_bwd_det(bool nhwc, void* const* dfeats_host, int grad_dtype, const int32_t* H_host,
+                                 const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                 float canonical_scale, int canonical_level, const float* boxes, const int32_t* box_image,
+                                 int n_rois, int n_images, int pooled, int sampling, const float* dout, void* stream) {
+    if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
+        return SKG_E_ARG;
+    if (n_images <= 0 || grad_dtype < SKG_DTYPE_F32 || grad_dtype > SKG_DTYPE_BF16) return SKG_E_ARG;
+    if (nhwc && ((C & 7) || pooled > SKG_ROI_NHWC_MAX_POOLED)) return SKG_E_ARG;     // 16-byte channel vectors; the LDS tile
+    if (!dfeats_host || !H_host || !W_host || !scales_host) return SKG_E_ARG;
+    if (n_rois > 0 && (!boxes || !box_image || !dout)) return SKG_E_ARG;             // (no RoI: the maps are still written)
+    if (n_rois > 0 && (!skg_aligned16(boxes) || (nhwc && !skg_aligned16(dout)))) return SKG_E_ALIGN;
+    skg_roi_levels L;
+    const int rc = skg_roi_levels_fill(L, reinterpret_cast<const void* const*>(dfeats_host), H_host, W_host, scales_host,
+                                       n_levels, C, k_min, k_max, canonical_scale, canonical_level);
+    if (rc) return rc;
+    skg_roi_det_grid G;
+    const int tw = nhwc ? SKG_ROI_DET_NT : SKG_ROI_DET_TW, th = nhwc ? SKG_ROI_DET_NT : SKG_ROI_DET_TH;
+    const int slab = nhwc ? SKG_ROI_NHWC_SLAB : SKG_ROI_DET_CS;
+    G.n_slabs = (C + slab - 1) / slab;
+    int64_t blocks = 0;
+    for (int l = 0; l < SKG_ROI_MAX_LEVELS; ++l) {
+        G.start[l] = (unsigned)blocks;
+        G.tiles_x[l] = G.tiles_y[l] = 0;
+        if (l >= n_levels) continue;
+        if (nhwc && !skg_aligned16(L.feat[l])) return SKG_E_ALIGN;
+        G.tiles_x[l] = (L.W[l] + tw - 1) / tw; G.tiles_y[l] = (L.H[l] + th - 1) / th;
+        blocks += (int64_t)G.tiles_x[l] * G.tiles_y[l] * n_images * G.n_slabs;
+        if (blocks > 0x7fffffffLL) return SKG_E_LIMIT;
+    }
+    G.start[SKG_ROI_MAX_LEVELS] = (unsigned)blocks;
+    g_roi_det_counts[nhwc ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+    hipStream_t s = (hipStream_t)stream;
+#define SKG_ROI_DET(K)                                                                                                  \
+    switch (grad_dtype) {                                                                                               \
+        case SKG_DTYPE_F32: hipLaunchKernelGGL((K<SKG_DTYPE_F32>), dim3((unsigned)blocks), dim3(256), 0, s, L, G, boxes, box_image, n_rois, pooled, sampling, dout); break; \
+        case SKG_DTYPE_F16: hipLaunchKernelGGL((K<SKG_DTYPE_F16>), dim3((unsigned)blocks), dim3(256), 0, s, L, G, boxes, box_image, n_rois, pooled, sampling, dout); break; \
+        default: hipLaunchKernelGGL((K<SKG_DTYPE_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, L, G, boxes, box_image, n_rois, pooled, sampling, dout); break;          \
+    }
+    if (nhwc) { SKG_ROI_DET(skg_roi_align_bwd_det_nhwc_kernel) } else { SKG_ROI_DET(skg_roi_align_bwd_det_kernel) }
+#undef SKG_ROI_DET
+    return skg_launch_status();
+}
+
+extern "C" int skg_roi_align_bwd_det_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host, const int32_t* W_host,
+                                       const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                       float canonical_scale, int canonical_level, const float* boxes,
+                                       const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling,
+                                       const float* dout, void* stream) {
+    return skg_roi_align_bwd_det(false, dfeats_host, grad_dtype, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
+                                 canonical_scale, canonical_level, boxes, box_image, n_rois, n_images, pooled, sampling, dout,
+                                 stream);
+}
+
+extern "C" int skg_roi_align_bwd_det_nhwc_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host,
+                                            const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                                            int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                                            const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling,
+                                            const float* dout, void* stream) {
+    return skg_roi_align_bwd_det(true, dfeats_host, grad_dtype, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
+                                 canonical_scale, canonical_level, boxes, box_image, n_rois, n_images, pooled, sampling, dout,
+                                 stream);
+}

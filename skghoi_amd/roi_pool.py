@@ -16,6 +16,10 @@ output being the fp32 result rounded once.  Any other mix of map dtypes is widen
 Channels-last maps (what a backbone run with memory_format=torch.channels_last hands over) are read in place too
 (`skg_roi_align_nhwc_x`, `channels_last_route` below says when), with bit-identical results; their gradients come back
 channels-last (`skg_roi_align_bwd_nhwc_f32`).  Every other layout is made [B, C, H, W]-contiguous first, as before.
+
+`deterministic` (None: follow `torch.use_deterministic_algorithms`) selects the backward without atomics
+(`skg_roi_align_bwd_det_x` / `skg_roi_align_bwd_det_nhwc_x`): a fixed summation order, the same bits on every run and in both
+layouts, gradients written once in the maps' dtype into uninitialised maps (no zero fill, no fp32 temporaries).
 """
 import ctypes as C
 import math
@@ -55,12 +59,21 @@ def channels_last_route(feats) -> bool:
                for f in feats)
 
 
+def resolve_deterministic(flag: Optional[bool]) -> bool:
+    """The `deterministic` keyword of MultiScaleRoIAlign at the time of a forward call: None follows
+    torch.are_deterministic_algorithms_enabled(), True / False override it."""
+    if flag is None:
+        return bool(torch.are_deterministic_algorithms_enabled())
+    return bool(flag)
+
+
 class _RoIAlignFn(torch.autograd.Function):
-    """out = MultiScaleRoIAlign(feats...); backward scatters d out into zeroed feature gradients (float atomics)."""
+    """out = MultiScaleRoIAlign(feats...); backward scatters d out into zeroed feature gradients (float atomics), or, when
+    cfg carries deterministic = True, gathers them in a fixed order into uninitialised maps of the maps' dtype."""
 
     @staticmethod
     def forward(ctx, cfg, rois, img, *feats):
-        scales, k_min, k_max, canon_s, canon_l, pooled, sampling, out_dtype = cfg
+        scales, k_min, k_max, canon_s, canon_l, pooled, sampling, out_dtype = cfg[:8]
         dts = {f.dtype for f in feats}
         nhwc = pooled <= _NHWC_MAX_POOLED and channels_last_route(feats)
         map_code = _HALF_CODES.get(feats[0].dtype) if len(dts) == 1 else None
@@ -93,12 +106,27 @@ class _RoIAlignFn(torch.autograd.Function):
         ctx.shapes = [tuple(f.shape) for f in fs]
         ctx.dtypes = [f.dtype for f in feats]
         ctx.nhwc = nhwc
+        ctx.det = bool(cfg[8]) if len(cfg) > 8 else False
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        scales, k_min, k_max, canon_s, canon_l, pooled, sampling, _ = ctx.cfg
+        scales, k_min, k_max, canon_s, canon_l, pooled, sampling = ctx.cfg[:7]
         dout = dout.float().contiguous()
+        if ctx.det:                                 # every element written once, in a fixed order: uninitialised maps
+            one = len(set(ctx.dtypes)) == 1 and ctx.dtypes[0] in _OUT_CODES
+            gdt = ctx.dtypes[0] if one else torch.float32           # mixed / fp64 maps: fp32 gradients, converted below
+            fmt = torch.channels_last if ctx.nhwc else torch.contiguous_format
+            dfs = [torch.empty(sh, device=dout.device, dtype=gdt, memory_format=fmt) for sh in ctx.shapes]
+            ptrs, Hs, Ws, sc = _level_args(dfs, scales)
+            name = "skg_roi_align_bwd_det_nhwc_x" if ctx.nhwc else "skg_roi_align_bwd_det_x"
+            _capi.check(getattr(_capi.lib(), name)(ptrs, _OUT_CODES[gdt], Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min,
+                                                   k_max, float(canon_s), int(canon_l), ctx.rois.data_ptr(),
+                                                   ctx.img.data_ptr(), ctx.rois.shape[0], ctx.shapes[0][0], pooled,
+                                                   sampling, dout.data_ptr(), _stream()), name)
+            if one:
+                return (None, None, None) + tuple(dfs)
+            return (None, None, None) + tuple(d.to(t) for d, t in zip(dfs, ctx.dtypes))
         if ctx.nhwc:                                # gradients of channels-last maps stay channels-last
             dfs = [torch.empty(sh, device=dout.device, dtype=torch.float32, memory_format=torch.channels_last).zero_()
                    for sh in ctx.shapes]
@@ -119,10 +147,16 @@ class _RoIAlignFn(torch.autograd.Function):
 
 class MultiScaleRoIAlign(nn.Module):
     def __init__(self, featmap_names: List[str], output_size, sampling_ratio: int, *, canonical_scale: int = 224,
-                 canonical_level: int = 4, output_dtype: Optional[torch.dtype] = None):
+                 canonical_level: int = 4, output_dtype: Optional[torch.dtype] = None,
+                 deterministic: Optional[bool] = None):
         """output_dtype: dtype of the pooled features -- None (float32, the default), torch.float32, torch.bfloat16 or
-        torch.float16."""
+        torch.float16.
+        deterministic: the backward -- None (the default) follows torch.are_deterministic_algorithms_enabled() at the
+        time of the forward call, True always takes the order-fixed backward without atomics, False always the atomics."""
         super().__init__()
+        if deterministic is not None and not isinstance(deterministic, bool):
+            raise ValueError("deterministic must be None, True or False (got %r)" % (deterministic,))
+        self.deterministic = deterministic
         if output_dtype is not None and output_dtype not in _OUT_CODES:
             raise ValueError("output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16 (got %r)"
                              % (output_dtype,))
@@ -142,6 +176,9 @@ class MultiScaleRoIAlign(nn.Module):
     def _out_dtype(self):
         dt = getattr(self, "output_dtype", None)            # (modules pickled before the keyword existed: float32)
         return torch.float32 if dt is None else dt
+
+    def _deterministic(self) -> bool:
+        return resolve_deterministic(getattr(self, "deterministic", None))   # (pickled before the keyword: None)
 
     @staticmethod
     def infer_scale(feature_hw, original_hw) -> float:
@@ -174,7 +211,7 @@ class MultiScaleRoIAlign(nn.Module):
         L = len(feats)
         k_min, k_max = (self.k_min, self.k_max) if L > 1 else (0, 0)
         cfg = (list(self.scales), k_min, k_max, self.canonical_scale, self.canonical_level, self.output_size,
-               self.sampling_ratio, self._out_dtype())
+               self.sampling_ratio, self._out_dtype(), self._deterministic())
         if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
             return _RoIAlignFn.apply(cfg, rois, img, *feats)
         return _RoIAlignFn.forward(_NoCtx(), cfg, rois, img, *feats)

@@ -1,11 +1,12 @@
 // Host emulation of skg_roialign.hip: the kernels run on the CPU, one host thread per work-item (hip/hip_runtime.h here is a
 // stand-in for the HIP runtime), so that AddressSanitizer / UBSan see every map, output and LDS-tile access.  Compares the
 // channels-last entries against the [B, C, H, W] entries on the same values: forward outputs byte for byte (nine dtype
-// pairs), fp32 gradients within 2e-5.  Shapes and boxes of tests/test_half_features_gpu.py::_roi_inputs.  No GPU involved.
+// pairs), fp32 gradients within 2e-5; and the two deterministic backward kernels byte for byte against a sequential loop
+// written here (run_det below).  Shapes and boxes of tests/test_half_features_gpu.py::_roi_inputs.  No GPU involved.
 //
 //   cd tools/roialign_host_emu && clang++ -x c++ -std=c++20 -O1 -g -ffp-contract=off -fsanitize=address,undefined -pthread \
 //       -I. -I../../skghoi_amd/csrc -I../../include main.cpp -o emu && ./emu        (a few minutes: 256 threads per workgroup)
-// Exit status 0 and "bad 0" on the last line: everything agreed.
+// Exit status 0 and "bad 0" on the last line: everything agreed.  `./emu det` runs the deterministic backward part alone.
 #include "skg_roialign.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -81,10 +82,113 @@ static int run(int map_dt, int Cc, int L0, int L, int pooled, int sampling) {
     return bad;
 }
 
-int main() {
+
+// ---------------------------------------------------------------------------------------- deterministic backward
+// skg_roi_align_bwd_det_x / skg_roi_align_bwd_det_nhwc_x against a plain sequential loop that applies the contract's order:
+// RoIs ascending, sample rows then sample columns ascending, taps 1..4, fp32 `acc += (wy * wx) * (dout / cnt)` from 0.f (a
+// sequential scatter gives every element its terms in exactly that order), rounded once.  Byte for byte, both layouts, maps
+// prefilled with 0xFF bytes (NaN), three images of which image 1 has no boxes.
+static const float DBOX[12][4] = {{10.f, 15.f, 60.f, 70.f}, {20.f, 20.f, 70.f, 65.f}, {10.f, 15.f, 60.f, 70.f},
+                                  {5.3f, 8.1f, 150.7f, 140.2f}, {0.f, 0.f, 179.f, 119.f}, {-60.f, -50.f, 240.f, 170.f},
+                                  {-300.f, -250.f, 500.f, 400.f}, {50.f, 30.f, 52.f, 31.5f}, {3.f, 3.f, 3.4f, 3.2f},
+                                  {150.f, 90.f, 200.f, 130.f}, {30.f, 40.f, 90.f, 110.f}, {100.f, 60.f, 179.f, 119.f}};
+static const int DIMG[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 2};
+
+static void det_reference(std::vector<std::vector<float>>& g, const int32_t* H, const int32_t* W, const float* sc, int L,
+                          int Cc, int kmin, int kmax, const float* boxes, const int* img, int n_rois, int B, int pooled,
+                          int sampling, const float* dout, std::vector<int>& level_used) {
+    for (int r = 0; r < n_rois; ++r) {
+        const float* b = boxes + 4 * r;
+        if (img[r] < 0 || img[r] >= B) continue;
+        const float s = sqrtf((b[2] - b[0]) * (b[3] - b[1]));
+        float lv = floorf((float)4 + log2f(s / 224.f) + 1e-6f);
+        lv = fminf(fmaxf(lv, (float)kmin), (float)kmax);
+        const int l = (int)lv - kmin;
+        level_used[l]++;
+        const int Hl = H[l], Wl = W[l];
+        const float x1 = b[0] * sc[l], y1 = b[1] * sc[l], x2 = b[2] * sc[l], y2 = b[3] * sc[l];
+        const float rw = fmaxf(x2 - x1, 1.f), rh = fmaxf(y2 - y1, 1.f);
+        const float bw = rw / (float)pooled, bh = rh / (float)pooled;
+        const int gh = sampling > 0 ? sampling : (int)ceilf(rh / pooled);
+        const int gw = sampling > 0 ? sampling : (int)ceilf(rw / pooled);
+        const float cnt = fmaxf((float)(gh * gw), 1.f);
+        for (int c = 0; c < Cc; ++c) {
+            float* f = g[l].data() + ((size_t)img[r] * Cc + c) * Hl * Wl;
+            for (int sy = 0; sy < pooled * gh; ++sy) for (int sx = 0; sx < pooled * gw; ++sx) {
+                const int ph = sy / gh, iy = sy % gh, pw = sx / gw, ix = sx % gw;
+                float y = y1 + ph * bh + (iy + 0.5f) * bh / (float)gh;
+                float x = x1 + pw * bw + (ix + 0.5f) * bw / (float)gw;
+                if (y < -1.0f || y > (float)Hl || x < -1.0f || x > (float)Wl) continue;
+                if (y <= 0.f) y = 0.f;
+                if (x <= 0.f) x = 0.f;
+                int yl = (int)y, xl = (int)x, yh, xh;
+                if (yl >= Hl - 1) { yh = yl = Hl - 1; y = (float)yl; } else yh = yl + 1;
+                if (xl >= Wl - 1) { xh = xl = Wl - 1; x = (float)xl; } else xh = xl + 1;
+                const float ly = y - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
+                const float gr = dout[(((size_t)r * Cc + c) * pooled + ph) * pooled + pw] / cnt;
+                f[yl * Wl + xl] += (hy * hx) * gr;
+                f[yl * Wl + xh] += (hy * lx) * gr;
+                f[yh * Wl + xl] += (ly * hx) * gr;
+                f[yh * Wl + xh] += (ly * lx) * gr;
+            }
+        }
+    }
+}
+
+template <class T> static T conv_nan(float v) { return conv<T>(v); }
+template <> uint16_t conv_nan<uint16_t>(float v) { return v != v ? (uint16_t)0x7FC0 : to_bf16(v); }
+
+template <class T>
+static int run_det(int dt, int Cc, int L0, int L, int pooled, int sampling, int n_rois, int far_image) {
+    const int B = 3;
+    std::mt19937 rng(Cc * 11 + dt);
+    std::normal_distribution<float> nd;
+    int32_t H[8], W[8]; float sc[8];
+    std::vector<T*> g_nchw(L), g_nhwc(L);
+    std::vector<std::vector<float>> ref(L);
+    for (int l = 0; l < L; ++l) {
+        const int s = 4 << (l + L0);
+        H[l] = 120 / s; W[l] = 180 / s; sc[l] = 1.f / s;
+        const size_t n = (size_t)B * Cc * H[l] * W[l];
+        g_nchw[l] = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16); g_nhwc[l] = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16);
+        memset(g_nchw[l], 0xFF, n * sizeof(T)); memset(g_nhwc[l], 0xFF, n * sizeof(T));
+        ref[l].assign(n, 0.f);
+    }
+    float* boxes = (float*)aligned_alloc(16, 12 * 16); memcpy(boxes, DBOX, 12 * 16);
+    int32_t* img = (int32_t*)aligned_alloc(16, 48); memcpy(img, DIMG, 48);
+    if (far_image) img[n_rois - 1] = 7;                                // a RoI of an image that does not exist
+    const int kmin = L > 1 ? 2 + L0 : 0, kmax = L > 1 ? kmin + L - 1 : 0;
+    const size_t no = (size_t)12 * Cc * pooled * pooled;
+    float* dout = (float*)aligned_alloc(16, (no * 4 + 15) / 16 * 16);
+    for (size_t i = 0; i < no; ++i) dout[i] = nd(rng);
+    std::vector<int> used(L, 0);
+    det_reference(ref, H, W, sc, L, Cc, kmin, kmax, boxes, img, n_rois, B, pooled, sampling, dout, used);
+    const int r1 = skg_roi_align_bwd_det_x((void* const*)g_nchw.data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, n_rois, B, pooled, sampling, dout, nullptr);
+    const int r2 = skg_roi_align_bwd_det_nhwc_x((void* const*)g_nhwc.data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, n_rois, B, pooled, sampling, dout, nullptr);
+    size_t d1 = 0, d2 = 0, nonzero = 0, img1 = 0;
+    for (int l = 0; l < L; ++l)
+        for (int b = 0; b < B; ++b) for (int c = 0; c < Cc; ++c) for (int y = 0; y < H[l]; ++y) for (int x = 0; x < W[l]; ++x) {
+            const float rv = ref[l][(((size_t)b * Cc + c) * H[l] + y) * W[l] + x];
+            const T want = conv_nan<T>(rv);
+            d1 += memcmp(&want, &g_nchw[l][(((size_t)b * Cc + c) * H[l] + y) * W[l] + x], sizeof(T)) != 0;
+            d2 += memcmp(&want, &g_nhwc[l][(((size_t)b * H[l] + y) * W[l] + x) * Cc + c], sizeof(T)) != 0;
+            nonzero += rv != 0.f; img1 += b == 1 && rv != 0.f;
+        }
+    int levels = 0;
+    for (int l = 0; l < L; ++l) levels += used[l] > 0;
+    printf("  det dt %d C %d L %d pooled %d samp %d rois %d far %d: rc %d %d, differing elements %zu %zu, nonzero %zu, levels used %d\n",
+           dt, Cc, L, pooled, sampling, n_rois, far_image, r1, r2, d1, d2, nonzero, levels);
+    const bool covered = n_rois == 0 ? nonzero == 0 : (nonzero > 0 && levels == L);
+    for (int l = 0; l < L; ++l) { free(g_nchw[l]); free(g_nhwc[l]); }
+    free(boxes); free(img); free(dout);
+    return (r1 || r2 || d1 || d2 || img1 || !covered) ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
     int bad = 0;
     const int Cs[3] = {8, 24, 72};
-    for (int ci = 0; ci < 3; ++ci) {
+    const bool det_only = argc > 1 && !strcmp(argv[1], "det");       // ./emu det: the deterministic backward alone
+    for (int ci = 0; ci < 3 && !det_only; ++ci) {
         const int Cc = Cs[ci];
         const int cfg[4][4] = {{0, 4, 7, 2}, {3, 1, 7, 2}, {0, 4, 7, 0}, {0, 4, 2, 2}};
         for (int k = 0; k < 4; ++k) {
@@ -95,7 +199,21 @@ int main() {
             bad += run<uint16_t>(2, Cc, cfg[k][0], cfg[k][1], cfg[k][2], cfg[k][3]);
         }
     }
+    for (int ci = 0; ci < 3; ++ci) {
+        const int Cc = Cs[ci];
+        const int cfg[4][4] = {{0, 4, 7, 2}, {3, 1, 7, 2}, {0, 4, 7, 0}, {0, 4, 2, 2}};
+        for (int k = 0; k < 4; ++k) {
+            printf("det C %d cfg %d\n", Cc, k);
+            bad += run_det<float>(0, Cc, cfg[k][0], cfg[k][1], cfg[k][2], cfg[k][3], 12, 0);
+            bad += run_det<_Float16>(1, Cc, cfg[k][0], cfg[k][1], cfg[k][2], cfg[k][3], 12, 0);
+            bad += run_det<uint16_t>(2, Cc, cfg[k][0], cfg[k][1], cfg[k][2], cfg[k][3], 12, 0);
+        }
+    }
+    bad += run_det<uint16_t>(2, 8, 0, 4, 7, 2, 0, 0);                  // no RoI: zeros everywhere
+    bad += run_det<float>(0, 8, 0, 4, 7, 2, 12, 1);                    // the last RoI names image 7 of 3
     int64_t cnt[4]; skg_roi_align_layout_counts(cnt, 1);
-    printf("counts %lld %lld %lld %lld, bad %d\n", (long long)cnt[0], (long long)cnt[1], (long long)cnt[2], (long long)cnt[3], bad);
+    int64_t dc[2]; skg_roi_align_det_counts(dc, 1);
+    printf("counts %lld %lld %lld %lld, det %lld %lld, bad %d\n", (long long)cnt[0], (long long)cnt[1], (long long)cnt[2], (long long)cnt[3],
+           (long long)dc[0], (long long)dc[1], bad);
     return bad != 0;
 }

@@ -577,13 +577,18 @@ int skg_layernorm_bwd_f32(const float* dy, int64_t lddy, const float* x, const f
                           int rows, float* dx, const float* relu_src, float* dx_masked, float* dgamma, float* dbeta,
                           void* stream);
 /* Backward of t = relu(m * f), m = P[p_idx] + Q[q_idx] + mbias, f = F[f_idx] (MBF fc_1 * fc_2, HEAD:469-474): g = dt
- * (zero where t <= 0) is overwritten with dm = g * f;  dF[f_idx] = (or +=, accumulate) g * m.                          */
+ * (zero where t <= 0) is overwritten with dm = g * f;  dF[f_idx] = (or +=, accumulate) g * m.  f_idx (NULL: row r itself)
+ * must be INJECTIVE: one workgroup per row r reads, adds to and writes dF row f_idx[r] without atomics, so two rows that
+ * map to one dF row race.  Rows of dF that no f_idx points at (the self pairs' grid rows) keep the caller's value.       */
 int skg_mul_bwd_f32(float* g, int64_t ldg, const float* F, const int32_t* f_idx, int64_t ldf, const float* P,
                     const int32_t* p_idx, int64_t ldp, const float* Q, const int32_t* q_idx, int64_t ldq,
                     const float* mbias, int rows, float* dF, int64_t lddf, int accumulate, void* stream);
 /* Row sums per human / node / image (gradients of the gathered fc_1 tables).  mode 0: src = grid rows; mode 1: src =
- * kept pairs; mode 2: src = kept pairs, outH[meta[a].image] = sum over the pairs of active image a (rows of images
- * without pairs are not written).  outH [sumH | batch, 1024], outN [sumN, 1024]; either may be NULL.                   */
+ * kept pairs; modes 0 and 1 write EVERY human / node row (a node no kept pair points at gets the empty sum, 0).  mode 2:
+ * src = kept pairs, outH[meta[a].image] = sum over the pairs of active image a -- outH has one row per image of the BATCH
+ * and only the rows of the n_active images listed in meta are written; the rows of the batch's other (skipped) images
+ * keep the caller's value, with or without accumulate.  outH [sumH | batch, 1024], outN [sumN, 1024]; either may be NULL
+ * (mode 2: outH only).                                                                                                   */
 int skg_segment_sum_f32(const float* src, int64_t ld, const skg_image_meta* meta, int n_active, const int32_t* hum_img,
                         const int32_t* node_img, int sum_h, int sum_n, int mode, float* outH, float* outN,
                         int accumulate, void* stream);

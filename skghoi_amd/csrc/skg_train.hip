@@ -247,6 +247,7 @@ extern "C" int skg_layernorm_bwd_f32(const float* dy, int64_t lddy, const float*
 // ------------------------------------------------------------------------------------------------ fc_1 * fc_2 backward
 // Forward (MBF / MessageMBF, HEAD:469-474, 509-527):  t = relu(m * f),  m = P[pi] + Q[qi] + mbias,  f = F[fi].
 // Given g = dt (already zeroed where t <= 0):   dF[fi] (+)= g * m,   dm = g * f  (written over g, in place).
+// f_idx must be injective: row r owns dF row f_idx[r] (read, add, write without atomics); two rows on one dF row race.
 __global__ __launch_bounds__(256) void skg_mul_bwd_kernel(float* __restrict__ g, int64_t ldg,
                                                           const float* __restrict__ F, const int32_t* __restrict__ f_idx,
                                                           int64_t ldf, const float* __restrict__ P,
@@ -347,7 +348,8 @@ extern "C" int skg_mul_bwd_f32(float* g, int64_t ldg, const float* F, const int3
 //   mode 0  src = grid rows (r = grid_off + i * n + j):   outH[(a, i)] = sum_j src[r],   outN[(a, j)] = sum_i src[r]
 //   mode 1  src = kept pairs (p = pair_off + i * (n - 1) + jj):  outH[(a, i)] = sum_jj src[p];
 //                                                          outN[(a, j)] = sum_{i != j} src[pair of (i, j)]
-//   mode 2  src = kept pairs:  outH[meta[a].image] = sum of all pairs of active image a   (outN unused)
+//   mode 2  src = kept pairs:  outH[meta[a].image] = sum of all pairs of active image a   (outN unused); outH rows of
+//           the batch's images that are not in meta (skipped: no human, or a single box) keep the caller's value
 // One workgroup per destination row, rows added in index order.
 __device__ __forceinline__ void skg_segment_sum_body(const float* __restrict__ src, int64_t ld,
                                                      const skg_image_meta* __restrict__ meta,

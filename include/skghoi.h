@@ -711,6 +711,61 @@ int skg_adamw_f32(const skg_adamw_chunk* chunks, int n_chunks, double lr, double
                   double weight_decay, double bias1, double bias2, float* steps, int n_steps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The guarded optimizer step: global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm type 2) and the skip
+ * of a step whose gradients are not finite, decided ON THE DEVICE -- nothing returns to the host, the step keeps its
+ * launch sequence.  Two launches per parameter group:
+ *
+ * skg_grad_sumsq_f32: the sum of the squares of every gradient element a chunk table names (its `g` and `count`; `p`,
+ * `m`, `v` are not read).  A fixed grid of SKG_GRADNORM_PARTIALS workgroups of 256 lanes; workgroup b takes chunks b,
+ * b + SKG_GRADNORM_PARTIALS, ...; inside a chunk whose `g` is 16-byte aligned lane l takes the 16-byte vectors l,
+ * l + 256, ... (elements x, y, z, w in this order) and then the elements 4 * (count / 4) + l, ... of the tail, otherwise
+ * the elements l, l + 256, ...  Every lane adds its squares to ONE double in that order (an fp32 square is exact in
+ * double), the 64 lanes of a wave meet in a butterfly (partners 32, 16, 8, 4, 2, 1 lanes apart), the four waves as
+ * (w0 + w1) + (w2 + w3), and partials[b] (device, 8-byte aligned, all SKG_GRADNORM_PARTIALS written: no zero fill, no
+ * atomics) receives the workgroup's sum: the same table gives the same bits in every run.  A NaN or an infinity anywhere
+ * makes its partial non-finite; finite fp32 gradients cannot overflow a double.  HBM-bound: 4 bytes per gradient element.
+ * n_chunks == 0 launches nothing (the partials keep what they held).
+ *
+ * skg_adamw_guarded_f32: skg_adamw_f32 with the gradient read as g * coef.  Every workgroup adds the n_partials doubles
+ * (the partials of ALL parameter groups, one contiguous array: the norm is global) in one fixed order -- lane l the
+ * entries l, l + 256, ..., then the butterfly and the wave order above -- so that every workgroup of every group's launch
+ * derives the same bits:  total_norm = sqrt(sum) (double);  coef = min(1, max_norm / (total_norm + 1e-6)) rounded to
+ * float once (torch's formula; a NaN stays a NaN; max_norm = +infinity: no clipping, coef = 1 exactly);
+ * finite = isfinite(sum).  With finite || !skip_nonfinite the step is APPLIED: per element one fp32 multiply g * coef,
+ * then the rule of skg_adamw_f32 (the same bits as scaling the gradient in memory first; the gradient itself is NOT
+ * modified), `steps` bumped.  Otherwise the step is SKIPPED: nothing is written to p, m, v or steps.
+ * The bias corrections follow the APPLIED count although the host cannot know of a skip: t_host (>= 1) is the host's
+ * step number, bias1 / bias2 are formed from it as for skg_adamw_f32, and status->pending_skips counts the skipped steps
+ * t_host does not know of.  While that count is zero the host's factors are used (bit-identical to skg_adamw_f32);
+ * otherwise 1 - beta^(t_host - pending) is recomputed in double on the device.  The count is double-buffered: a launch
+ * READS slot t_host & 1 (all workgroups) and WRITES the other (workgroup 0), so consecutive launches on one stream must
+ * pass consecutive t_host; a host that has read the record lowers its step number by the pending count and zeroes both
+ * slots.  Workgroup 0 also writes the rest of the record: the step's norm, factor and outcome, and the running counters
+ * (cleared by the host by zeroing them).  One record per parameter group (each launch keeps its own).
+ * Errors, before any launch: SKG_E_ARG for a null chunks / steps (with a count > 0) / partials / status, a negative
+ * count, n_partials < 1, t_host < 1, bias1 / bias2 <= 0, eps < 0, max_norm <= 0 or NaN; SKG_E_ALIGN for partials or
+ * status not 8-byte aligned.  n_chunks == 0 returns 0 (nothing launched, the record untouched).                      */
+#define SKG_GRADNORM_PARTIALS 1024
+typedef struct {
+    float   total_norm;        /* the last step's gradient norm (double, rounded once)                                  */
+    float   coef;              /* ... and the factor its gradients were read with                                      */
+    int32_t applied;           /* ... 1 = the update was applied, 0 = skipped                                          */
+    int32_t reserved;
+    int64_t steps_applied;     /* running counters since the record was last zeroed                                    */
+    int64_t steps_skipped;
+    int64_t steps_clipped;     /* applied steps with coef < 1                                                          */
+    float   max_total_norm;    /* largest FINITE total_norm seen                                                       */
+    int32_t reserved2;
+    int64_t pending_skips[2];  /* skipped steps the host's t_host does not know of (double-buffered, see above)        */
+} skg_step_status;
+int skg_grad_sumsq_f32(const skg_adamw_chunk* chunks, int n_chunks, double* partials, void* stream);
+int skg_adamw_guarded_f32(const skg_adamw_chunk* chunks, int n_chunks, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, double bias1, double bias2, int64_t t_host, double max_norm,
+                          int skip_nonfinite, const double* partials, int n_partials, float* steps, int n_steps,
+                          skg_step_status* status, void* stream);
+int skg_sizeof_step_status(void);                                   /* sizeof(skg_step_status): for bindings that mirror it */
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Native launch plan of the fused TRAINING step's dense part: GraphHead.forward in training mode (HEAD:769-993; the
  * classifier HEAD:410-411) and its backward -- what the reference leaves to eager PyTorch + autograd inside
  * `net(...)` / `loss.backward()` (utils.py:213-229) -- as ONE host call per phase.  The call enqueues the whole launch

@@ -78,6 +78,16 @@ class Exchange(C.Structure):
                                                                           "bias1", "bias2")]
 
 
+GRADNORM_PARTIALS = 1024
+
+
+class StepStatus(C.Structure):
+    """Mirror of skg_step_status: what skg_adamw_guarded_f32 leaves behind (last step, running counters)."""
+    _fields_ = [("total_norm", _f32), ("coef", _f32), ("applied", _i32), ("reserved", _i32),
+                ("steps_applied", _i64), ("steps_skipped", _i64), ("steps_clipped", _i64),
+                ("max_total_norm", _f32), ("reserved2", _i32), ("pending_skips", _i64 * 2)]
+
+
 class Tuning(C.Structure):
     """Mirror of skg_tuning: the eval GEMM's developer switches, kept in a context (0 = the library's default)."""
     _fields_ = [(n, _i32) for n in ("small_mode", "small_tiles", "route_tiles", "khalves_blocks")]
@@ -158,6 +168,10 @@ PROTOTYPES = {
     "skg_gemm_b16_x_counts": (None, [C.POINTER(_i64), C.c_int]),
     "skg_row_exponents_f32": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, _vp]),
     "skg_adamw_f32": (C.c_int, [_vp, C.c_int] + [C.c_double] * 7 + [_vp, C.c_int, _vp]),
+    "skg_grad_sumsq_f32": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "skg_adamw_guarded_f32": (C.c_int, [_vp, C.c_int] + [C.c_double] * 7 + [_i64, C.c_double, C.c_int, _vp, C.c_int, _vp,
+                                                                          C.c_int, _vp, _vp]),
+    "skg_sizeof_step_status": (C.c_int, []),
     "skg_ctx_set_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),
     "skg_ctx_get_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),
     "skg_ctx_make_current": (_vp, [_vp]),
@@ -272,6 +286,8 @@ def lib():
         fn.argtypes = args
     if l.skg_abi_version() == ABI_VERSION and l.skg_sizeof_exchange() != C.sizeof(Exchange):
         raise SkgError("skg_exchange is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_exchange(), C.sizeof(Exchange)))
+    if l.skg_abi_version() == ABI_VERSION and l.skg_sizeof_step_status() != C.sizeof(StepStatus):
+        raise SkgError("skg_step_status is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_step_status(), C.sizeof(StepStatus)))
     if l.skg_abi_version() != ABI_VERSION:
         raise SkgError("libskghoi_hip.so ABI %d != binding ABI %d" % (l.skg_abi_version(), ABI_VERSION))
     _LIB = l

@@ -8,6 +8,8 @@
 //                        so a stale packed copy would be a silent parity bug.  HBM-bound: 118 MB read once
 //                        (the bytes of the parameters), one 16-byte load per lane and step.
 //   skg_adamw          : AdamW over every parameter of the training step in one launch (chunk table).
+//   skg_grad_sumsq / skg_adamw_guarded : the same step with global-norm clipping and a skip of non-finite gradients,
+//                        both decided on the device (a deterministic sum-of-squares pass, then AdamW reading g * coef).
 #include "skg_common.h"
 
 #define CK_THREADS 256
@@ -124,6 +126,162 @@ int skg_adamw_slice(const skg_adamw_chunk* chunks, int first, int last, const sk
                        with_steps ? x.adamw_steps : (float*)nullptr, with_steps ? x.adamw_n_steps : 0);
     return skg_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------ guarded AdamW
+// Global-norm clipping and the non-finite skip, decided on the device (include/skghoi.h): a sum-of-squares pass over the
+// gradients of the chunk table, then the AdamW launch that reads the partial sums itself.
+__device__ __forceinline__ double skg_wave_sum_f64(double v) {
+    // butterfly: both partners add the same two numbers, so all 64 lanes end with the same bits
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// the workgroup's sum in every lane: (w0 + w1) + (w2 + w3)
+__device__ __forceinline__ double skg_block_sum_f64(double v, double* sred) {
+    v = skg_wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sred[0] + sred[1]) + (sred[2] + sred[3]);
+}
+
+// Grid-stride over the chunk table like skg_param_checksum_kernel: a fixed grid, one double per workgroup, no atomics and
+// no zero fill -- the order of the additions is a function of the table alone.  Double from the first element on (the
+// square of an fp32 number is exact in double: the fused multiply-add below rounds exactly like a multiply and an add).
+__global__ __launch_bounds__(256) void skg_grad_sumsq_kernel(const skg_adamw_chunk* __restrict__ chunks, int n_chunks,
+                                                             double* __restrict__ partials) {
+    __shared__ double sred[4];
+    double acc = 0.0;
+    for (int ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
+        const float* __restrict__ g = chunks[ci].g;
+        const uint32_t n = chunks[ci].count;
+        uint32_t done = 0;
+        if (skg_aligned16_dev(g)) {
+            const uint32_t n4 = n >> 2;
+            const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+#pragma unroll 4
+            for (uint32_t i = threadIdx.x; i < n4; i += 256) {
+                const float4 x = g4[i];
+                acc = fma((double)x.x, (double)x.x, acc);
+                acc = fma((double)x.y, (double)x.y, acc);
+                acc = fma((double)x.z, (double)x.z, acc);
+                acc = fma((double)x.w, (double)x.w, acc);
+            }
+            done = 4u * n4;
+        }
+        for (uint32_t i = done + threadIdx.x; i < n; i += 256) {
+            const double x = (double)g[i];
+            acc = fma(x, x, acc);
+        }
+    }
+    const double total = skg_block_sum_f64(acc, sred);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+extern "C" int skg_grad_sumsq_f32(const skg_adamw_chunk* chunks, int n_chunks, double* partials, void* stream) {
+    if (n_chunks < 0 || (n_chunks > 0 && !chunks) || !partials) return SKG_E_ARG;
+    if ((((uintptr_t)partials) & 7u) != 0) return SKG_E_ALIGN;
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(skg_grad_sumsq_kernel, dim3(SKG_GRADNORM_PARTIALS), dim3(256), 0, (hipStream_t)stream, chunks,
+                       n_chunks, partials);
+    return skg_launch_status();
+}
+
+struct skg_guard_factors {
+    float decay, c1, beta2, c2, step_size, inv_sqrt_b2, eps;     // as skg_adamw_kernel's, from the host's step number
+    int skip_nonfinite;
+    double lr, beta1d, beta2d, max_norm;                        // ... and what recomputing them for another step number takes
+    int64_t t_host;
+};
+
+__global__ __launch_bounds__(256) void skg_adamw_guarded_kernel(const skg_adamw_chunk* __restrict__ chunks,
+                                                                const skg_guard_factors f,
+                                                                const double* __restrict__ partials, int n_partials,
+                                                                float* __restrict__ steps, int n_steps,
+                                                                skg_step_status* status) {
+    __shared__ double sred[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
+    const double sum = skg_block_sum_f64(acc, sred);              // the same bits in every workgroup of every group's launch
+    const bool finite = sum - sum == 0.0;                         // (false for NaN and for an infinity)
+    const double total_norm = sqrt(sum);
+    double coefd = 1.0;
+    if (f.max_norm < HUGE_VAL) {                                  // torch: clamp(max_norm / (total_norm + 1e-6), max = 1); NaN stays
+        coefd = f.max_norm / (total_norm + 1e-6);
+        if (coefd > 1.0) coefd = 1.0;
+    }
+    const float coef = (float)coefd;
+    const bool apply = finite || !f.skip_nonfinite;
+    // the slot no launch with this t_host writes (workgroup 0 writes the other one)
+    const int slot = (int)(f.t_host & 1);
+    const int64_t pending = status->pending_skips[slot];
+    if (blockIdx.x == 0) {
+        if (apply)
+            for (int i = threadIdx.x; i < n_steps; i += 256) steps[i] += 1.f;
+        if (threadIdx.x == 0) {
+            const float tn = (float)total_norm;
+            status->total_norm = tn;
+            status->coef = coef;
+            status->applied = apply ? 1 : 0;
+            if (apply) status->steps_applied += 1; else status->steps_skipped += 1;
+            if (apply && coef < 1.f) status->steps_clipped += 1;
+            if (tn - tn == 0.f && tn > status->max_total_norm) status->max_total_norm = tn;    // (finite as a float, too)
+            status->pending_skips[slot ^ 1] = pending + (apply ? 0 : 1);
+        }
+    }
+    if (!apply) return;
+    float step_size = f.step_size, inv_sqrt_b2 = f.inv_sqrt_b2;
+    if (pending != 0) {                                           // steps were skipped behind the host's back: the applied count
+        const double t = (double)(f.t_host - pending);
+        step_size = (float)(f.lr / (1.0 - pow(f.beta1d, t)));
+        inv_sqrt_b2 = (float)(1.0 / sqrt(1.0 - pow(f.beta2d, t)));
+    }
+    const skg_adamw_chunk c = chunks[blockIdx.x];
+    const uint32_t n = c.count;
+    const bool vec = ((((uintptr_t)c.p) | ((uintptr_t)c.g) | ((uintptr_t)c.m) | ((uintptr_t)c.v)) & 15u) == 0;
+    uint32_t done = 0;
+    if (vec) {
+        const uint32_t n4 = n >> 2;
+        float4* p4 = reinterpret_cast<float4*>(c.p); const float4* g4 = reinterpret_cast<const float4*>(c.g);
+        float4* m4 = reinterpret_cast<float4*>(c.m); float4* v4 = reinterpret_cast<float4*>(c.v);
+        for (uint32_t i = threadIdx.x; i < n4; i += 256) {
+            float4 p = p4[i], m = m4[i], v = v4[i];
+            const float4 g = g4[i];
+            skg_adamw_one(p.x, g.x * coef, m.x, v.x, f.decay, f.c1, f.beta2, f.c2, step_size, inv_sqrt_b2, f.eps);
+            skg_adamw_one(p.y, g.y * coef, m.y, v.y, f.decay, f.c1, f.beta2, f.c2, step_size, inv_sqrt_b2, f.eps);
+            skg_adamw_one(p.z, g.z * coef, m.z, v.z, f.decay, f.c1, f.beta2, f.c2, step_size, inv_sqrt_b2, f.eps);
+            skg_adamw_one(p.w, g.w * coef, m.w, v.w, f.decay, f.c1, f.beta2, f.c2, step_size, inv_sqrt_b2, f.eps);
+            p4[i] = p; m4[i] = m; v4[i] = v;
+        }
+        done = 4u * n4;
+    }
+    for (uint32_t i = done + threadIdx.x; i < n; i += 256) {
+        float p = c.p[i], m = c.m[i], v = c.v[i];
+        skg_adamw_one(p, c.g[i] * coef, m, v, f.decay, f.c1, f.beta2, f.c2, step_size, inv_sqrt_b2, f.eps);
+        c.p[i] = p; c.m[i] = m; c.v[i] = v;
+    }
+}
+
+extern "C" int skg_adamw_guarded_f32(const skg_adamw_chunk* chunks, int n_chunks, double lr, double beta1, double beta2,
+                                     double eps, double weight_decay, double bias1, double bias2, int64_t t_host,
+                                     double max_norm, int skip_nonfinite, const double* partials, int n_partials,
+                                     float* steps, int n_steps, skg_step_status* status, void* stream) {
+    if (n_chunks < 0 || (n_chunks > 0 && !chunks) || n_steps < 0 || (n_steps > 0 && !steps)) return SKG_E_ARG;
+    if (!(bias1 > 0.0) || !(bias2 > 0.0) || !(eps >= 0.0) || t_host < 1 || !(max_norm > 0.0)) return SKG_E_ARG;
+    if (!partials || n_partials < 1 || !status) return SKG_E_ARG;
+    if (((((uintptr_t)partials) | ((uintptr_t)status)) & 7u) != 0) return SKG_E_ALIGN;
+    if (n_chunks == 0) return 0;
+    skg_guard_factors f;
+    f.decay = (float)(1.0 - lr * weight_decay); f.c1 = (float)(1.0 - beta1); f.beta2 = (float)beta2;
+    f.c2 = (float)(1.0 - beta2); f.step_size = (float)(lr / bias1); f.inv_sqrt_b2 = (float)(1.0 / sqrt(bias2));
+    f.eps = (float)eps; f.skip_nonfinite = skip_nonfinite ? 1 : 0;
+    f.lr = lr; f.beta1d = beta1; f.beta2d = beta2; f.max_norm = max_norm; f.t_host = t_host;
+    hipLaunchKernelGGL(skg_adamw_guarded_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, f,
+                       partials, n_partials, steps, n_steps, status);
+    return skg_launch_status();
+}
+
+extern "C" int skg_sizeof_step_status(void) { return (int)sizeof(skg_step_status); }
 
 // ------------------------------------------------------------------------------------------------ bf16 twins
 thread_local skg_twin_map skg_tls_twin = {{nullptr, nullptr}, {nullptr, nullptr}, {0, 0}};

@@ -29,9 +29,14 @@ def limit_host_threads(ranks_on_host: int = 1, cap: int = 4) -> int:
     return n
 
 
-def build_optimizer(net: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-4, head_key: str = "interaction_head"):
+def build_optimizer(net: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-4, head_key: str = "interaction_head",
+                    max_grad_norm=None, skip_nonfinite: bool = False):
     """main:109-127: parameters whose name contains `head_key` train at lr, the rest at lr * 0.1.  A bare
-    InteractionHead (no wrapper, so no 'interaction_head' in its names) is treated as all-head."""
+    InteractionHead (no wrapper, so no 'interaction_head' in its names) is treated as all-head.
+
+    max_grad_norm / skip_nonfinite: global-norm gradient clipping and the skip of a step with non-finite gradients, both
+    decided on the device inside the optimizer's launches (SkgAdamW; the reference's sibling engine clips with
+    clip_grad_norm_, hicodet/detections/main_detr.py:320).  Parameters on the GPU only: there is no host version."""
     named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
     head = [p for n, p in named if head_key in n]
     rest = [p for n, p in named if head_key not in n]
@@ -44,7 +49,13 @@ def build_optimizer(net: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-4
     # parameter group walk (6 ms of host time for the head's 408 tensors)
     on_gpu = bool(named) and all(p.is_cuda for _, p in named)
     if on_gpu:
-        return SkgAdamW(groups, lr=lr, weight_decay=weight_decay, fused=True)
+        if max_grad_norm is None and not skip_nonfinite:
+            return SkgAdamW(groups, lr=lr, weight_decay=weight_decay, fused=True)
+        return SkgAdamW(groups, lr=lr, weight_decay=weight_decay, fused=True, max_grad_norm=max_grad_norm,
+                        skip_nonfinite=skip_nonfinite)
+    if max_grad_norm is not None or skip_nonfinite:
+        raise ValueError("max_grad_norm / skip_nonfinite need every trained parameter on the GPU (the guard runs inside "
+                         "SkgAdamW's launches)")
     return torch.optim.AdamW(groups, lr=lr, weight_decay=weight_decay)
 
 
@@ -517,7 +528,7 @@ def _plain_step(optimizer):
     hits, two more events on their queue) than the 0.07 ms it takes off the tail: bf16 1.27 -> 1.33 ms, fp32 2.48 -> 2.51,
     data-parallel route at world size 1 1.35 -> 1.38.  Results are bit-identical either way (tests/test_trainer.py)."""
     from torch.optim import optimizer as _topt
-    return isinstance(optimizer, SkgAdamW) and not optimizer._optimizer_step_pre_hooks and \
+    return isinstance(optimizer, SkgAdamW) and not optimizer.guarded and not optimizer._optimizer_step_pre_hooks and \
         not optimizer._optimizer_step_post_hooks and not _topt._global_optimizer_pre_hooks and \
         not _topt._global_optimizer_post_hooks and _os.environ.get("SKG_ADAMW_IN_BACKWARD", "0") == "1"
 
@@ -740,12 +751,13 @@ def train_step(net, optimizer, *inputs, targets, lazy=False, prefetch=None, pref
     return {k: float(v.detach()) for k, v in loss_dict.items()}, out
 
 
-def read_losses(loss_dict: dict) -> dict:
-    """Floats of a lazy loss dict in ONE device-to-host copy, with the reference's NaN guard (utils.py:219)."""
+def read_losses(loss_dict: dict, check: bool = True) -> dict:
+    """Floats of a lazy loss dict in ONE device-to-host copy, with the reference's NaN guard (utils.py:219; check=False:
+    without it -- Trainer(on_nonfinite="skip"), whose optimizer has left such a step out)."""
     keys = list(loss_dict)
     vals = torch.stack([torch.as_tensor(loss_dict[k]).reshape(()).float() for k in keys]).tolist()
     out = dict(zip(keys, vals))
-    if "hoi_loss" in out and out["hoi_loss"] != out["hoi_loss"]:
+    if check and "hoi_loss" in out and out["hoi_loss"] != out["hoi_loss"]:
         raise ValueError(f"The HOI loss is NaN")
     return out
 
@@ -759,14 +771,138 @@ class SkgAdamW(CachedFusedAdamW):
     elements) is rebuilt and uploaded through pinned memory only when the gradients' addresses changed (the fused step hands
     out the same gradient arena from step to step); the state's `step` tensors are views of one flat buffer the launch bumps
     itself.  Anything outside the fast path (first step, a missing or non-contiguous gradient, parameters with
-    different step counts, amsgrad, ...) takes the stock implementation."""
+    different step counts, amsgrad, ...) takes the stock implementation.
+
+    max_grad_norm / skip_nonfinite (both off by default: then step() issues exactly the one `skg_adamw_f32` per group and
+    allocates nothing else) turn on the GUARDED step: per group one `skg_grad_sumsq_f32` -- a deterministic double-precision
+    sum of squares over the group's gradients, one extra read of them -- and then one `skg_adamw_guarded_f32`, which forms
+    the global norm over all groups from the partial sums, reads every gradient as `g * coef` with torch's
+    `coef = min(1, max_grad_norm / (norm + 1e-6))` (clip_grad_norm_), and with skip_nonfinite writes NOTHING -- no
+    parameter, no moment, no step counter -- when the sum of squares is not finite.  The decision is made on the device:
+    no value returns to the host and the step keeps its launch sequence.  `p.grad` is NOT scaled in memory (torch's
+    clip_grad_norm_ does scale it; the update is bit-identical to scaling first).  A skipped step does not advance the
+    bias corrections: the state's `step` counts APPLIED updates, as torch's fused AdamW does under `found_inf`.
+    `grad_stats()` reads the record the launches keep (last norm and factor, applied / skipped / clipped counts, largest
+    finite norm) in one device-to-host copy; `reset_grad_stats()` clears the counters.  Off the fast path (first step, a
+    missing gradient, differing step counts) the same semantics are applied from the host with clip_grad_norm_ and a
+    finiteness test -- that route synchronises and, like torch, DOES scale `p.grad` in place.  The optimizer inside the
+    backward (backward_slices) is declined: the norm needs every gradient.  Data parallel: call step() after the
+    gradients of every parameter this optimizer owns have been exchanged -- all ranks then hold the same gradients and
+    derive, bit for bit, the same norm and the same decision without a further collective."""
 
     CHUNK = 16384
     _DT = None
+    _ST = None
 
-    def __init__(self, *args, **kw):
+    def __init__(self, *args, max_grad_norm=None, skip_nonfinite=False, **kw):
         super().__init__(*args, **kw)
         self._plans = {}
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError("max_grad_norm must be positive (None: no clipping), not %r" % (max_grad_norm,))
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self.guarded = max_grad_norm is not None or self.skip_nonfinite
+        self._gstat = None                   # [groups, 8] int64 on the device: one skg_step_status per parameter group
+        self._gpart = None                   # [groups * GRADNORM_PARTIALS] float64: the sum-of-squares partials of the step
+
+    # ---- the guarded step's device state
+    @staticmethod
+    def _status_dtype():
+        import numpy as np
+        if SkgAdamW._ST is None:
+            SkgAdamW._ST = np.dtype([("total_norm", "f4"), ("coef", "f4"), ("applied", "i4"), ("reserved", "i4"),
+                                     ("steps_applied", "i8"), ("steps_skipped", "i8"), ("steps_clipped", "i8"),
+                                     ("max_total_norm", "f4"), ("reserved2", "i4"), ("pending_skips", "i8", (2,))])
+        return SkgAdamW._ST
+
+    def _guard_state(self, dev):
+        """The status records and the partials buffer for the present number of groups (made on first use; a group added
+        later starts with a copy of group 0's record: the counters are the same in all of them)."""
+        from . import _capi
+        n = len(self.param_groups)
+        if self._gstat is None or self._gstat.shape[0] != n or self._gstat.device != dev:
+            new = torch.zeros(n, 8, dtype=torch.int64, device=dev)
+            if self._gstat is not None and self._gstat.shape[0] > 0:
+                new[:, :6] = self._gstat[0, :6].to(dev)
+                self._plans.clear()              # (pending skips dropped with the old records: the step counts are re-read)
+            self._gstat = new
+            self._gpart = torch.empty(n * _capi.GRADNORM_PARTIALS, dtype=torch.float64, device=dev)
+        return self._gstat, self._gpart
+
+    def _read_status(self):
+        """The records as a numpy structured array (ONE device-to-host copy), or None before the first guarded step."""
+        if self._gstat is None:
+            return None
+        return self._gstat.cpu().numpy().reshape(-1).view(self._status_dtype())
+
+    def grad_stats(self):
+        """What the guarded steps left behind, in one device-to-host copy (it waits for the steps enqueued so far): the last
+        step's `total_norm`, `coef` and `applied`, and since the last reset_grad_stats() `steps_applied`, `steps_skipped`,
+        `steps_clipped` and `max_total_norm` (the largest finite norm).  Also re-synchronises the host's step numbers with
+        the device's applied counts, so that the launches after a skipped step use host-formed bias corrections again."""
+        if not self.guarded:
+            raise RuntimeError("grad_stats(): this optimizer was built without max_grad_norm / skip_nonfinite")
+        rec = self._read_status()
+        if rec is None:
+            return dict(total_norm=None, coef=None, applied=None, steps_applied=0, steps_skipped=0, steps_clipped=0,
+                        max_total_norm=0.0)
+        moved = False
+        for gi, pl in self._plans.items():
+            if pl.get("ok") and gi < len(rec):
+                # the slot the group's next launch would read: written by its last one
+                pend = int(rec[gi]["pending_skips"][(pl["host_step"] + 1) & 1])
+                if pend:
+                    pl["host_step"] -= pend
+                    moved = True
+        if moved:
+            self._gstat[:, 6:8].zero_()
+        r = rec[0]
+        return dict(total_norm=float(r["total_norm"]), coef=float(r["coef"]), applied=bool(r["applied"]),
+                    steps_applied=int(r["steps_applied"]), steps_skipped=int(r["steps_skipped"]),
+                    steps_clipped=int(r["steps_clipped"]), max_total_norm=float(r["max_total_norm"]))
+
+    def reset_grad_stats(self):
+        """Clears the running counters (applied, skipped, clipped, largest norm); the last step's values stay."""
+        if self._gstat is not None:
+            self._gstat[:, 2:6].zero_()
+
+    def _stock_step(self, closure=None):
+        """Everything the one-launch path does not cover.  With the guard on: the same semantics from the host -- torch's
+        clip_grad_norm_ (it scales p.grad in place), one finiteness read-back, the status records updated from here."""
+        if not self.guarded:
+            return CachedFusedAdamW.step(self, closure)
+        import numpy as np
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not params:
+            return loss
+        dev = params[0].device
+        if self.max_grad_norm is not None:
+            norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+        else:
+            norm = torch.linalg.vector_norm(torch.stack(torch._foreach_norm([p.grad for p in params])))
+        norm = float(norm)
+        finite = math.isfinite(norm)
+        coef = 1.0 if self.max_grad_norm is None else min(1.0, self.max_grad_norm / (norm + 1e-6)) if norm == norm else norm
+        apply = finite or not self.skip_nonfinite
+        if apply:
+            CachedFusedAdamW.step(self)
+        self._guard_state(dev)
+        rec = self._read_status().copy()
+        for r in rec:
+            r["total_norm"], r["coef"], r["applied"] = norm, coef, int(apply)
+            r["steps_applied" if apply else "steps_skipped"] += 1
+            if apply and coef < 1.0:
+                r["steps_clipped"] += 1
+            if finite and np.float32(norm) > r["max_total_norm"]:
+                r["max_total_norm"] = norm
+            r["pending_skips"] = 0           # (every caller dropped its plans: the next ones re-read the step counts)
+        self._gstat.copy_(torch.from_numpy(rec.view(np.int64).reshape(-1, 8)))
+        return loss
 
     def _plan(self, gi, c):
         """Static part of a group's chunk table; None if the group does not qualify."""
@@ -833,6 +969,8 @@ class SkgAdamW(CachedFusedAdamW):
                   flat_step=flat_step,
                   pinned=[torch.empty(nb, dtype=torch.uint8, pin_memory=True) for _ in range(2)],
                   events=[None, None], dtab=torch.empty(nb, dtype=torch.uint8, device=dev), flip=0)
+        if self._gstat is not None and gi < self._gstat.shape[0]:
+            self._gstat[gi, 6:8].zero_()     # host_step was just read from the device: no skip is pending behind it
         self._plans[gi] = pl
         return pl
 
@@ -846,6 +984,8 @@ class SkgAdamW(CachedFusedAdamW):
         the one-launch kernel does not cover, step hooks.  The caller MUST call backward_done() once the backward has been
         submitted with the slices."""
         import numpy as np
+        if self.guarded:                     # the norm needs every gradient: no update before the backward has ended
+            return None
         if len(self.param_groups) != 1 or getattr(self, "grad_scale", None) is not None or \
                 getattr(self, "found_inf", None) is not None:
             return None
@@ -902,7 +1042,10 @@ class SkgAdamW(CachedFusedAdamW):
         from .engine import _stream
         if closure is not None or getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
             self._plans.clear()
-            return super().step(closure)
+            return self._stock_step(closure)
+        guard = self.guarded
+        if guard and self.param_groups and self.param_groups[0]["params"]:
+            gstat, gpart = self._guard_state(self.param_groups[0]["params"][0].device)
         work = []
         for gi, group in enumerate(self.param_groups):
             c = None
@@ -912,7 +1055,7 @@ class SkgAdamW(CachedFusedAdamW):
             pl = self._plan(gi, c) if c is not None else None
             if pl is None or not pl["ok"]:
                 self._plans.clear()                          # step counts move outside this class: re-read them next time
-                return super().step()
+                return self._stock_step()
             grads = [p.grad for p in c[1]]
             # the fused step hands out the SAME gradient views from step to step (one gradient arena, reused when nothing
             # holds it: train_fused.Stacked.grad_arena): same addresses as in the table already on the device -> nothing
@@ -922,14 +1065,15 @@ class SkgAdamW(CachedFusedAdamW):
                 ptrs = list(map(_data_ptr, grads))
             except TypeError:                                # a parameter without gradient
                 self._plans.clear()
-                return super().step()
+                return self._stock_step()
             same = pl.get("grad_ptrs") == ptrs
             if not same and any(g is None or g.dtype != torch.float32 or not g.is_contiguous() or g.device != pl["dev"]
                                 for g in grads):
                 self._plans.clear()
-                return super().step()
+                return self._stock_step()
             work.append((group, c, pl, grads, same))
         lib = _capi.lib()
+        sums = []
         for group, c, pl, grads, same in work:
             tab = pl["tab"]
             if not same:
@@ -943,12 +1087,32 @@ class SkgAdamW(CachedFusedAdamW):
                 ev = pl["events"][k] or torch.cuda.Event()
                 ev.record(); pl["events"][k] = ev
                 pl["grad_ptrs"] = ptrs
+            if guard:
+                # the group's sum of squares into its slice of the partials; the updates follow once every group's is enqueued
+                _capi.check(lib.skg_grad_sumsq_f32(pl["dtab"].data_ptr(), len(tab),
+                                                   gpart.data_ptr() + 8 * _capi.GRADNORM_PARTIALS * len(sums), _stream()),
+                            "skg_grad_sumsq_f32")
+                sums.append((group, pl))
+                continue
             t = pl["host_step"] + 1
             beta1, beta2 = group["betas"]
             fs = pl["flat_step"]                             # the state's step tensors (one flat fp32 buffer): + 1 in the same launch
             _capi.check(lib.skg_adamw_f32(pl["dtab"].data_ptr(), len(tab), float(group["lr"]), float(beta1), float(beta2),
                                           float(group["eps"]), float(group["weight_decay"]), 1.0 - beta1 ** t,
                                           1.0 - beta2 ** t, fs.data_ptr(), fs.numel(), _stream()), "skg_adamw_f32")
+            pl["host_step"] = t
+        max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
+        for gi, (group, pl) in enumerate(sums):
+            # the norm over ALL groups' partials; a skipped step is the device's secret until grad_stats(): host_step counts
+            # launches, the record's pending_skips what to take off (include/skghoi.h)
+            t = pl["host_step"] + 1
+            beta1, beta2 = group["betas"]
+            fs = pl["flat_step"]
+            _capi.check(lib.skg_adamw_guarded_f32(pl["dtab"].data_ptr(), len(pl["tab"]), float(group["lr"]), float(beta1),
+                                                  float(beta2), float(group["eps"]), float(group["weight_decay"]),
+                                                  1.0 - beta1 ** t, 1.0 - beta2 ** t, t, max_norm, int(self.skip_nonfinite),
+                                                  gpart.data_ptr(), _capi.GRADNORM_PARTIALS * len(sums), fs.data_ptr(),
+                                                  fs.numel(), gstat.data_ptr() + 64 * gi, _stream()), "skg_adamw_guarded_f32")
             pl["host_step"] = t
         return None
 
@@ -1113,10 +1277,26 @@ class Trainer:
     wrapped net without DDP's "module." prefix, as pocket saves `net.module.state_dict()`).
 
     `step_fn(net, optimizer, batch) -> (loss_dict, results)` adapts the loader's batch to the net's call; the default
-    expects (features, detections, image_shapes, targets) batches and calls `train_step`."""
+    expects (features, detections, image_shapes, targets) batches and calls `train_step`.
+
+    on_nonfinite: what a step with non-finite gradients means when the optimizer skips such steps on the device
+    (SkgAdamW(skip_nonfinite=True): the weights, the moments and the step counts stay as they were).  "raise" (default):
+    the ValueError of the reference's NaN guard, raised where the optimizer's record is read -- at the print interval and
+    at the end of the epoch, never per step -- naming the iteration; the weights are intact and a checkpoint can still be
+    written.  "skip": the step is counted and the run goes on (needs lazy_losses=True with the default step: the eager
+    NaN guard of `train_step` raises before the optimizer is reached).  With a guarded optimizer the record -- last and
+    largest gradient norm, clipped and skipped steps -- is read on every rank (the decision to raise is the same on all
+    of them), printed beside the losses on rank 0 and kept in `last_report["grad_stats"]`."""
 
     def __init__(self, net, optimizer, scheduler=None, train_loader=None, rank=0, cache_dir=None, step_fn=None,
-                 print_interval=0, lazy_losses=False, val_loader=None, num_classes=117, train_meter=None, device=None):
+                 print_interval=0, lazy_losses=False, val_loader=None, num_classes=117, train_meter=None, device=None,
+                 on_nonfinite="raise"):
+        if on_nonfinite not in ("raise", "skip"):
+            raise ValueError("on_nonfinite must be 'raise' or 'skip', not %r" % (on_nonfinite,))
+        if on_nonfinite == "skip" and step_fn is None and not lazy_losses:
+            raise ValueError("on_nonfinite='skip' needs lazy_losses=True: the eager NaN guard raises in front of the optimizer")
+        self.on_nonfinite = on_nonfinite
+        self._skipped_seen = 0
         self.net, self.optimizer, self.scheduler = net, optimizer, scheduler
         self.train_loader = train_loader
         self.val_loader = val_loader
@@ -1198,7 +1378,8 @@ class Trainer:
         t1 = time.perf_counter()
         ap_val = self.validate() if self.val_loader is not None else None
         t2 = time.perf_counter()
-        self.last_report = dict(epoch=self.epoch, training_map=(None if ap_train is None else float(ap_train.mean())),
+        kept = {k: v for k, v in (self.last_report or {}).items() if k == "grad_stats"}      # (the guarded optimizer's record)
+        self.last_report = dict(kept, epoch=self.epoch, training_map=(None if ap_train is None else float(ap_train.mean())),
                                 validation_map=(None if ap_val is None else float(ap_val.mean())),
                                 evaluation_time_s=t1 - t0, total_time_s=t2 - t0)
         if self.rank == 0 and (ap_train is not None or ap_val is not None):
@@ -1237,6 +1418,26 @@ class Trainer:
         self.epoch = int(ckpt.get("epoch", 0))
         self.iteration = int(ckpt.get("iteration", 0))
 
+    def _grad_report(self):
+        """The guarded optimizer's record (None without one), kept in last_report; raises for a newly skipped step unless
+        on_nonfinite == "skip".  One device-to-host copy: called where the losses are read anyway."""
+        if not getattr(self.optimizer, "guarded", False):
+            return None
+        stats = self.optimizer.grad_stats()
+        self.last_report = dict(self.last_report or {}, grad_stats=stats)
+        new = stats["steps_skipped"] - self._skipped_seen
+        self._skipped_seen = stats["steps_skipped"]
+        if new > 0 and self.on_nonfinite == "raise":
+            raise ValueError("Non-finite gradients: %d step(s) up to iteration %d were skipped by the optimizer (the weights "
+                             "are intact)" % (new, self.iteration))
+        return stats
+
+    @staticmethod
+    def _grad_text(stats):
+        return "grad norm %.4g (max %.4g), clipped %d, skipped %d" % (
+            stats["total_norm"] if stats["total_norm"] is not None else float("nan"), stats["max_total_norm"],
+            stats["steps_clipped"], stats["steps_skipped"])
+
     # -- loop
     def train_epoch(self) -> None:
         sampler = getattr(self.train_loader, "sampler", None)
@@ -1247,6 +1448,7 @@ class Trainer:
             self.meter = self._new_meter()
         # the default step looks TWO batches ahead (train_step: prefetch / prefetch2): batch i + 2's preparation starts
         # during step i and ends during step i + 1, off the step boundary
+        check = self.on_nonfinite != "skip"                 # ("skip": a NaN loss belongs to a step the optimizer left out)
         for batch, nxt, nxt2 in _with_lookahead(self.train_loader, self.lookahead, depth=2):
             losses, results = self.step_fn(self.net, self.optimizer, batch, nxt, nxt2) if self.lookahead else \
                 self.step_fn(self.net, self.optimizer, batch)
@@ -1255,13 +1457,19 @@ class Trainer:
             self.iteration += 1
             self.history.append(losses)
             if self.print_interval and self.iteration % self.print_interval == 0:
+                stats = self._grad_report()                  # (first: a skipped step is reported as such, not as a NaN loss)
                 if self.lazy_losses:
-                    losses = self.history[-1] = read_losses(losses)          # every rank: the NaN guard is collective
+                    losses = self.history[-1] = read_losses(losses, check)   # every rank: the NaN guard is collective
                 if self.rank == 0:
-                    print("Epoch %d iteration %d: %s" % (self.epoch, self.iteration,
-                                                         ", ".join("%s %.4f" % kv for kv in losses.items())))
+                    print("Epoch %d iteration %d: %s%s" % (self.epoch, self.iteration,
+                                                           ", ".join("%s %.4f" % kv for kv in losses.items()),
+                                                           "" if stats is None else " | " + self._grad_text(stats)))
+        stats = self._grad_report()
         if self.lazy_losses:
-            self.history = [h if all(isinstance(v, float) for v in h.values()) else read_losses(h) for h in self.history]
+            self.history = [h if all(isinstance(v, float) for v in h.values()) else read_losses(h, check)
+                            for h in self.history]
+        if stats is not None and self.rank == 0:
+            print("Epoch %d: %s" % (self.epoch, self._grad_text(stats)))
         if self.meter is not None or self.val_loader is not None:
             self.on_end_epoch()
         self.epoch += 1

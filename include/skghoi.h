@@ -84,7 +84,8 @@ int skg_layout_pack_train(const int64_t* n_h_host, const int64_t* n_host, const 
 /* ---------------------------------------------------------------------------------------------------------------
  * InteractionHead.preprocess (HEAD:92-151): score >= thresh -> class-wise NMS (torchvision batched_nms, coordinate
  * trick, IoU > nms_thresh suppresses) -> descending score (ties: ascending input index) -> first max_human humans and
- * max_object others -> humans first.  One workgroup per image.
+ * max_object others -> humans first.  One workgroup per image.  A NaN coordinate in an active box reaches the offset
+ * of the coordinate trick as it does through Tensor.max(): nothing is suppressed in that image.
  *   det_off[B+1]  : row range of each image in boxes/scores/labels (train: GT boxes already prepended, HEAD:107-116)
  *   nverbs[num_obj_classes] : number of target classes per object class (len(object_class_to_target_class[c]))
  *   prior_pow     : exponent applied to detection scores by compute_prior_scores (HEAD:742), used only for out_count

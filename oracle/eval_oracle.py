@@ -1,6 +1,7 @@
 """ORACLE (test infrastructure): loop-level restatement of pocket's BoxPairAssociation and DetectionAPMeter ('11P') as
 utils.py:148-198 uses them.  pocket is absent and unpinned: parity is unpinned at this boundary."""
 import numpy as np
+import torch
 
 
 def iou1(a, b):
@@ -43,7 +44,9 @@ def ap_11p(scores, labels, num_gt):
         tp += labels[i]; fp += 1 - labels[i]
         prec.append(tp / (tp + fp)); rec.append(tp / num_gt)
     ap = 0.0
-    for t in np.linspace(0, 1, 11):
+    # the meter's own thresholds, torch.linspace in float64 (end - step * k in the upper half: 0.6 and 0.7 exactly, where
+    # np.linspace's start + step * k gives 0.6000000000000001 and 0.7000000000000001 and drops a recall of exactly 3 / 5)
+    for t in torch.linspace(0, 1, 11, dtype=torch.float64).tolist():
         ps = [p for p, r in zip(prec, rec) if r >= t]
         if ps:
             ap += max(ps) / 11

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(PRE_THREADS) void skg_preprocess_kernel(
     __shared__ unsigned char shum[SKG_MAX_DET_PER_IMAGE];
     __shared__ float sred[PRE_THREADS / 64];
     __shared__ int ssel[SKG_MAX_NODES];
-    __shared__ int sact;
+    __shared__ int sact, snan;
     // the image's raw candidates, read ONCE: boxes, scores, labels and the verb counts of the classes all leave in one round
     // trip (independent loads), every later phase -- sorted-order boxes, the counts at the end -- reads these copies.  The
     // kernel is a chain of dependent phases on one workgroup: each trip to global memory it does not make is ~2 us of a
@@ -65,6 +65,7 @@ __global__ __launch_bounds__(PRE_THREADS) void skg_preprocess_kernel(
     // ---- keys: descending score, ties by ascending input index; inactive (score < thresh or NaN) sort last
     float lmax = -INFINITY;
     int lact = 0;
+    bool lnan = false;                                 // an ACTIVE box with a NaN coordinate (fmaxf would drop it)
     for (int t = tid; t < 256 && t < num_obj_classes; t += PRE_THREADS) snv[t] = nverbs[t];
     for (int i = tid; i < npow; i += PRE_THREADS) {
         unsigned long long key = ~0ull;
@@ -78,6 +79,7 @@ __global__ __launch_bounds__(PRE_THREADS) void skg_preprocess_kernel(
             if (s >= score_thresh) {
                 key = ((unsigned long long)(~skg_orderable(s)) << 32) | (unsigned)i;
                 lmax = fmaxf(lmax, fmaxf(fmaxf(bx.x, bx.y), fmaxf(bx.z, bx.w)));
+                lnan |= (bx.x != bx.x) | (bx.y != bx.y) | (bx.z != bx.z) | (bx.w != bx.w);
                 ++lact;
             }
         }
@@ -87,13 +89,18 @@ __global__ __launch_bounds__(PRE_THREADS) void skg_preprocess_kernel(
     lmax = skg_wave_max(lmax);
     if ((tid & 63) == 0) sred[tid >> 6] = lmax;
     __syncthreads();
-    const float max_coord = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
+    float max_coord = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
     // number of active candidates
-    if (tid == 0) sact = 0;
+    if (tid == 0) { sact = 0; snan = 0; }
     __syncthreads();
     if (lact) atomicAdd(&sact, lact);
+    if (lnan) snan = 1;                                // (every writer stores the same value)
     __syncthreads();
     const int nact = sact;
+    // Tensor.max() propagates NaN where fmaxf drops it: one NaN coordinate in an active box makes every offset of the
+    // image NaN, hence every shifted box, area and IoU, and `IoU > thr` never holds -- the reference suppresses nothing
+    // in such an image.  (With max_coord NaN the fmaxf / fminf of the IoU below no longer matter: both areas are NaN.)
+    if (snan) max_coord = __uint_as_float(0x7fc00000u);
 
     // ---- bitonic sort of the keys (ascending)
     for (int k = 2; k <= npow; k <<= 1) {

@@ -18,7 +18,9 @@
 // Limits of the *_nhwc entries: C % 8 == 0 and pooled <= SKG_ROI_NHWC_MAX_POOLED (8: the 64 x (pooled^2 | 1) fp32 tile is
 // static LDS, 16.25 KiB) else SKG_E_ARG; every level base, boxes, out / dout 16-byte aligned else SKG_E_ALIGN;
 // n_rois * ceil(C / 64) workgroups <= 2^31 - 1 else SKG_E_LIMIT.
+#include <algorithm>
 #include <atomic>
+#include <type_traits>
 #include "skg_common.h"
 
 struct skg_roi_levels {
@@ -51,6 +53,68 @@ template <> struct skg_roi_elem<SKG_DTYPE_BF16> {
     }
 };
 
+// Level and bin grid of one RoI: the one place that knows LevelMapper, the scaled corners, the >= 1 clamps and the grid.
+struct skg_roi_geom {
+    int l, H, W, gh, gw;
+    float x1, y1, bw, bh, cnt;
+};
+__device__ __forceinline__ skg_roi_geom skg_roi_box_geom(const skg_roi_levels& L, const float4 b, int pooled, int sampling) {
+    skg_roi_geom g;
+    const float s = sqrtf((b.z - b.x) * (b.w - b.y));                  // LevelMapper (torchvision.ops.poolers.LevelMapper)
+    float lv = floorf((float)L.canonical_level + log2f(s / L.canonical_scale) + 1e-6f);
+    lv = fminf(fmaxf(lv, (float)L.k_min), (float)L.k_max);
+    g.l = (int)lv - L.k_min;
+    g.H = L.H[g.l]; g.W = L.W[g.l];
+    const float sc = L.scale[g.l];
+    const float x1 = b.x * sc, y1 = b.y * sc, x2 = b.z * sc, y2 = b.w * sc;
+    const float rw = fmaxf(x2 - x1, 1.f), rh = fmaxf(y2 - y1, 1.f);
+    g.x1 = x1; g.y1 = y1;
+    g.bw = rw / (float)pooled; g.bh = rh / (float)pooled;
+    g.gh = sampling > 0 ? sampling : (int)ceilf(rh / pooled);
+    g.gw = sampling > 0 ? sampling : (int)ceilf(rw / pooled);
+    g.cnt = fmaxf((float)(g.gh * g.gw), 1.f);
+    return g;
+}
+
+// Coordinate of sample i of the n in bin `bin` along one axis.  Every kernel's bits depend on exactly this operation order:
+// nothing is factored, reassociated or hoisted (size / n in particular).
+__device__ __forceinline__ float skg_roi_coord(float origin, int bin, float size, int i, int n) {
+    return origin + bin * size + (i + 0.5f) * size / (float)n;
+}
+
+// One axis of a sample, the one place that knows the outside test and the clamps: false when the sample lies outside on
+// this axis, else the two taps and their weights l (high tap) / h (low tap).
+struct skg_roi_axis {
+    int low, high;
+    float l, h;
+};
+__device__ __forceinline__ bool skg_roi_axis_sample(int size, float v, skg_roi_axis& a) {
+    if (v < -1.0f || v > (float)size) return false;
+    if (v <= 0.f) v = 0.f;
+    int low = (int)v, high;
+    if (low >= size - 1) { high = low = size - 1; v = (float)low; } else high = low + 1;
+    a.low = low; a.high = high;
+    a.l = v - low; a.h = 1.f - a.l;
+    return true;
+}
+
+// The four taps of one sample and their weights; false: the sample lies outside and adds 0.
+struct skg_roi_taps {
+    int y_low, y_high, x_low, x_high;
+    float w1, w2, w3, w4;
+};
+__device__ __forceinline__ bool skg_roi_sample(int H, int W, float y, float x, skg_roi_taps& t) {
+    skg_roi_axis ay, ax;
+    if (!skg_roi_axis_sample(H, y, ay) || !skg_roi_axis_sample(W, x, ax)) return false;
+    t.y_low = ay.low; t.y_high = ay.high; t.x_low = ax.low; t.x_high = ax.high;
+    t.w1 = ay.h * ax.h; t.w2 = ay.h * ax.l; t.w3 = ay.l * ax.h; t.w4 = ay.l * ax.l;
+    return true;
+}
+
+// The [B, C, H, W] forward below keeps its own copy of the geometry, the coordinate and the sample rule (skg_bilinear): on
+// skg_roi_box_geom / skg_roi_sample it computed the same bits but ran 0.4-0.5 us of 30-32 us slower on an MI355X (kernel-only
+// times), with fewer instructions as with more.  Its expressions must stay those of the helpers above, operation
+// for operation: tests/test_channels_last_roi_gpu.py and the host emulation compare its bits with the channels-last forward.
 template <int DT>
 __device__ __forceinline__ float skg_bilinear(const typename skg_roi_elem<DT>::T* __restrict__ f, int H, int W, float y,
                                               float x) {
@@ -122,36 +186,20 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_kernel(const skg_roi_le
         const int ph = (int)((idx / pooled) % pooled);
         const int c = (int)((idx / ((int64_t)pooled * pooled)) % L.C);
         const int n = (int)(idx / ((int64_t)pooled * pooled * L.C));
-        const float4 b = *reinterpret_cast<const float4*>(boxes + 4 * (int64_t)n);
-        const float s = sqrtf((b.z - b.x) * (b.w - b.y));
-        float lv = floorf((float)L.canonical_level + log2f(s / L.canonical_scale) + 1e-6f);
-        lv = fminf(fmaxf(lv, (float)L.k_min), (float)L.k_max);
-        const int l = (int)lv - L.k_min;
-        const int H = L.H[l], W = L.W[l];
-        const float sc = L.scale[l];
-        float* f = static_cast<float*>(const_cast<void*>(L.feat[l])) + ((int64_t)box_image[n] * L.C + c) * H * W;       // gradient map of the level
-        const float x1 = b.x * sc, y1 = b.y * sc, x2 = b.z * sc, y2 = b.w * sc;
-        const float rw = fmaxf(x2 - x1, 1.f), rh = fmaxf(y2 - y1, 1.f);
-        const float bw = rw / (float)pooled, bh = rh / (float)pooled;
-        const int gh = sampling > 0 ? sampling : (int)ceilf(rh / pooled);
-        const int gw = sampling > 0 ? sampling : (int)ceilf(rw / pooled);
-        const float g = dout[idx] / fmaxf((float)(gh * gw), 1.f);
-        for (int iy = 0; iy < gh; ++iy) {
-            float y = y1 + ph * bh + (iy + 0.5f) * bh / (float)gh;
-            for (int ix = 0; ix < gw; ++ix) {
-                float x = x1 + pw * bw + (ix + 0.5f) * bw / (float)gw;
-                float yy = y;
-                if (yy < -1.0f || yy > (float)H || x < -1.0f || x > (float)W) continue;
-                if (yy <= 0.f) yy = 0.f;
-                if (x <= 0.f) x = 0.f;
-                int y_low = (int)yy, x_low = (int)x, y_high, x_high;
-                if (y_low >= H - 1) { y_high = y_low = H - 1; yy = (float)y_low; } else y_high = y_low + 1;
-                if (x_low >= W - 1) { x_high = x_low = W - 1; x = (float)x_low; } else x_high = x_low + 1;
-                const float ly = yy - y_low, lx = x - x_low, hy = 1.f - ly, hx = 1.f - lx;
-                atomicAdd(f + y_low * W + x_low, hy * hx * g);
-                atomicAdd(f + y_low * W + x_high, hy * lx * g);
-                atomicAdd(f + y_high * W + x_low, ly * hx * g);
-                atomicAdd(f + y_high * W + x_high, ly * lx * g);
+        const skg_roi_geom g = skg_roi_box_geom(L, *reinterpret_cast<const float4*>(boxes + 4 * (int64_t)n), pooled, sampling);
+        const int W = g.W;
+        float* f = static_cast<float*>(const_cast<void*>(L.feat[g.l])) + ((int64_t)box_image[n] * L.C + c) * g.H * W;   // gradient map of the level
+        const float gr = dout[idx] / g.cnt;
+        for (int iy = 0; iy < g.gh; ++iy) {
+            const float y = skg_roi_coord(g.y1, ph, g.bh, iy, g.gh);
+            for (int ix = 0; ix < g.gw; ++ix) {
+                const float x = skg_roi_coord(g.x1, pw, g.bw, ix, g.gw);
+                skg_roi_taps t;
+                if (!skg_roi_sample(g.H, W, y, x, t)) continue;
+                atomicAdd(f + t.y_low * W + t.x_low, t.w1 * gr);
+                atomicAdd(f + t.y_low * W + t.x_high, t.w2 * gr);
+                atomicAdd(f + t.y_high * W + t.x_low, t.w3 * gr);
+                atomicAdd(f + t.y_high * W + t.x_high, t.w4 * gr);
             }
         }
     }
@@ -161,47 +209,6 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_kernel(const skg_roi_le
 #define SKG_ROI_NHWC_SLAB 64
 #define SKG_ROI_NHWC_MAX_POOLED 8
 #define SKG_ROI_NHWC_TILE (SKG_ROI_NHWC_SLAB * (SKG_ROI_NHWC_MAX_POOLED * SKG_ROI_NHWC_MAX_POOLED + 1))
-
-// Level and bin grid of one RoI: the expressions of skg_roi_align_kernel, once per thread instead of once per element.
-struct skg_roi_geom {
-    int l, H, W, gh, gw;
-    float x1, y1, bw, bh, cnt;
-};
-__device__ __forceinline__ skg_roi_geom skg_roi_box_geom(const skg_roi_levels& L, const float4 b, int pooled, int sampling) {
-    skg_roi_geom g;
-    const float s = sqrtf((b.z - b.x) * (b.w - b.y));
-    float lv = floorf((float)L.canonical_level + log2f(s / L.canonical_scale) + 1e-6f);
-    lv = fminf(fmaxf(lv, (float)L.k_min), (float)L.k_max);
-    g.l = (int)lv - L.k_min;
-    g.H = L.H[g.l]; g.W = L.W[g.l];
-    const float sc = L.scale[g.l];
-    const float x1 = b.x * sc, y1 = b.y * sc, x2 = b.z * sc, y2 = b.w * sc;
-    const float rw = fmaxf(x2 - x1, 1.f), rh = fmaxf(y2 - y1, 1.f);
-    g.x1 = x1; g.y1 = y1;
-    g.bw = rw / (float)pooled; g.bh = rh / (float)pooled;
-    g.gh = sampling > 0 ? sampling : (int)ceilf(rh / pooled);
-    g.gw = sampling > 0 ? sampling : (int)ceilf(rw / pooled);
-    g.cnt = fmaxf((float)(g.gh * g.gw), 1.f);
-    return g;
-}
-
-// The four taps of one sample and their weights (skg_bilinear's clamps); false: the sample lies outside and adds 0.
-struct skg_roi_taps {
-    int y_low, y_high, x_low, x_high;
-    float w1, w2, w3, w4;
-};
-__device__ __forceinline__ bool skg_roi_sample(int H, int W, float y, float x, skg_roi_taps& t) {
-    if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return false;
-    if (y <= 0.f) y = 0.f;
-    if (x <= 0.f) x = 0.f;
-    int y_low = (int)y, x_low = (int)x, y_high, x_high;
-    if (y_low >= H - 1) { y_high = y_low = H - 1; y = (float)y_low; } else y_high = y_low + 1;
-    if (x_low >= W - 1) { x_high = x_low = W - 1; x = (float)x_low; } else x_high = x_low + 1;
-    const float ly = y - y_low, lx = x - x_low, hy = 1.f - ly, hx = 1.f - lx;
-    t.y_low = y_low; t.y_high = y_high; t.x_low = x_low; t.x_high = x_high;
-    t.w1 = hy * hx; t.w2 = hy * lx; t.w3 = ly * hx; t.w4 = ly * lx;
-    return true;
-}
 
 // 16 bytes of consecutive elements of dtype DT
 template <int DT> union skg_roi_vec {
@@ -239,9 +246,9 @@ __global__ __launch_bounds__(256) void skg_roi_align_nhwc_kernel(const skg_roi_l
 #pragma unroll
             for (int j = 0; j < VM; ++j) acc[j] = 0.f;
             for (int iy = 0; iy < g.gh; ++iy) {
-                const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
+                const float y = skg_roi_coord(g.y1, ph, g.bh, iy, g.gh);
                 for (int ix = 0; ix < g.gw; ++ix) {
-                    const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
+                    const float x = skg_roi_coord(g.x1, pw, g.bw, ix, g.gw);
                     skg_roi_taps t;
                     if (!skg_roi_sample(H, W, y, x, t)) {
 #pragma unroll
@@ -313,9 +320,9 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_nhwc_kernel(const skg_r
 #pragma unroll
         for (int j = 0; j < VM; ++j) gr[j] = tile[(cl + j) * S + bin] / g.cnt;
         for (int iy = 0; iy < g.gh; ++iy) {
-            const float y = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / (float)g.gh;
+            const float y = skg_roi_coord(g.y1, ph, g.bh, iy, g.gh);
             for (int ix = 0; ix < g.gw; ++ix) {
-                const float x = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / (float)g.gw;
+                const float x = skg_roi_coord(g.x1, pw, g.bw, ix, g.gw);
                 skg_roi_taps t;
                 if (!skg_roi_sample(H, W, y, x, t)) continue;
                 float* p1 = f + ((int64_t)t.y_low * W + t.x_low) * L.C;
@@ -333,191 +340,6 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_nhwc_kernel(const skg_r
             }
         }
     }
-}
-
-// launches since the last reset: forward NCHW, forward NHWC, backward NCHW, backward NHWC (skg_roi_align_layout_counts)
-static std::atomic<long long> g_roi_layout_counts[4];
-
-static int skg_roi_levels_fill(skg_roi_levels& L, const void* const* feats_host, const int32_t* H_host,
-                               const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
-                               float canonical_scale, int canonical_level) {
-    for (int l = 0; l < SKG_ROI_MAX_LEVELS; ++l) {
-        const bool in = l < n_levels;
-        L.feat[l] = in ? feats_host[l] : nullptr;
-        L.H[l] = in ? H_host[l] : 0; L.W[l] = in ? W_host[l] : 0; L.scale[l] = in ? scales_host[l] : 0.f;
-        if (in && (!L.feat[l] || L.H[l] <= 0 || L.W[l] <= 0)) return SKG_E_ARG;
-    }
-    L.n_levels = n_levels; L.k_min = k_min; L.k_max = k_max; L.C = C;
-    L.canonical_scale = canonical_scale; L.canonical_level = canonical_level;
-    return 0;
-}
-
-extern "C" int skg_roi_align_bwd_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
-                                     const float* scales_host, int n_levels, int C, int k_min, int k_max,
-                                     float canonical_scale, int canonical_level, const float* boxes,
-                                     const int32_t* box_image, int n_rois, int pooled, int sampling, const float* dout,
-                                     void* stream) {
-    if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
-        return SKG_E_ARG;
-    if (n_rois == 0) return 0;
-    if (!dfeats_host || !H_host || !W_host || !scales_host || !boxes || !box_image || !dout) return SKG_E_ARG;
-    if (!skg_aligned16(boxes)) return SKG_E_ALIGN;
-    skg_roi_levels L;
-    const int rc = skg_roi_levels_fill(L, reinterpret_cast<const void* const*>(dfeats_host), H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
-                                       canonical_level);
-    if (rc) return rc;
-    const int64_t total = (int64_t)n_rois * C * pooled * pooled;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    g_roi_layout_counts[2].fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(skg_roi_align_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, L, boxes,
-                       box_image, n_rois, pooled, sampling, dout);
-    return skg_launch_status();
-}
-
-// launch of one <map, output> instance (arguments checked by the caller)
-template <int MDT, int ODT>
-static void skg_roi_align_launch(const skg_roi_levels& L, const float* boxes, const int32_t* box_image, int n_rois,
-                                 int pooled, int sampling, void* out, hipStream_t stream) {
-    const int64_t total = (int64_t)n_rois * L.C * pooled * pooled;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;                          // grid-stride the rest
-    hipLaunchKernelGGL((skg_roi_align_kernel<MDT, ODT>), dim3((unsigned)blocks), dim3(256), 0, stream, L, boxes,
-                       box_image, n_rois, pooled, sampling, static_cast<typename skg_roi_elem<ODT>::T*>(out));
-}
-
-extern "C" int skg_roi_align_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
-                               const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
-                               int k_max, float canonical_scale, int canonical_level, const float* boxes,
-                               const int32_t* box_image, int n_rois, int pooled, int sampling, void* out, int out_dtype,
-                               void* stream) {
-    if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
-        return SKG_E_ARG;
-    if (map_dtype < SKG_DTYPE_F32 || map_dtype > SKG_DTYPE_BF16 || out_dtype < SKG_DTYPE_F32 || out_dtype > SKG_DTYPE_BF16)
-        return SKG_E_ARG;
-    if (n_rois == 0) return 0;
-    if (!feats_host || !H_host || !W_host || !scales_host || !boxes || !box_image || !out) return SKG_E_ARG;
-    if (!skg_aligned16(boxes)) return SKG_E_ALIGN;
-    skg_roi_levels L;
-    const int rc = skg_roi_levels_fill(L, feats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
-                                       canonical_scale, canonical_level);
-    if (rc) return rc;
-    g_roi_layout_counts[0].fetch_add(1, std::memory_order_relaxed);
-    hipStream_t s = (hipStream_t)stream;
-#define SKG_ROI_OUT(M)                                                                                           \
-    switch (out_dtype) {                                                                                         \
-        case SKG_DTYPE_F32: skg_roi_align_launch<M, SKG_DTYPE_F32>(L, boxes, box_image, n_rois, pooled, sampling, out, s); break; \
-        case SKG_DTYPE_F16: skg_roi_align_launch<M, SKG_DTYPE_F16>(L, boxes, box_image, n_rois, pooled, sampling, out, s); break; \
-        default: skg_roi_align_launch<M, SKG_DTYPE_BF16>(L, boxes, box_image, n_rois, pooled, sampling, out, s); break;          \
-    }
-    switch (map_dtype) {
-        case SKG_DTYPE_F32: SKG_ROI_OUT(SKG_DTYPE_F32) break;
-        case SKG_DTYPE_F16: SKG_ROI_OUT(SKG_DTYPE_F16) break;
-        default: SKG_ROI_OUT(SKG_DTYPE_BF16) break;
-    }
-#undef SKG_ROI_OUT
-    return skg_launch_status();
-}
-
-extern "C" int skg_roi_align_f32(const float* const* feats_host, const int32_t* H_host, const int32_t* W_host,
-                                 const float* scales_host, int n_levels, int C, int k_min, int k_max,
-                                 float canonical_scale, int canonical_level, const float* boxes,
-                                 const int32_t* box_image, int n_rois, int pooled, int sampling, float* out,
-                                 void* stream) {
-    return skg_roi_align_x(reinterpret_cast<const void* const*>(feats_host), SKG_DTYPE_F32, H_host, W_host, scales_host,
-                           n_levels, C, k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois,
-                           pooled, sampling, out, SKG_DTYPE_F32, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ channels-last entries
-extern "C" void skg_roi_align_layout_counts(int64_t* out4, int reset) {
-    for (int i = 0; i < 4; ++i) {
-        if (out4) out4[i] = g_roi_layout_counts[i].load(std::memory_order_relaxed);
-        if (reset) g_roi_layout_counts[i].store(0, std::memory_order_relaxed);
-    }
-}
-
-// what both *_nhwc entries ask of the shape (header comment of this file)
-static int skg_roi_nhwc_check(int n_levels, int C, int k_min, int k_max, int pooled, int n_rois) {
-    if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
-        return SKG_E_ARG;
-    if ((C & 7) || pooled > SKG_ROI_NHWC_MAX_POOLED) return SKG_E_ARG;
-    return 0;
-}
-
-static int skg_roi_nhwc_levels(skg_roi_levels& L, const void* const* feats_host, const int32_t* H_host,
-                               const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
-                               float canonical_scale, int canonical_level, int n_rois, int64_t* blocks) {
-    const int rc = skg_roi_levels_fill(L, feats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
-                                       canonical_scale, canonical_level);
-    if (rc) return rc;
-    for (int l = 0; l < n_levels; ++l)
-        if (!skg_aligned16(L.feat[l])) return SKG_E_ALIGN;
-    *blocks = (int64_t)n_rois * ((C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB);
-    return *blocks > 0x7fffffffLL ? SKG_E_LIMIT : 0;
-}
-
-template <int MDT, int ODT>
-static void skg_roi_align_nhwc_launch(const skg_roi_levels& L, const float* boxes, const int32_t* box_image, int64_t blocks,
-                                      int pooled, int sampling, void* out, hipStream_t stream) {
-    hipLaunchKernelGGL((skg_roi_align_nhwc_kernel<MDT, ODT>), dim3((unsigned)blocks), dim3(256), 0, stream, L, boxes,
-                       box_image, (L.C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB, pooled, sampling,
-                       static_cast<typename skg_roi_elem<ODT>::T*>(out));
-}
-
-extern "C" int skg_roi_align_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
-                                    const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
-                                    int k_max, float canonical_scale, int canonical_level, const float* boxes,
-                                    const int32_t* box_image, int n_rois, int pooled, int sampling, void* out,
-                                    int out_dtype, void* stream) {
-    int rc = skg_roi_nhwc_check(n_levels, C, k_min, k_max, pooled, n_rois);
-    if (rc) return rc;
-    if (map_dtype < SKG_DTYPE_F32 || map_dtype > SKG_DTYPE_BF16 || out_dtype < SKG_DTYPE_F32 || out_dtype > SKG_DTYPE_BF16)
-        return SKG_E_ARG;
-    if (n_rois == 0) return 0;
-    if (!feats_host || !H_host || !W_host || !scales_host || !boxes || !box_image || !out) return SKG_E_ARG;
-    if (!skg_aligned16(boxes) || !skg_aligned16(out)) return SKG_E_ALIGN;
-    skg_roi_levels L;
-    int64_t blocks = 0;
-    rc = skg_roi_nhwc_levels(L, feats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
-                             canonical_level, n_rois, &blocks);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    g_roi_layout_counts[1].fetch_add(1, std::memory_order_relaxed);
-#define SKG_ROI_OUT(M)                                                                                           \
-    switch (out_dtype) {                                                                                         \
-        case SKG_DTYPE_F32: skg_roi_align_nhwc_launch<M, SKG_DTYPE_F32>(L, boxes, box_image, blocks, pooled, sampling, out, s); break; \
-        case SKG_DTYPE_F16: skg_roi_align_nhwc_launch<M, SKG_DTYPE_F16>(L, boxes, box_image, blocks, pooled, sampling, out, s); break; \
-        default: skg_roi_align_nhwc_launch<M, SKG_DTYPE_BF16>(L, boxes, box_image, blocks, pooled, sampling, out, s); break;          \
-    }
-    switch (map_dtype) {
-        case SKG_DTYPE_F32: SKG_ROI_OUT(SKG_DTYPE_F32) break;
-        case SKG_DTYPE_F16: SKG_ROI_OUT(SKG_DTYPE_F16) break;
-        default: SKG_ROI_OUT(SKG_DTYPE_BF16) break;
-    }
-#undef SKG_ROI_OUT
-    return skg_launch_status();
-}
-
-extern "C" int skg_roi_align_bwd_nhwc_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
-                                          const float* scales_host, int n_levels, int C, int k_min, int k_max,
-                                          float canonical_scale, int canonical_level, const float* boxes,
-                                          const int32_t* box_image, int n_rois, int pooled, int sampling,
-                                          const float* dout, void* stream) {
-    int rc = skg_roi_nhwc_check(n_levels, C, k_min, k_max, pooled, n_rois);
-    if (rc) return rc;
-    if (n_rois == 0) return 0;
-    if (!dfeats_host || !H_host || !W_host || !scales_host || !boxes || !box_image || !dout) return SKG_E_ARG;
-    if (!skg_aligned16(boxes) || !skg_aligned16(dout)) return SKG_E_ALIGN;
-    skg_roi_levels L;
-    int64_t blocks = 0;
-    rc = skg_roi_nhwc_levels(L, reinterpret_cast<const void* const*>(dfeats_host), H_host, W_host, scales_host, n_levels,
-                             C, k_min, k_max, canonical_scale, canonical_level, n_rois, &blocks);
-    if (rc) return rc;
-    g_roi_layout_counts[3].fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(skg_roi_align_bwd_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, L, boxes,
-                       box_image, (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB, pooled, sampling, dout);
-    return skg_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------ deterministic backward
@@ -552,34 +374,19 @@ struct skg_roi_det_item {
     float x1, y1, bw, bh, cnt;
 };
 
-// One axis of skg_roi_sample: false when the sample lies outside on this axis; l / h are ly / hy (lx / hx).
-struct skg_roi_axis {
-    int low, high;
-    float l, h;
-};
-__device__ __forceinline__ bool skg_roi_axis_sample(int size, float v, skg_roi_axis& a) {
-    if (v < -1.0f || v > (float)size) return false;
-    if (v <= 0.f) v = 0.f;
-    int low = (int)v, high;
-    if (low >= size - 1) { high = low = size - 1; v = (float)low; } else high = low + 1;
-    a.low = low; a.high = high;
-    a.l = v - low; a.h = 1.f - a.l;
-    return true;
-}
-
 // The taps of RoI `it` that land on pixel (py, px), in the contract's order: add(bin, wy * wx) per tap.
 template <class F>
 __device__ __forceinline__ void skg_roi_det_walk(const skg_roi_det_item& it, int H, int W, int pooled, int py, int px, F add) {
     for (int ph = 0; ph < pooled; ++ph)
         for (int iy = 0; iy < it.gh; ++iy) {
-            const float y = it.y1 + ph * it.bh + (iy + 0.5f) * it.bh / (float)it.gh;
+            const float y = skg_roi_coord(it.y1, ph, it.bh, iy, it.gh);
             skg_roi_axis ay;
             if (!skg_roi_axis_sample(H, y, ay)) continue;
             const bool yl = ay.low == py, yh = ay.high == py;
             if (!yl && !yh) continue;
             for (int pw = 0; pw < pooled; ++pw)
                 for (int ix = 0; ix < it.gw; ++ix) {
-                    const float x = it.x1 + pw * it.bw + (ix + 0.5f) * it.bw / (float)it.gw;
+                    const float x = skg_roi_coord(it.x1, pw, it.bw, ix, it.gw);
                     skg_roi_axis ax;
                     if (!skg_roi_axis_sample(W, x, ax)) continue;
                     const bool xl = ax.low == px, xh = ax.high == px;
@@ -608,10 +415,8 @@ __device__ __forceinline__ int skg_roi_det_list(const skg_roi_levels& L, const f
     if (r < n_rois && box_image[r] == b) {
         const skg_roi_geom g = skg_roi_box_geom(L, *reinterpret_cast<const float4*>(boxes + 4 * (int64_t)r), pooled, sampling);
         if (g.l == l) {
-            const float yf = g.y1 + 0 * g.bh + (0 + 0.5f) * g.bh / (float)g.gh;
-            const float ye = g.y1 + (pooled - 1) * g.bh + ((g.gh - 1) + 0.5f) * g.bh / (float)g.gh;
-            const float xf = g.x1 + 0 * g.bw + (0 + 0.5f) * g.bw / (float)g.gw;
-            const float xe = g.x1 + (pooled - 1) * g.bw + ((g.gw - 1) + 0.5f) * g.bw / (float)g.gw;
+            const float yf = skg_roi_coord(g.y1, 0, g.bh, 0, g.gh), ye = skg_roi_coord(g.y1, pooled - 1, g.bh, g.gh - 1, g.gh);
+            const float xf = skg_roi_coord(g.x1, 0, g.bw, 0, g.gw), xe = skg_roi_coord(g.x1, pooled - 1, g.bw, g.gw - 1, g.gw);
             hit = !(floorf(fmaxf(ye, 0.f)) + 2.f < (float)ty0) && !(floorf(fmaxf(yf, 0.f)) - 1.f > (float)ty1) &&
                   !(floorf(fmaxf(xe, 0.f)) + 2.f < (float)tx0) && !(floorf(fmaxf(xf, 0.f)) - 1.f > (float)tx1);
             it.r = r; it.gh = g.gh; it.gw = g.gw;
@@ -762,6 +567,169 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_nhwc_kernel(const s
     }
 }
 
+// ------------------------------------------------------------------------------------------------ entries
+// launches since the last reset: forward NCHW, forward NHWC, backward NCHW, backward NHWC (skg_roi_align_layout_counts)
+static std::atomic<long long> g_roi_layout_counts[4];
+
+extern "C" void skg_roi_align_layout_counts(int64_t* out4, int reset) {
+    for (int i = 0; i < 4; ++i) {
+        if (out4) out4[i] = g_roi_layout_counts[i].load(std::memory_order_relaxed);
+        if (reset) g_roi_layout_counts[i].store(0, std::memory_order_relaxed);
+    }
+}
+
+static int skg_roi_levels_fill(skg_roi_levels& L, const void* const* feats_host, const int32_t* H_host,
+                               const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                               float canonical_scale, int canonical_level) {
+    for (int l = 0; l < SKG_ROI_MAX_LEVELS; ++l) {
+        const bool in = l < n_levels;
+        L.feat[l] = in ? feats_host[l] : nullptr;
+        L.H[l] = in ? H_host[l] : 0; L.W[l] = in ? W_host[l] : 0; L.scale[l] = in ? scales_host[l] : 0.f;
+        if (in && (!L.feat[l] || L.H[l] <= 0 || L.W[l] <= 0)) return SKG_E_ARG;
+    }
+    L.n_levels = n_levels; L.k_min = k_min; L.k_max = k_max; L.C = C;
+    L.canonical_scale = canonical_scale; L.canonical_level = canonical_level;
+    return 0;
+}
+
+// The argument check of all five launching entries, in the order that decides which code wins; fills L.
+//   nhwc: the channels-last limits -- C % 8 and pooled <= SKG_ROI_NHWC_MAX_POOLED, `io` (out / dout) and every level base
+//         16-byte aligned;
+//   det:  a deterministic entry -- n_images is checked, and without a RoI it still launches (the maps are written), where
+//         the others have nothing to do; the level bases are left to its grid loop, which reports them level by level
+//         between the workgroup counts.
+//   dt0, dt1: the entry's dtype codes (an entry with one passes it twice, an fp32-only entry SKG_DTYPE_F32).
+// Returns SKG_E_* or 0; *nothing: 0 was returned because there is no RoI and the entry is not deterministic (no launch).
+static int skg_roi_check(bool nhwc, bool det, skg_roi_levels& L, const void* const* feats_host, int dt0, int dt1,
+                         const int32_t* H_host, const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                         int k_max, float canonical_scale, int canonical_level, const float* boxes, const int32_t* box_image,
+                         int n_rois, int n_images, int pooled, const void* io, bool* nothing) {
+    *nothing = false;
+    if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
+        return SKG_E_ARG;
+    if (dt0 < SKG_DTYPE_F32 || dt0 > SKG_DTYPE_BF16 || dt1 < SKG_DTYPE_F32 || dt1 > SKG_DTYPE_BF16) return SKG_E_ARG;
+    if (det && n_images <= 0) return SKG_E_ARG;
+    if (nhwc && ((C & 7) || pooled > SKG_ROI_NHWC_MAX_POOLED)) return SKG_E_ARG;     // 16-byte channel vectors; the LDS tile
+    if (n_rois == 0 && !det) { *nothing = true; return 0; }
+    if (!feats_host || !H_host || !W_host || !scales_host) return SKG_E_ARG;
+    if (n_rois > 0 && (!boxes || !box_image || !io)) return SKG_E_ARG;
+    if (n_rois > 0 && (!skg_aligned16(boxes) || (nhwc && !skg_aligned16(io)))) return SKG_E_ALIGN;
+    const int rc = skg_roi_levels_fill(L, feats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
+                                       canonical_level);
+    if (rc) return rc;
+    for (int l = 0; nhwc && !det && l < n_levels; ++l)
+        if (!skg_aligned16(L.feat[l])) return SKG_E_ALIGN;
+    return 0;
+}
+
+// f(std::integral_constant<int, dt>()) for a checked dtype code: the template argument of a kernel from a run-time value
+template <class F>
+static void skg_roi_with_dtype(int dt, F f) {
+    switch (dt) {
+        case SKG_DTYPE_F32: f(std::integral_constant<int, SKG_DTYPE_F32>()); break;
+        case SKG_DTYPE_F16: f(std::integral_constant<int, SKG_DTYPE_F16>()); break;
+        default: f(std::integral_constant<int, SKG_DTYPE_BF16>()); break;
+    }
+}
+
+// The four entries below: every check, the counter, one launch.
+
+// [B, C, H, W] kernels: one thread per output element, grid-stride beyond 256 * 64 workgroups
+static dim3 skg_roi_nchw_grid(int n_rois, int C, int pooled) {
+    return dim3((unsigned)std::min<int64_t>(((int64_t)n_rois * C * pooled * pooled + 255) / 256, 256 * 64));
+}
+
+extern "C" int skg_roi_align_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
+                               const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                               int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                               const int32_t* box_image, int n_rois, int pooled, int sampling, void* out, int out_dtype,
+                               void* stream) {
+    skg_roi_levels L;
+    bool nothing;
+    const int rc = skg_roi_check(false, false, L, feats_host, map_dtype, out_dtype, H_host, W_host, scales_host, n_levels, C,
+                                 k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois, 1, pooled, out, &nothing);
+    if (rc || nothing) return rc;
+    g_roi_layout_counts[0].fetch_add(1, std::memory_order_relaxed);
+    skg_roi_with_dtype(map_dtype, [&](auto m) {
+        skg_roi_with_dtype(out_dtype, [&](auto o) {
+            hipLaunchKernelGGL((skg_roi_align_kernel<decltype(m)::value, decltype(o)::value>), skg_roi_nchw_grid(n_rois, C, pooled),
+                               dim3(256), 0, (hipStream_t)stream, L, boxes, box_image, n_rois, pooled, sampling,
+                               static_cast<typename skg_roi_elem<decltype(o)::value>::T*>(out));
+        });
+    });
+    return skg_launch_status();
+}
+
+extern "C" int skg_roi_align_f32(const float* const* feats_host, const int32_t* H_host, const int32_t* W_host,
+                                 const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                 float canonical_scale, int canonical_level, const float* boxes,
+                                 const int32_t* box_image, int n_rois, int pooled, int sampling, float* out,
+                                 void* stream) {
+    return skg_roi_align_x(reinterpret_cast<const void* const*>(feats_host), SKG_DTYPE_F32, H_host, W_host, scales_host,
+                           n_levels, C, k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois,
+                           pooled, sampling, out, SKG_DTYPE_F32, stream);
+}
+
+extern "C" int skg_roi_align_bwd_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                                     const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                     float canonical_scale, int canonical_level, const float* boxes,
+                                     const int32_t* box_image, int n_rois, int pooled, int sampling, const float* dout,
+                                     void* stream) {
+    skg_roi_levels L;
+    bool nothing;
+    const int rc = skg_roi_check(false, false, L, reinterpret_cast<const void* const*>(dfeats_host), SKG_DTYPE_F32,
+                                 SKG_DTYPE_F32, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
+                                 canonical_level, boxes, box_image, n_rois, 1, pooled, dout, &nothing);
+    if (rc || nothing) return rc;
+    g_roi_layout_counts[2].fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(skg_roi_align_bwd_kernel, skg_roi_nchw_grid(n_rois, C, pooled), dim3(256), 0, (hipStream_t)stream,
+                       L, boxes, box_image, n_rois, pooled, sampling, dout);
+    return skg_launch_status();
+}
+
+// channels-last: one workgroup per (RoI, slab of SKG_ROI_NHWC_SLAB channels)
+extern "C" int skg_roi_align_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
+                                    const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                                    int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                                    const int32_t* box_image, int n_rois, int pooled, int sampling, void* out,
+                                    int out_dtype, void* stream) {
+    skg_roi_levels L;
+    bool nothing;
+    const int rc = skg_roi_check(true, false, L, feats_host, map_dtype, out_dtype, H_host, W_host, scales_host, n_levels, C,
+                                 k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois, 1, pooled, out, &nothing);
+    if (rc || nothing) return rc;
+    const int n_slabs = (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB;
+    if ((int64_t)n_rois * n_slabs > 0x7fffffffLL) return SKG_E_LIMIT;
+    g_roi_layout_counts[1].fetch_add(1, std::memory_order_relaxed);
+    skg_roi_with_dtype(map_dtype, [&](auto m) {
+        skg_roi_with_dtype(out_dtype, [&](auto o) {
+            hipLaunchKernelGGL((skg_roi_align_nhwc_kernel<decltype(m)::value, decltype(o)::value>), dim3((unsigned)(n_rois * n_slabs)),
+                               dim3(256), 0, (hipStream_t)stream, L, boxes, box_image, n_slabs, pooled, sampling,
+                               static_cast<typename skg_roi_elem<decltype(o)::value>::T*>(out));
+        });
+    });
+    return skg_launch_status();
+}
+
+extern "C" int skg_roi_align_bwd_nhwc_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                                          const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                          float canonical_scale, int canonical_level, const float* boxes,
+                                          const int32_t* box_image, int n_rois, int pooled, int sampling,
+                                          const float* dout, void* stream) {
+    skg_roi_levels L;
+    bool nothing;
+    const int rc = skg_roi_check(true, false, L, reinterpret_cast<const void* const*>(dfeats_host), SKG_DTYPE_F32,
+                                 SKG_DTYPE_F32, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
+                                 canonical_level, boxes, box_image, n_rois, 1, pooled, dout, &nothing);
+    if (rc || nothing) return rc;
+    const int n_slabs = (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB;
+    if ((int64_t)n_rois * n_slabs > 0x7fffffffLL) return SKG_E_LIMIT;
+    g_roi_layout_counts[3].fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(skg_roi_align_bwd_nhwc_kernel, dim3((unsigned)(n_rois * n_slabs)), dim3(256), 0, (hipStream_t)stream,
+                       L, boxes, box_image, n_slabs, pooled, sampling, dout);
+    return skg_launch_status();
+}
+
 // deterministic backward launches since the last reset: [B, C, H, W], channels-last (skg_roi_align_det_counts)
 static std::atomic<long long> g_roi_det_counts[2];
 
@@ -777,16 +745,11 @@ static int skg_roi_align_bwd_det(bool nhwc, void* const* dfeats_host, int grad_d
                                  const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
                                  float canonical_scale, int canonical_level, const float* boxes, const int32_t* box_image,
                                  int n_rois, int n_images, int pooled, int sampling, const float* dout, void* stream) {
-    if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
-        return SKG_E_ARG;
-    if (n_images <= 0 || grad_dtype < SKG_DTYPE_F32 || grad_dtype > SKG_DTYPE_BF16) return SKG_E_ARG;
-    if (nhwc && ((C & 7) || pooled > SKG_ROI_NHWC_MAX_POOLED)) return SKG_E_ARG;     // 16-byte channel vectors; the LDS tile
-    if (!dfeats_host || !H_host || !W_host || !scales_host) return SKG_E_ARG;
-    if (n_rois > 0 && (!boxes || !box_image || !dout)) return SKG_E_ARG;             // (no RoI: the maps are still written)
-    if (n_rois > 0 && (!skg_aligned16(boxes) || (nhwc && !skg_aligned16(dout)))) return SKG_E_ALIGN;
     skg_roi_levels L;
-    const int rc = skg_roi_levels_fill(L, reinterpret_cast<const void* const*>(dfeats_host), H_host, W_host, scales_host,
-                                       n_levels, C, k_min, k_max, canonical_scale, canonical_level);
+    bool nothing;
+    const int rc = skg_roi_check(nhwc, true, L, reinterpret_cast<const void* const*>(dfeats_host), grad_dtype, grad_dtype,
+                                 H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale, canonical_level, boxes,
+                                 box_image, n_rois, n_images, pooled, dout, &nothing);
     if (rc) return rc;
     skg_roi_det_grid G;
     const int tw = nhwc ? SKG_ROI_DET_NT : SKG_ROI_DET_TW, th = nhwc ? SKG_ROI_DET_NT : SKG_ROI_DET_TH;
@@ -804,15 +767,11 @@ static int skg_roi_align_bwd_det(bool nhwc, void* const* dfeats_host, int grad_d
     }
     G.start[SKG_ROI_MAX_LEVELS] = (unsigned)blocks;
     g_roi_det_counts[nhwc ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
-    hipStream_t s = (hipStream_t)stream;
-#define SKG_ROI_DET(K)                                                                                                  \
-    switch (grad_dtype) {                                                                                               \
-        case SKG_DTYPE_F32: hipLaunchKernelGGL((K<SKG_DTYPE_F32>), dim3((unsigned)blocks), dim3(256), 0, s, L, G, boxes, box_image, n_rois, pooled, sampling, dout); break; \
-        case SKG_DTYPE_F16: hipLaunchKernelGGL((K<SKG_DTYPE_F16>), dim3((unsigned)blocks), dim3(256), 0, s, L, G, boxes, box_image, n_rois, pooled, sampling, dout); break; \
-        default: hipLaunchKernelGGL((K<SKG_DTYPE_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, L, G, boxes, box_image, n_rois, pooled, sampling, dout); break;          \
-    }
-    if (nhwc) { SKG_ROI_DET(skg_roi_align_bwd_det_nhwc_kernel) } else { SKG_ROI_DET(skg_roi_align_bwd_det_kernel) }
-#undef SKG_ROI_DET
+    skg_roi_with_dtype(grad_dtype, [&](auto d) {
+        const dim3 grid((unsigned)blocks), wg(256);
+        if (nhwc) hipLaunchKernelGGL((skg_roi_align_bwd_det_nhwc_kernel<decltype(d)::value>), grid, wg, 0, (hipStream_t)stream, L, G, boxes, box_image, n_rois, pooled, sampling, dout);
+        else hipLaunchKernelGGL((skg_roi_align_bwd_det_kernel<decltype(d)::value>), grid, wg, 0, (hipStream_t)stream, L, G, boxes, box_image, n_rois, pooled, sampling, dout);
+    });
     return skg_launch_status();
 }
 

@@ -88,20 +88,10 @@ class _RoIAlignFn(torch.autograd.Function):
         n_rois, Cc = rois.shape[0], fs[0].shape[1]
         out = torch.empty(n_rois, Cc, pooled, pooled, device=rois.device, dtype=out_dtype)
         ptrs, Hs, Ws, sc = _level_args(fs, scales)
-        if nhwc:
-            _capi.check(_capi.lib().skg_roi_align_nhwc_x(ptrs, map_code, Hs, Ws, sc, len(fs), Cc, k_min, k_max,
-                                                         float(canon_s), int(canon_l), rois.data_ptr(), img.data_ptr(),
-                                                         n_rois, pooled, sampling, out.data_ptr(), _OUT_CODES[out_dtype],
-                                                         _stream()), "skg_roi_align_nhwc_x")
-        elif map_code == _capi.DTYPE_F32 and out_dtype == torch.float32:
-            _capi.check(_capi.lib().skg_roi_align_f32(ptrs, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s),
-                                                      int(canon_l), rois.data_ptr(), img.data_ptr(), n_rois, pooled,
-                                                      sampling, out.data_ptr(), _stream()), "skg_roi_align_f32")
-        else:
-            _capi.check(_capi.lib().skg_roi_align_x(ptrs, map_code, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s),
-                                                    int(canon_l), rois.data_ptr(), img.data_ptr(), n_rois, pooled,
-                                                    sampling, out.data_ptr(), _OUT_CODES[out_dtype], _stream()),
-                        "skg_roi_align_x")
+        name = "skg_roi_align_nhwc_x" if nhwc else "skg_roi_align_x"
+        _capi.check(getattr(_capi.lib(), name)(ptrs, map_code, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s),
+                                               int(canon_l), rois.data_ptr(), img.data_ptr(), n_rois, pooled, sampling,
+                                               out.data_ptr(), _OUT_CODES[out_dtype], _stream()), name)
         ctx.cfg, ctx.rois, ctx.img = cfg, rois, img
         ctx.shapes = [tuple(f.shape) for f in fs]
         ctx.dtypes = [f.dtype for f in feats]
@@ -113,35 +103,29 @@ class _RoIAlignFn(torch.autograd.Function):
     def backward(ctx, dout):
         scales, k_min, k_max, canon_s, canon_l, pooled, sampling = ctx.cfg[:7]
         dout = dout.float().contiguous()
+        fmt = torch.channels_last if ctx.nhwc else torch.contiguous_format    # gradients of channels-last maps stay so
+        one = len(set(ctx.dtypes)) == 1 and ctx.dtypes[0] in _OUT_CODES
         if ctx.det:                                 # every element written once, in a fixed order: uninitialised maps
-            one = len(set(ctx.dtypes)) == 1 and ctx.dtypes[0] in _OUT_CODES
             gdt = ctx.dtypes[0] if one else torch.float32           # mixed / fp64 maps: fp32 gradients, converted below
-            fmt = torch.channels_last if ctx.nhwc else torch.contiguous_format
-            dfs = [torch.empty(sh, device=dout.device, dtype=gdt, memory_format=fmt) for sh in ctx.shapes]
-            ptrs, Hs, Ws, sc = _level_args(dfs, scales)
             name = "skg_roi_align_bwd_det_nhwc_x" if ctx.nhwc else "skg_roi_align_bwd_det_x"
-            _capi.check(getattr(_capi.lib(), name)(ptrs, _OUT_CODES[gdt], Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min,
-                                                   k_max, float(canon_s), int(canon_l), ctx.rois.data_ptr(),
-                                                   ctx.img.data_ptr(), ctx.rois.shape[0], ctx.shapes[0][0], pooled,
-                                                   sampling, dout.data_ptr(), _stream()), name)
-            if one:
-                return (None, None, None) + tuple(dfs)
-            return (None, None, None) + tuple(d.to(t) for d, t in zip(dfs, ctx.dtypes))
-        if ctx.nhwc:                                # gradients of channels-last maps stay channels-last
-            dfs = [torch.empty(sh, device=dout.device, dtype=torch.float32, memory_format=torch.channels_last).zero_()
-                   for sh in ctx.shapes]
-            ptrs, Hs, Ws, sc = _level_args(dfs, scales)
-            _capi.check(_capi.lib().skg_roi_align_bwd_nhwc_f32(ptrs, Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min, k_max,
-                                                               float(canon_s), int(canon_l), ctx.rois.data_ptr(),
-                                                               ctx.img.data_ptr(), ctx.rois.shape[0], pooled, sampling,
-                                                               dout.data_ptr(), _stream()), "skg_roi_align_bwd_nhwc_f32")
-            return (None, None, None) + tuple(d.to(t) for d, t in zip(dfs, ctx.dtypes))
-        dfs = [torch.zeros(sh, device=dout.device, dtype=torch.float32) for sh in ctx.shapes]
+            dtype_arg, images_arg = (_OUT_CODES[gdt],), (ctx.shapes[0][0],)    # the two arguments only these entries take
+        else:                                       # float atomics into zeroed fp32 maps
+            gdt = torch.float32
+            name = "skg_roi_align_bwd_nhwc_f32" if ctx.nhwc else "skg_roi_align_bwd_f32"
+            dtype_arg, images_arg = (), ()
+        if ctx.det:
+            dfs = [torch.empty(sh, device=dout.device, dtype=gdt, memory_format=fmt) for sh in ctx.shapes]
+        elif ctx.nhwc:
+            dfs = [torch.empty(sh, device=dout.device, dtype=gdt, memory_format=fmt).zero_() for sh in ctx.shapes]
+        else:
+            dfs = [torch.zeros(sh, device=dout.device, dtype=gdt) for sh in ctx.shapes]
         ptrs, Hs, Ws, sc = _level_args(dfs, scales)
-        _capi.check(_capi.lib().skg_roi_align_bwd_f32(ptrs, Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min, k_max,
-                                                      float(canon_s), int(canon_l), ctx.rois.data_ptr(), ctx.img.data_ptr(),
-                                                      ctx.rois.shape[0], pooled, sampling, dout.data_ptr(), _stream()),
-                    "skg_roi_align_bwd_f32")
+        _capi.check(getattr(_capi.lib(), name)(ptrs, *dtype_arg, Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min, k_max,
+                                               float(canon_s), int(canon_l), ctx.rois.data_ptr(), ctx.img.data_ptr(),
+                                               ctx.rois.shape[0], *images_arg, pooled, sampling, dout.data_ptr(),
+                                               _stream()), name)
+        if ctx.det and one:
+            return (None, None, None) + tuple(dfs)
         return (None, None, None) + tuple(d.to(t) for d, t in zip(dfs, ctx.dtypes))
 
 

@@ -48,37 +48,103 @@ def _bwd(lib, p, H, W, sc, n_levels=1, Cc=8, k_min=0, k_max=0, boxes=16, img=16,
                                           dout, None)
 
 
-@pytest.mark.parametrize("call", [_fwd, _bwd], ids=["forward", "backward"])
+def _fwd_nchw(lib, p, H, W, sc, n_levels=1, Cc=8, k_min=0, k_max=0, boxes=16, img=16, n_rois=2, pooled=7, out=16, map_dt=2,
+              out_dt=2):
+    return lib.skg_roi_align_x(p, map_dt, H, W, sc, n_levels, Cc, k_min, k_max, 224.0, 4, boxes, img, n_rois, pooled, 2, out,
+                               out_dt, None)
+
+
+def _fwd_nchw_f32(lib, p, H, W, sc, n_levels=1, Cc=8, k_min=0, k_max=0, boxes=16, img=16, n_rois=2, pooled=7, out=16):
+    return lib.skg_roi_align_f32(p, H, W, sc, n_levels, Cc, k_min, k_max, 224.0, 4, boxes, img, n_rois, pooled, 2, out, None)
+
+
+def _bwd_nchw(lib, p, H, W, sc, n_levels=1, Cc=8, k_min=0, k_max=0, boxes=16, img=16, n_rois=2, pooled=7, dout=16):
+    return lib.skg_roi_align_bwd_f32(p, H, W, sc, n_levels, Cc, k_min, k_max, 224.0, 4, boxes, img, n_rois, pooled, 2, dout,
+                                     None)
+
+
+E_ARG, E_ALIGN = -1, -2
+
+
+@pytest.mark.parametrize("call", [_fwd, _bwd, _fwd_nchw, _fwd_nchw_f32, _bwd_nchw],
+                         ids=["forward", "backward", "nchw_x", "nchw_f32", "nchw_backward"])
 def test_nhwc_entries_reject_before_any_gpu_call(lib, call):
+    """Every row returns before a launch: the level, boxes and out addresses are fake.  A row that the [B, C, H, W] entries
+    accept (C % 8, pooled = 9, a misaligned level or out / dout) would launch there, so it is asked of them with
+    n_rois = 0 only, where it must return 0."""
+    nhwc = call in (_fwd, _bwd)
+    fwd = call in (_fwd, _fwd_nchw, _fwd_nchw_f32)
+    last = "out" if fwd else "dout"
     p, H, W, sc = _levels(1)
-    last = "out" if call is _fwd else "dout"
-    for Cc in (6, 12, 0, -8):
-        assert call(lib, p, H, W, sc, Cc=Cc) < 0, Cc
+    before = (C.c_int64 * 4)()
+    lib.skg_roi_align_layout_counts(before, 0)
+    for Cc in (6, 12):
+        if nhwc:
+            assert call(lib, p, H, W, sc, Cc=Cc) == E_ARG, Cc
+        assert call(lib, p, H, W, sc, Cc=Cc, n_rois=0) == (E_ARG if nhwc else 0), Cc   # the limit comes before "no RoI"
+    for Cc in (0, -8):
+        assert call(lib, p, H, W, sc, Cc=Cc) == E_ARG, Cc
+        assert call(lib, p, H, W, sc, Cc=Cc, n_rois=0) == E_ARG, Cc
     p8 = _levels(1, base=8)[0]
-    assert call(lib, p8, H, W, sc) == -2                               # a level base at address 8: SKG_E_ALIGN
     p4 = _levels(4)
     bad = (C.c_void_p * 4)(16, 32, 40, 64)                             # a later level misaligned
-    assert call(lib, bad, *p4[1:], n_levels=4, k_min=2, k_max=5) == -2
-    assert call(lib, p, H, W, sc, boxes=8) == -2
-    assert call(lib, p, H, W, sc, **{last: 8}) == -2
+    if nhwc:
+        assert call(lib, p8, H, W, sc) == E_ALIGN                      # a level base at address 8: SKG_E_ALIGN
+        assert call(lib, bad, *p4[1:], n_levels=4, k_min=2, k_max=5) == E_ALIGN
+        assert call(lib, p, H, W, sc, **{last: 8}) == E_ALIGN
+        assert call(lib, p, H, W, sc, pooled=9) == E_ARG               # 9: beyond the LDS tile
+    assert call(lib, p8, H, W, sc, n_rois=0) == 0                      # no RoI: the levels are not looked at
+    assert call(lib, p, H, W, sc, n_rois=0, **{last: 8}) == 0
+    assert call(lib, p, H, W, sc, pooled=9, n_rois=0) == (E_ARG if nhwc else 0)
+    assert call(lib, p, H, W, sc, boxes=8) == E_ALIGN
+    assert call(lib, p, H, W, sc, boxes=8, n_rois=0) == 0
     p9 = _levels(9)
-    assert call(lib, p, H, W, sc, n_levels=0, k_min=0, k_max=-1) < 0
-    assert call(lib, *p9, n_levels=9, k_min=0, k_max=8) < 0
-    assert call(lib, *p4, n_levels=4, k_min=2, k_max=4) < 0           # k_max - k_min + 1 != n_levels
-    assert call(lib, *p4, n_levels=4, k_min=2, k_max=6) < 0
-    for pooled in (0, -1, 9):                                          # 9: beyond the LDS tile
-        assert call(lib, p, H, W, sc, pooled=pooled) < 0, pooled
-    assert call(lib, None, H, W, sc) < 0
-    assert call(lib, p, None, W, sc) < 0
-    assert call(lib, p, H, None, sc) < 0
-    assert call(lib, p, H, W, None) < 0
-    assert call(lib, p, H, W, sc, boxes=None) < 0
-    assert call(lib, p, H, W, sc, img=None) < 0
-    assert call(lib, p, H, W, sc, **{last: None}) < 0
-    assert call(lib, (C.c_void_p * 1)(None), H, W, sc) < 0             # a null level
-    assert call(lib, p, H, W, sc, n_rois=-1) < 0
+    assert call(lib, p, H, W, sc, n_levels=0, k_min=0, k_max=-1) == E_ARG
+    assert call(lib, *p9, n_levels=9, k_min=0, k_max=8) == E_ARG
+    assert call(lib, *p4, n_levels=4, k_min=2, k_max=4) == E_ARG       # k_max - k_min + 1 != n_levels
+    assert call(lib, *p4, n_levels=4, k_min=2, k_max=6) == E_ARG
+    assert call(lib, *p4, n_levels=4, k_min=2, k_max=4, n_rois=0) == E_ARG
+    for pooled in (0, -1):
+        assert call(lib, p, H, W, sc, pooled=pooled) == E_ARG, pooled
+        assert call(lib, p, H, W, sc, pooled=pooled, n_rois=0) == E_ARG, pooled
+    assert call(lib, None, H, W, sc) == E_ARG
+    assert call(lib, p, None, W, sc) == E_ARG
+    assert call(lib, p, H, None, sc) == E_ARG
+    assert call(lib, p, H, W, None) == E_ARG
+    assert call(lib, p, H, W, sc, boxes=None) == E_ARG
+    assert call(lib, p, H, W, sc, img=None) == E_ARG
+    assert call(lib, p, H, W, sc, **{last: None}) == E_ARG
+    null_level = (C.c_void_p * 1)(None)
+    assert call(lib, null_level, H, W, sc) == E_ARG                    # a null level
+    bad_hw = (C.c_int32 * 1)(0)
+    assert call(lib, p, bad_hw, W, sc) == E_ARG and call(lib, p, H, bad_hw, sc) == E_ARG
+    # several conditions at once: a null pointer wins over a misaligned one, the boxes' alignment over a level's contents
+    assert call(lib, p, None, W, sc, boxes=8) == E_ARG
+    assert call(lib, p, H, W, sc, boxes=8, **{last: None}) == E_ARG
+    assert call(lib, null_level, H, W, sc, boxes=8) == E_ALIGN
+    assert call(lib, p, bad_hw, W, sc, boxes=8) == E_ALIGN
+    assert call(lib, p8, H, W, sc, boxes=8, Cc=0) == E_ARG
+    if nhwc:
+        assert call(lib, null_level, H, W, sc, **{last: 8}) == E_ALIGN
+        assert call(lib, bad, p4[1], (C.c_int32 * 4)(8, 8, 8, 0), p4[3], n_levels=4, k_min=2, k_max=5) == E_ARG
+    assert call(lib, None, None, None, None, boxes=None, img=None, n_rois=0, **{last: None}) == 0
+    assert call(lib, p, H, W, sc, n_rois=-1) == E_ARG
     assert call(lib, p, H, W, sc, n_rois=0) == 0
     assert call(lib, *p4, n_levels=4, k_min=2, k_max=5, n_rois=0) == 0
+    after = (C.c_int64 * 4)()
+    lib.skg_roi_align_layout_counts(after, 0)
+    assert list(after) == list(before)                                 # nothing was launched
+
+
+def test_nchw_forward_rejects_unknown_dtypes(lib):
+    p, H, W, sc = _levels(1)
+    for map_dt, out_dt in ((3, 0), (-1, 0), (0, 3), (2, -1)):
+        assert _fwd_nchw(lib, p, H, W, sc, map_dt=map_dt, out_dt=out_dt) == E_ARG
+        assert _fwd_nchw(lib, p, H, W, sc, map_dt=map_dt, out_dt=out_dt, n_rois=0) == E_ARG
+        assert _fwd_nchw(lib, p, H, W, sc, map_dt=map_dt, out_dt=out_dt, boxes=8) == E_ARG
+    for map_dt in range(3):
+        for out_dt in range(3):
+            assert _fwd_nchw(lib, p, H, W, sc, map_dt=map_dt, out_dt=out_dt, n_rois=0) == 0
 
 
 def test_nhwc_forward_rejects_unknown_dtypes(lib):

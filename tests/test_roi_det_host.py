@@ -12,7 +12,7 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign, resolve_deterministic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("skg_roi_align_bwd_det_x", "skg_roi_align_bwd_det_nhwc_x", "skg_roi_align_det_counts")
-E_ARG, E_ALIGN = -1, -2
+E_ARG, E_ALIGN, E_LIMIT = -1, -2, -3
 
 
 @pytest.fixture(scope="module")
@@ -94,6 +94,13 @@ def test_det_entries_reject_before_any_gpu_call(lib, name):
     assert call(p, H, W, sc, n_rois=-1) == E_ARG
     bad_hw = (C.c_int32 * 1)(0)
     assert call(p, bad_hw, W, sc) == E_ARG and call(p, H, bad_hw, sc) == E_ARG
+    # more than 2^31 - 1 workgroups, reached at level 1: reported before a misaligned level 2 is looked at, after level 0
+    big = dict(n_levels=4, k_min=2, k_max=5, n_images=2 ** 31 - 1)
+    assert call(*p4, **big) == E_LIMIT
+    if nhwc:
+        assert call((C.c_void_p * 4)(16, 32, 40, 64), *p4[1:], **big) == E_LIMIT
+        assert call((C.c_void_p * 4)(8, 32, 48, 64), *p4[1:], **big) == E_ALIGN
+    assert call(*p4, boxes=8, **big) == E_ALIGN
     assert _det_counts(lib) == [0, 0]                                  # a rejected call counts nothing
 
 

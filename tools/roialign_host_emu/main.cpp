@@ -2,7 +2,9 @@
 // stand-in for the HIP runtime), so that AddressSanitizer / UBSan see every map, output and LDS-tile access.  Compares the
 // channels-last entries against the [B, C, H, W] entries on the same values: forward outputs byte for byte (nine dtype
 // pairs), fp32 gradients within 2e-5; and the two deterministic backward kernels byte for byte against a sequential loop
-// written here (run_det below).  Shapes and boxes of tests/test_half_features_gpu.py::_roi_inputs.  No GPU involved.
+// written here (run_det below).  Every case prints FNV-1a digests of its forward outputs / deterministic gradients: the
+// logs of two builds (-I a directory holding another skg_roialign.hip first) must agree line for line.  Shapes and boxes
+// of tests/test_half_features_gpu.py::_roi_inputs.  No GPU involved.
 //
 //   cd tools/roialign_host_emu && clang++ -x c++ -std=c++20 -O1 -g -ffp-contract=off -fsanitize=address,undefined -pthread \
 //       -I. -I../../skghoi_amd/csrc -I../../include main.cpp -o emu && ./emu        (a few minutes: 256 threads per workgroup)
@@ -13,6 +15,12 @@
 #include <random>
 thread_local dim3 threadIdx, blockIdx, gridDim;
 std::barrier<>* g_barrier;
+
+// 64-bit FNV-1a over a buffer (chained through h): printed per case, so that two builds of the kernels can be compared
+static uint64_t fnv1a(const void* p, size_t n, uint64_t h = 0xcbf29ce484222325ull) {
+    for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const unsigned char*>(p)[i]) * 0x100000001b3ull;
+    return h;
+}
 
 static uint16_t to_bf16(float v) { uint32_t u = __float_as_uint(v); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }
 
@@ -52,6 +60,7 @@ static int run(int map_dt, int Cc, int L0, int L, int pooled, int sampling) {
     const int kmin = L > 1 ? 2 + L0 : 0, kmax = L > 1 ? kmin + L - 1 : 0;
     const size_t no = (size_t)8 * Cc * pooled * pooled;
     int bad = 0;
+    unsigned long long dig[2][3];
     for (int odt = 0; odt < 3; ++odt) {
         const size_t es = odt == 0 ? 4 : 2;
         void* o1 = aligned_alloc(16, (no * es + 15) / 16 * 16); void* o2 = aligned_alloc(16, (no * es + 15) / 16 * 16);
@@ -59,8 +68,11 @@ static int run(int map_dt, int Cc, int L0, int L, int pooled, int sampling) {
         int r1 = skg_roi_align_x((const void* const*)nchw.data(), map_dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, 8, pooled, sampling, o1, odt, nullptr);
         int r2 = skg_roi_align_nhwc_x((const void* const*)nhwc.data(), map_dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, 8, pooled, sampling, o2, odt, nullptr);
         if (r1 || r2 || memcmp(o1, o2, no * es)) { printf("  MISMATCH fwd mdt %d odt %d C %d L %d pooled %d samp %d rc %d %d\n", map_dt, odt, Cc, L, pooled, sampling, r1, r2); ++bad; }
+        dig[0][odt] = fnv1a(o1, no * es); dig[1][odt] = fnv1a(o2, no * es);
         free(o1); free(o2);
     }
+    printf("  fwd mdt %d C %d L %d pooled %d samp %d: digests %016llx %016llx %016llx, channels-last %016llx %016llx %016llx\n", map_dt,
+           Cc, L, pooled, sampling, dig[0][0], dig[0][1], dig[0][2], dig[1][0], dig[1][1], dig[1][2]);
     if (map_dt == 0) {
         float* dout = (float*)aligned_alloc(16, (no * 4 + 15) / 16 * 16);
         for (size_t i = 0; i < no; ++i) dout[i] = nd(rng);
@@ -175,9 +187,14 @@ static int run_det(int dt, int Cc, int L0, int L, int pooled, int sampling, int 
             nonzero += rv != 0.f; img1 += b == 1 && rv != 0.f;
         }
     int levels = 0;
-    for (int l = 0; l < L; ++l) levels += used[l] > 0;
-    printf("  det dt %d C %d L %d pooled %d samp %d rois %d far %d: rc %d %d, differing elements %zu %zu, nonzero %zu, levels used %d\n",
-           dt, Cc, L, pooled, sampling, n_rois, far_image, r1, r2, d1, d2, nonzero, levels);
+    uint64_t h1 = fnv1a(nullptr, 0), h2 = h1;
+    for (int l = 0; l < L; ++l) {
+        levels += used[l] > 0;
+        const size_t n = (size_t)B * Cc * H[l] * W[l] * sizeof(T);
+        h1 = fnv1a(g_nchw[l], n, h1); h2 = fnv1a(g_nhwc[l], n, h2);
+    }
+    printf("  det dt %d C %d L %d pooled %d samp %d rois %d far %d: rc %d %d, differing elements %zu %zu, nonzero %zu, levels used %d, digests %016llx %016llx\n",
+           dt, Cc, L, pooled, sampling, n_rois, far_image, r1, r2, d1, d2, nonzero, levels, (unsigned long long)h1, (unsigned long long)h2);
     const bool covered = n_rois == 0 ? nonzero == 0 : (nonzero > 0 && levels == L);
     for (int l = 0; l < L; ++l) { free(g_nchw[l]); free(g_nhwc[l]); }
     free(boxes); free(img); free(dout);

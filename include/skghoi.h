@@ -972,6 +972,50 @@ double skg_train_flops(const skg_train_plan* plan_host, int which);
 /* Offset (floats) of a saved activation inside ws, for tests: 0 enc, 1 h_node, 2 node, 3 adjacency logits, 4 raw fc_2.   */
 int64_t skg_train_ws_offset(const skg_train_plan* plan_host, int which);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Batch gather out of a feature set that is RESIDENT in device memory (skghoi_amd/resident.py): the payload of the
+ * feature shards, their global features, the raw detections and the targets, each kept as one ragged array -- rows in
+ * storage order plus an offset table, image i owning rows src_off[i] .. src_off[i + 1] -- and every batch of a sampler's
+ * order assembled from them by ONE launch: no host copy, no pinned buffer, no synchronisation, no allocation, no atomics.
+ *
+ * For slot b in 0 .. batch - 1 the image is i = order[first + b]; in every array the rows of image i go to dst, starting at
+ * row (rows of slots 0 .. b - 1 of that array).  An image may fill several slots of one batch (a sampler pads by wrapping):
+ * the launch only reads the set.  `order` is trusted: the host validates it once per epoch, every entry in 0 .. n_images - 1.
+ *
+ * src_dtype / dst_dtype: SKG_DTYPE_F32 / _F16 / _BF16, or SKG_DTYPE_BYTES for rows of row_elems opaque bytes (an int64
+ * label is 8 of them).  same -> same moves the stored bits; F16 -> F32 and BF16 -> F32 (bits << 16) widen exactly; any
+ * other pair is SKG_E_ARG.  dst_rows is the host's row count of this batch: a row at or behind it is not written, so dst
+ * needs room for dst_rows rows and no more, whatever the tables say.
+ *
+ * Kernel: 256-lane workgroups, at most 2048 of them.  Each first builds, in LDS, the prefix table of every array over the
+ * batch's slots (SKG_CACHE_MAX_ARRAYS x (SKG_CACHE_MAX_BATCH + 1) int32), then takes tiles of 256 consecutive pieces of one
+ * array in a grid-stride loop; a lane finds its piece's row and, by binary search in the table, the slot and source row.
+ * A piece is 16 bytes of the source row -- one 16-byte load and one (copy) or two (widening) 16-byte stores, so a tile is
+ * 4 KB read -- when the row's byte length and both base addresses are multiples of 16 (the real row: 12 544 bf16 =
+ * 1568 x 16 B); otherwise the largest of 8 / 4 / 2 / 1 bytes that divides them (copy) or one element (widening).  Only
+ * plain vector stores.
+ * Errors, before any launch: SKG_E_ARG for a null pointer (arrays, order, any src / src_off / dst), n_arrays outside
+ * 1 .. SKG_CACHE_MAX_ARRAYS, batch outside 1 .. SKG_CACHE_MAX_BATCH, first < 0, first + batch > order_len, row_elems < 1,
+ * dst_rows < 0, a dtype code outside 0 .. 3 or an unsupported pair; SKG_E_ALIGN for typed rows not aligned to their
+ * element; SKG_E_LIMIT for more than 2^31 - 1 rows in one array of the batch.  A batch without a row launches nothing.  */
+#define SKG_DTYPE_BYTES 3
+#define SKG_CACHE_MAX_ARRAYS 16
+#define SKG_CACHE_MAX_BATCH  256
+typedef struct {
+    const void*    src;         /* rows in storage order                                                              */
+    const int64_t* src_off;     /* [n_images + 1] row offsets                                                          */
+    int64_t        row_elems;   /* elements per row (bytes for SKG_DTYPE_BYTES)                                        */
+    int32_t        src_dtype;
+    int32_t        reserved;
+    void*          dst;
+    int32_t        dst_dtype;
+    int32_t        reserved2;
+    int64_t        dst_rows;    /* rows of this batch, computed on the host: the bound of every store                  */
+} skg_cache_array;
+int skg_cache_gather_x(const skg_cache_array* arrays_host, int n_arrays, const int32_t* order, int64_t order_len,
+                       int64_t first, int batch, void* stream);
+int skg_sizeof_cache_array(void);                                   /* sizeof(skg_cache_array): for bindings that mirror it */
+
 #ifdef __cplusplus
 }
 #endif

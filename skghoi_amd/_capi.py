@@ -8,6 +8,8 @@ LIB_PATH = os.environ.get("SKG_LIB") or os.path.join(_HERE, "csrc", "libskghoi_h
 
 EPI_BIAS, EPI_BIAS_RELU, EPI_MUL_RELU, EPI_RELU_DOT, EPI_BIAS_RES_RELU = range(5)
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(3)          # SKG_DTYPE_*: skg_roi_align_x, the feature shard's dtype field
+DTYPE_BYTES = 3                                      # SKG_DTYPE_BYTES: opaque rows (skg_cache_gather_x only)
+CACHE_MAX_ARRAYS, CACHE_MAX_BATCH = 16, 256          # SKG_CACHE_MAX_*
 MAX_DET_PER_IMAGE = 1024
 MAX_NODES = 160
 SPATIAL_LD = 48
@@ -86,6 +88,12 @@ class StepStatus(C.Structure):
     _fields_ = [("total_norm", _f32), ("coef", _f32), ("applied", _i32), ("reserved", _i32),
                 ("steps_applied", _i64), ("steps_skipped", _i64), ("steps_clipped", _i64),
                 ("max_total_norm", _f32), ("reserved2", _i32), ("pending_skips", _i64 * 2)]
+
+
+class CacheArray(C.Structure):
+    """Mirror of skg_cache_array: one ragged array of a resident feature set and where its rows of a batch go."""
+    _fields_ = [("src", _vp), ("src_off", _vp), ("row_elems", _i64), ("src_dtype", _i32), ("reserved", _i32),
+                ("dst", _vp), ("dst_dtype", _i32), ("reserved2", _i32), ("dst_rows", _i64)]
 
 
 class Tuning(C.Structure):
@@ -262,6 +270,8 @@ PROTOTYPES = {
     "skg_ctx_train_backward_progress": (C.c_int, [_vp]),
     "skg_train_ws_offset": (C.c_int64, [C.POINTER(TrainPlan), C.c_int]),
     "skg_train_flops": (C.c_double, [C.POINTER(TrainPlan), C.c_int]),
+    "skg_cache_gather_x": (C.c_int, [C.POINTER(CacheArray), C.c_int, _vp, _i64, _i64, C.c_int, _vp]),
+    "skg_sizeof_cache_array": (C.c_int, []),
 }
 
 _LIB = None
@@ -288,6 +298,8 @@ def lib():
         raise SkgError("skg_exchange is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_exchange(), C.sizeof(Exchange)))
     if l.skg_abi_version() == ABI_VERSION and l.skg_sizeof_step_status() != C.sizeof(StepStatus):
         raise SkgError("skg_step_status is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_step_status(), C.sizeof(StepStatus)))
+    if l.skg_abi_version() == ABI_VERSION and l.skg_sizeof_cache_array() != C.sizeof(CacheArray):
+        raise SkgError("skg_cache_array is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_cache_array(), C.sizeof(CacheArray)))
     if l.skg_abi_version() != ABI_VERSION:
         raise SkgError("libskghoi_hip.so ABI %d != binding ABI %d" % (l.skg_abi_version(), ABI_VERSION))
     _LIB = l

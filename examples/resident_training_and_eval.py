@@ -6,6 +6,11 @@
   Trainer epoch over `loader(batch_size=4)`: every batch is one device gather in DistributedSampler order -> one
   `trainer.test` pass over `loader(batch_size=1, shuffle=False)` into the device evaluator.
 
+With --flip the producer also writes the horizontally flipped variant of every training shard from the same maps
+(`produce_shard(..., mirror=True)`: the maps are read mirrored, nothing is copied but the coarsest level), the set holds both
+variants and the epoch serves one per image by the reference's coins -- `trainer.draw_flips(n)`, drawn once.  This is the
+flip of `trainer.hflip_sample` (the cached maps mirrored, the boxes with them), not the backbone run on the mirrored image.
+
 The companion of cached_inference_and_eval.py, which reads its shards batch by batch through FeatureShard.
 """
 import argparse
@@ -25,7 +30,7 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16"):
+def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=False):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_resident_")
     o2v = synth.hico_object_to_verb()
@@ -46,7 +51,7 @@ def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16"):
     shapes = [(H, W)] * n_images
     to_dev = lambda ds: [{k: v.to(dev) for k, v in d.items()} for d in ds]
     # ---- producer: one pass over the feature maps, a training-mode and an eval-mode shard per chunk (the kept rows differ)
-    shards = {"train": [], "eval": []}
+    shards = {"train": [], "eval": [], "train_flipped": []}
     for lo in range(0, n_images, per_shard):
         hi = min(n_images, lo + per_shard)
         feats = OrderedDict((str(l), torch.randn(hi - lo, 256, H // s, W // s, generator=g).to(dev))
@@ -57,15 +62,24 @@ def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16"):
             cache.produce_shard(head, feats, to_dev(raw[lo:hi]), shapes[lo:hi], path, dtype=dtype,
                                 targets=to_dev(targets[lo:hi]) if mode == "train" else None)
             shards[mode].append(path)
+        if flip:                                                        # the flipped variant of the training shard
+            head.train()
+            path = os.path.join(out_dir, "train_flipped_%04d.skgfc" % lo)
+            cache.produce_shard(head, feats, to_dev(raw[lo:hi]), shapes[lo:hi], path, dtype=dtype,
+                                targets=to_dev(targets[lo:hi]), mirror=True)
+            shards["train_flipped"].append(path)
     head.box_roi_pool = resident.BatchPool()
     # ---- one training epoch from the resident set
-    train_set = resident.ResidentFeatureSet(shards["train"], raw, targets, device=dev)
+    train_set = resident.ResidentFeatureSet(shards["train"], raw, targets, device=dev,
+                                            flipped_shard_paths=shards["train_flipped"] if flip else None)
     head.train()
-    train_set.check_alignment(head)
+    train_set.check_alignment(head)                                     # (both variants when there are two)
     net = trainer.wrap_ddp(head, dev)
     opt = trainer.build_optimizer(net, lr=1e-4)
     torch.manual_seed(seed)
-    tr = trainer.Trainer(net, opt, None, train_set.loader(batch_size=4, shuffle=True, seed=seed), lazy_losses=True)
+    coins = trainer.draw_flips(n_images) if flip else None              # DataFactory._flip: one coin per sample, drawn once
+    tr = trainer.Trainer(net, opt, None, train_set.loader(batch_size=4, shuffle=True, seed=seed, flips=coins),
+                         lazy_losses=True)
     tr.train_epoch()
     # ---- one evaluation pass from the resident set
     eval_set = resident.ResidentFeatureSet(shards["eval"], raw, eval_targets, device=dev)
@@ -77,6 +91,8 @@ def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16"):
             num_gt[h] += 1
     summ = trainer.test(head, eval_set.loader(batch_size=1, shuffle=False), evaluate.DeviceHOIEvaluator(num_gt, lut, device=dev),
                         device=dev)
+    if flip:
+        print("flipped images this epoch: %d of %d" % (int(coins.sum()), n_images))
     print("images %d, arena %.1f MB (%s) + %.1f MB, %d training steps, last losses %s, mAP over classes with GT: %.4f, cache dir %s"
           % (n_images, train_set.arena_bytes / 1e6, dtype, eval_set.arena_bytes / 1e6, tr.iteration,
              {k: round(v, 4) for k, v in tr.history[-1].items()},
@@ -90,5 +106,6 @@ if __name__ == "__main__":
     ap.add_argument("--per-shard", type=int, default=8)
     ap.add_argument("--dtype", default="bf16", choices=["fp32", "fp16", "bf16"])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--flip", action="store_true", help="produce both variants and train with the reference's fixed coins")
     a = ap.parse_args()
-    main(a.images, a.per_shard, a.out, dtype=a.dtype)
+    main(a.images, a.per_shard, a.out, dtype=a.dtype, flip=a.flip)

@@ -211,6 +211,47 @@ int skg_roi_align_bwd_det_nhwc_x(void* const* dfeats_host, int grad_dtype, const
 /* Statistics: deterministic backward launches since the last reset -- out2 = [B,C,H,W], channels-last.  They do not count
  * in skg_roi_align_layout_counts; reset != 0 zeroes them after the read.                                            */
 void skg_roi_align_det_counts(int64_t out2[2], int reset);
+/* MIRRORED images: the six entries above with per-image mirror flags.  image_mirror is a DEVICE array of n_images int32
+ * (nonzero: mirrored) or null.  For a RoI of a mirrored image the kernels address column W_l - 1 - x wherever they address
+ * column x -- both x taps of every sample, on the RoI's level; the sampling coordinates, the outside test, the clamps, the
+ * four weights and the order of every sum are untouched.  So the forward has the bits of the plain entry on a copy of the maps
+ * whose flagged images are mirrored along W, the deterministic backward the bits of the plain one on that copy mirrored back
+ * (its summation order holds in the mirrored frame), and the atomics backward adds the same products at the mirrored
+ * addresses.  The boxes are in the frame of the mirrored maps.  box_image values must lie in [0, n_images).
+ * A null image_mirror launches exactly what the entry without flags launches (which forwards here); the same checks in the
+ * same order with the same codes, plus: a non-null image_mirror with n_images <= 0 is SKG_E_ARG.  The launches count in
+ * skg_roi_align_layout_counts / skg_roi_align_det_counts like those of the entries without flags.  The deterministic
+ * signatures carry n_images already: they gain the flags alone.                                                        */
+int skg_roi_align_mirror_x(const void* const* feats_host, int map_dtype, const int32_t* H_host, const int32_t* W_host,
+                           const float* scales_host, int n_levels, int C, int k_min, int k_max, float canonical_scale,
+                           int canonical_level, const float* boxes, const int32_t* box_image, int n_rois, int pooled,
+                           int sampling, void* out, int out_dtype, const int32_t* image_mirror, int n_images,
+                           void* stream);
+int skg_roi_align_mirror_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
+                                const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                float canonical_scale, int canonical_level, const float* boxes, const int32_t* box_image,
+                                int n_rois, int pooled, int sampling, void* out, int out_dtype,
+                                const int32_t* image_mirror, int n_images, void* stream);
+int skg_roi_align_bwd_mirror_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                                 const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                 float canonical_scale, int canonical_level, const float* boxes,
+                                 const int32_t* box_image, int n_rois, int pooled, int sampling, const float* dout,
+                                 const int32_t* image_mirror, int n_images, void* stream);
+int skg_roi_align_bwd_mirror_nhwc_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                                      const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                      float canonical_scale, int canonical_level, const float* boxes,
+                                      const int32_t* box_image, int n_rois, int pooled, int sampling, const float* dout,
+                                      const int32_t* image_mirror, int n_images, void* stream);
+int skg_roi_align_bwd_det_mirror_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host, const int32_t* W_host,
+                                   const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                   float canonical_scale, int canonical_level, const float* boxes,
+                                   const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling,
+                                   const float* dout, const int32_t* image_mirror, void* stream);
+int skg_roi_align_bwd_det_mirror_nhwc_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host,
+                                        const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                                        int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                                        const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling,
+                                        const float* dout, const int32_t* image_mirror, void* stream);
 
 /* AdaptiveAvgPool2d(1) of features['3'] (HEAD:811): in [B, C, HW] -> out [B, C]. */
 int skg_global_avgpool_f32(const float* in, int B, int C, int HW, float* out, void* stream);

@@ -157,6 +157,23 @@ PROTOTYPES = {
     "skg_roi_align_bwd_det_nhwc_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32,
                                                C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "skg_roi_align_det_counts": (None, [C.POINTER(_i64), C.c_int]),
+    # the mirrored siblings: the signature above + (image_mirror, n_images) before the stream; the deterministic ones,
+    # which carry n_images already, + image_mirror
+    "skg_roi_align_mirror_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, C.c_int,
+                                         _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "skg_roi_align_mirror_nhwc_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32,
+                                              C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                              _vp]),
+    "skg_roi_align_bwd_mirror_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32, C.c_int,
+                                               _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "skg_roi_align_bwd_mirror_nhwc_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32,
+                                                    C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int,
+                                                    _vp]),
+    "skg_roi_align_bwd_det_mirror_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32,
+                                                 C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "skg_roi_align_bwd_det_mirror_nhwc_x": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      _f32, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                                      _vp, _vp]),
     "skg_global_avgpool_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "skg_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "skg_transh_draw_f32": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),

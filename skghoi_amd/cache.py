@@ -127,18 +127,54 @@ def _half_to_storage(pooled, dtype_code):
     return x.cpu().numpy()
 
 
-def produce_shard(head, features, detections, image_shapes, path, dtype="fp32", targets=None):
+def produce_shard(head, features, detections, image_shapes, path, dtype="fp32", targets=None, mirror=False,
+                  canvas_width=None):
     """The feature-cache producer: runs the head's own preprocess (NMS / top-k on the device), its `box_roi_pool` on
     the kept boxes and the global average pool of features['3'], and writes one shard.  Returns the kept detections
     (list of dicts) so that the caller can store them next to the shard (write_detections_json).  The pool may return
-    fp32, fp16 or bf16 (MultiScaleRoIAlign(output_dtype=...))."""
+    fp32, fp16 or bf16 (MultiScaleRoIAlign(output_dtype=...)).
+
+    mirror=True writes the shard of the horizontally FLIPPED images from the unflipped maps (trainer.hflip_sample's meaning
+    of a flip: every map mirrored along W, the boxes with it), without a copy of any map: the detection and target boxes of
+    image i are flipped about its own width w_i = image_shapes[i][1] (trainer.horizontal_flip_boxes), `head.preprocess` runs
+    on them, and the pool reads the maps mirrored (MultiScaleRoIAlign's mirror=) at the kept boxes shifted in x by
+    canvas_width - w_i -- one fp32 add on x1 and one on x2, exactly 0 for an unpadded image.  That is the geometry of
+    mirroring the padded canvas: the content of image i ends up in [canvas_width - w_i, canvas_width), while the head keeps
+    seeing boxes in the image's own frame.  canvas_width defaults to the width the maps cover: W of the pool's finest level
+    divided by its inferred scale.  The global feature is the same average pool of features['3'], taken over a mirrored copy
+    of that one (coarsest) level so that its fp32 sum runs in the flipped map's order.  The kept detections come back in the flipped image's own frame, and the file is a plain
+    shard (ResidentFeatureSet's flipped_shard_paths)."""
     from . import _capi
     from .engine import _stream
     with torch.no_grad():
+        if mirror:
+            from .trainer import horizontal_flip_boxes
+            widths = [float(s[1]) for s in image_shapes]
+            detections = [dict(d, boxes=horizontal_flip_boxes(w, d["boxes"])) for d, w in zip(detections, widths)]
+            if targets is not None:
+                targets = [dict(t, boxes_h=horizontal_flip_boxes(w, t["boxes_h"]), boxes_o=horizontal_flip_boxes(w, t["boxes_o"]))
+                           for t, w in zip(targets, widths)]
         kept = head.preprocess(detections, targets)
         coords = [d["boxes"] for d in kept]
-        pooled = head.box_roi_pool(features, coords, image_shapes)
-        f3 = features["3"].float().contiguous()
+        if mirror:
+            pool = head.box_roi_pool
+            if canvas_width is None:
+                finest = next(features[k] for k in pool.featmap_names if k in features)
+                hw = (max(s[0] for s in image_shapes), max(s[1] for s in image_shapes))
+                canvas_width = float(finest.shape[-1]) / pool.infer_scale(finest.shape[-2:], hw)
+            shifted = []
+            for c, w in zip(coords, widths):
+                c = c.clone()
+                c[:, 0] += float(canvas_width) - w
+                c[:, 2] += float(canvas_width) - w
+                shifted.append(c)
+            pooled = pool(features, shifted, image_shapes, mirror=[True] * len(coords))
+        else:
+            pooled = head.box_roi_pool(features, coords, image_shapes)
+        f3 = features["3"].float()
+        if mirror:                                  # the mean of the mirrored map, summed in ITS order: the bytes of the plain
+            f3 = f3.flip(-1)                        # producer on the flipped maps (one copy of the coarsest level only)
+        f3 = f3.contiguous()
         g = torch.empty(f3.shape[0], f3.shape[1], device=f3.device)
         _capi.check(_capi.lib().skg_global_avgpool_f32(f3.data_ptr(), f3.shape[0], f3.shape[1],
                                                        f3.shape[2] * f3.shape[3], g.data_ptr(), _stream()),

@@ -18,6 +18,12 @@
 // Limits of the *_nhwc entries: C % 8 == 0 and pooled <= SKG_ROI_NHWC_MAX_POOLED (8: the 64 x (pooled^2 | 1) fp32 tile is
 // static LDS, 16.25 KiB) else SKG_E_ARG; every level base, boxes, out / dout 16-byte aligned else SKG_E_ALIGN;
 // n_rois * ceil(C / 64) workgroups <= 2^31 - 1 else SKG_E_LIMIT.
+//
+// Mirrored images (the *_mirror_* entries): image_mirror[b] != 0 makes every kernel address column W_l - 1 - x of image b
+// wherever it addresses column x -- both x taps of every sample, on the RoI's level.  The coordinates, the outside test, the
+// clamps, the weights and the order of the sums are untouched, so the result has the bits of running the plain kernel on a
+// .flip(-1) copy of that image's maps.  MIR is a template parameter: the instances of a launch without flags contain no trace
+// of it (their flag pointer, the last kernel argument, is never read).
 #include <algorithm>
 #include <atomic>
 #include <type_traits>
@@ -111,13 +117,18 @@ __device__ __forceinline__ bool skg_roi_sample(int H, int W, float y, float x, s
     return true;
 }
 
+// Tap columns of a mirrored image: the addresses only, after every coordinate, test, clamp and weight.
+__device__ __forceinline__ void skg_roi_mirror_taps(int W, skg_roi_taps& t) {
+    t.x_low = W - 1 - t.x_low; t.x_high = W - 1 - t.x_high;
+}
+
 // The [B, C, H, W] forward below keeps its own copy of the geometry, the coordinate and the sample rule (skg_bilinear): on
 // skg_roi_box_geom / skg_roi_sample it computed the same bits but ran 0.4-0.5 us of 30-32 us slower on an MI355X (kernel-only
 // times), with fewer instructions as with more.  Its expressions must stay those of the helpers above, operation
 // for operation: tests/test_channels_last_roi_gpu.py and the host emulation compare its bits with the channels-last forward.
-template <int DT>
+template <int DT, bool MIR>
 __device__ __forceinline__ float skg_bilinear(const typename skg_roi_elem<DT>::T* __restrict__ f, int H, int W, float y,
-                                              float x) {
+                                              float x, bool mirror) {
     if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return 0.f;
     if (y <= 0.f) y = 0.f;
     if (x <= 0.f) x = 0.f;
@@ -125,6 +136,7 @@ __device__ __forceinline__ float skg_bilinear(const typename skg_roi_elem<DT>::T
     if (y_low >= H - 1) { y_high = y_low = H - 1; y = (float)y_low; } else y_high = y_low + 1;
     if (x_low >= W - 1) { x_high = x_low = W - 1; x = (float)x_low; } else x_high = x_low + 1;
     const float ly = y - y_low, lx = x - x_low, hy = 1.f - ly, hx = 1.f - lx;
+    if (MIR && mirror) { x_low = W - 1 - x_low; x_high = W - 1 - x_high; }         // the addresses only
     typedef skg_roi_elem<DT> E;
     const float v1 = E::ld(f, y_low * W + x_low), v2 = E::ld(f, y_low * W + x_high);
     const float v3 = E::ld(f, y_high * W + x_low), v4 = E::ld(f, y_high * W + x_high);
@@ -133,11 +145,12 @@ __device__ __forceinline__ float skg_bilinear(const typename skg_roi_elem<DT>::T
 
 // MDT: map dtype, ODT: output dtype (SKG_DTYPE_*).  <F32, F32> is skg_roi_align_f32; the other instances only change
 // how an element is loaded (widened exactly) and how the fp32 result is stored (rounded once).
-template <int MDT, int ODT>
+template <int MDT, int ODT, bool MIR>
 __global__ __launch_bounds__(256) void skg_roi_align_kernel(const skg_roi_levels L, const float* __restrict__ boxes,
                                                             const int32_t* __restrict__ box_image, int n_rois,
                                                             int pooled, int sampling,
-                                                            typename skg_roi_elem<ODT>::T* __restrict__ out) {
+                                                            typename skg_roi_elem<ODT>::T* __restrict__ out,
+                                                            const int32_t* __restrict__ image_mirror) {
     typedef typename skg_roi_elem<MDT>::T TM;
     const int64_t total = (int64_t)n_rois * L.C * pooled * pooled;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
@@ -160,12 +173,13 @@ __global__ __launch_bounds__(256) void skg_roi_align_kernel(const skg_roi_levels
         const int gh = sampling > 0 ? sampling : (int)ceilf(rh / pooled);
         const int gw = sampling > 0 ? sampling : (int)ceilf(rw / pooled);
         const float cnt = fmaxf((float)(gh * gw), 1.f);
+        const bool mirror = MIR && image_mirror[box_image[n]] != 0;
         float acc = 0.f;
         for (int iy = 0; iy < gh; ++iy) {
             const float y = y1 + ph * bh + (iy + 0.5f) * bh / (float)gh;
             for (int ix = 0; ix < gw; ++ix) {
                 const float x = x1 + pw * bw + (ix + 0.5f) * bw / (float)gw;
-                acc += skg_bilinear<MDT>(f, H, W, y, x);
+                acc += skg_bilinear<MDT, MIR>(f, H, W, y, x, mirror);
             }
         }
         skg_roi_elem<ODT>::st(out, idx, acc / cnt);
@@ -176,10 +190,12 @@ __global__ __launch_bounds__(256) void skg_roi_align_kernel(const skg_roi_levels
 // d feat[l][b, c, y, x] += sum over the samples that tapped it of  weight * d out[n, c, ph, pw] / count  (torchvision's
 // roi_align backward: no gradient with respect to the boxes).  One thread per output element, float atomics on the
 // feature gradients (zeroed by the caller): the summation order is not fixed, as in torchvision's kernel.
+template <bool MIR>
 __global__ __launch_bounds__(256) void skg_roi_align_bwd_kernel(const skg_roi_levels L, const float* __restrict__ boxes,
                                                                 const int32_t* __restrict__ box_image, int n_rois,
                                                                 int pooled, int sampling,
-                                                                const float* __restrict__ dout) {
+                                                                const float* __restrict__ dout,
+                                                                const int32_t* __restrict__ image_mirror) {
     const int64_t total = (int64_t)n_rois * L.C * pooled * pooled;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         const int pw = (int)(idx % pooled);
@@ -190,12 +206,14 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_kernel(const skg_roi_le
         const int W = g.W;
         float* f = static_cast<float*>(const_cast<void*>(L.feat[g.l])) + ((int64_t)box_image[n] * L.C + c) * g.H * W;   // gradient map of the level
         const float gr = dout[idx] / g.cnt;
+        const bool mirror = MIR && image_mirror[box_image[n]] != 0;
         for (int iy = 0; iy < g.gh; ++iy) {
             const float y = skg_roi_coord(g.y1, ph, g.bh, iy, g.gh);
             for (int ix = 0; ix < g.gw; ++ix) {
                 const float x = skg_roi_coord(g.x1, pw, g.bw, ix, g.gw);
                 skg_roi_taps t;
                 if (!skg_roi_sample(g.H, W, y, x, t)) continue;
+                if (MIR && mirror) skg_roi_mirror_taps(W, t);
                 atomicAdd(f + t.y_low * W + t.x_low, t.w1 * gr);
                 atomicAdd(f + t.y_low * W + t.x_high, t.w2 * gr);
                 atomicAdd(f + t.y_high * W + t.x_low, t.w3 * gr);
@@ -217,11 +235,12 @@ template <int DT> union skg_roi_vec {
 };
 
 // grid = n_rois * n_slabs workgroups of 256: thread -> (bin group, 16-byte channel vector of the slab).
-template <int MDT, int ODT>
+template <int MDT, int ODT, bool MIR>
 __global__ __launch_bounds__(256) void skg_roi_align_nhwc_kernel(const skg_roi_levels L, const float* __restrict__ boxes,
                                                                  const int32_t* __restrict__ box_image, int n_slabs,
                                                                  int pooled, int sampling,
-                                                                 typename skg_roi_elem<ODT>::T* __restrict__ out) {
+                                                                 typename skg_roi_elem<ODT>::T* __restrict__ out,
+                                                                 const int32_t* __restrict__ image_mirror) {
     typedef skg_roi_elem<MDT> EM;
     typedef skg_roi_elem<ODT> EO;
     typedef typename EM::T TM;
@@ -239,6 +258,7 @@ __global__ __launch_bounds__(256) void skg_roi_align_nhwc_kernel(const skg_roi_l
     const int H = g.H, W = g.W;
     const int cl = ((int)threadIdx.x % NV) * VM;
     if (cl < cs) {
+        const bool mirror = MIR && image_mirror[box_image[n]] != 0;
         const TM* f = static_cast<const TM*>(L.feat[g.l]) + (int64_t)box_image[n] * H * W * L.C + c0 + cl;
         for (int bin = (int)threadIdx.x / NV; bin < pp; bin += NG) {
             const int ph = bin / pooled, pw = bin - ph * pooled;
@@ -255,6 +275,7 @@ __global__ __launch_bounds__(256) void skg_roi_align_nhwc_kernel(const skg_roi_l
                         for (int j = 0; j < VM; ++j) acc[j] += 0.f;
                         continue;
                     }
+                    if (MIR && mirror) skg_roi_mirror_taps(W, t);
                     skg_roi_vec<MDT> v1, v2, v3, v4;
                     v1.q = *reinterpret_cast<const uint4*>(f + ((int64_t)t.y_low * W + t.x_low) * L.C);
                     v2.q = *reinterpret_cast<const uint4*>(f + ((int64_t)t.y_low * W + t.x_high) * L.C);
@@ -288,10 +309,12 @@ __global__ __launch_bounds__(256) void skg_roi_align_nhwc_kernel(const skg_roi_l
 // Backward into channels-last fp32 gradient maps: d out of the slab staged through LDS (16-byte loads); then a lane owns
 // one channel and a wave one bin at a time (waves take the bins round-robin, the bin geometry is wave-uniform), so every
 // atomic instruction of a full slab adds 256 contiguous bytes.  Same products as skg_roi_align_bwd_kernel.
+template <bool MIR>
 __global__ __launch_bounds__(256) void skg_roi_align_bwd_nhwc_kernel(const skg_roi_levels L, const float* __restrict__ boxes,
                                                                      const int32_t* __restrict__ box_image, int n_slabs,
                                                                      int pooled, int sampling,
-                                                                     const float* __restrict__ dout) {
+                                                                     const float* __restrict__ dout,
+                                                                     const int32_t* __restrict__ image_mirror) {
     constexpr int VM = 1, NV = SKG_ROI_NHWC_SLAB / VM, NG = 256 / NV;       // channels per lane, lanes per bin, bins in flight
     __shared__ float tile[SKG_ROI_NHWC_TILE];
     const int n = (int)(blockIdx.x / (unsigned)n_slabs);
@@ -313,6 +336,7 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_nhwc_kernel(const skg_r
     const int H = g.H, W = g.W;
     const int cl = ((int)threadIdx.x % NV) * VM;
     if (cl >= cs) return;
+    const bool mirror = MIR && image_mirror[box_image[n]] != 0;
     float* f = static_cast<float*>(const_cast<void*>(L.feat[g.l])) + (int64_t)box_image[n] * H * W * L.C + c0 + cl;
     for (int bin = (int)threadIdx.x / NV; bin < pp; bin += NG) {
         const int ph = bin / pooled, pw = bin - ph * pooled;
@@ -325,6 +349,7 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_nhwc_kernel(const skg_r
                 const float x = skg_roi_coord(g.x1, pw, g.bw, ix, g.gw);
                 skg_roi_taps t;
                 if (!skg_roi_sample(H, W, y, x, t)) continue;
+                if (MIR && mirror) skg_roi_mirror_taps(W, t);
                 float* p1 = f + ((int64_t)t.y_low * W + t.x_low) * L.C;
                 float* p2 = f + ((int64_t)t.y_low * W + t.x_high) * L.C;
                 float* p3 = f + ((int64_t)t.y_high * W + t.x_low) * L.C;
@@ -356,6 +381,9 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_nhwc_kernel(const skg_r
 // index into an LDS list; the chunks follow each other, so n_rois is unbounded and no workspace is needed.  The per-pixel
 // tap tests walk the 1-D sample rows and columns with the forward's expressions (skg_roi_sample's rules per axis): the
 // sampling is never inverted analytically, and the walk indexes no memory by a tap coordinate.
+// A workgroup belongs to one image, so its mirror flag is uniform: the thread that owns physical pixel (py, px) of a mirrored
+// image runs the walk for the virtual pixel (py, W - 1 - px), the tile's rectangle is listed as [W - 1 - tx1, W - 1 - tx0], and
+// the store goes to the physical pixel.  The order above holds in the virtual frame: the bits of autograd through .flip(-1).
 #define SKG_ROI_DET_CHUNK 256
 #define SKG_ROI_DET_TW 32                      // [B, C, H, W]: 32 x 8 pixels, lanes along x, 16 channels per slab
 #define SKG_ROI_DET_TH 8
@@ -448,11 +476,12 @@ __device__ __forceinline__ void skg_roi_det_item_of_block(const skg_roi_levels& 
 }
 
 // [B, C, H, W] gradient maps of dtype DT: a thread owns one pixel of the 32 x 8 tile (lanes along x) and the slab's channels.
-template <int DT>
+template <int DT, bool MIR>
 __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_kernel(const skg_roi_levels L, const skg_roi_det_grid G,
                                                                     const float* __restrict__ boxes,
                                                                     const int32_t* __restrict__ box_image, int n_rois,
-                                                                    int pooled, int sampling, const float* __restrict__ dout) {
+                                                                    int pooled, int sampling, const float* __restrict__ dout,
+                                                                    const int32_t* __restrict__ image_mirror) {
     typedef skg_roi_elem<DT> E;
     typedef typename E::T T;
     constexpr int CS = SKG_ROI_DET_CS;
@@ -466,18 +495,21 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_kernel(const skg_ro
     const int ty1 = min(ty0 + SKG_ROI_DET_TH, H) - 1, tx1 = min(tx0 + SKG_ROI_DET_TW, W) - 1;
     const int py = ty0 + (int)threadIdx.x / SKG_ROI_DET_TW, px = tx0 + (int)threadIdx.x % SKG_ROI_DET_TW;
     const bool own = py < H && px < W;
+    const bool mirror = MIR && image_mirror[b] != 0;
+    const int vx = mirror ? W - 1 - px : px;                           // the pixel of the walk (virtual frame)
+    const int lx0 = mirror ? W - 1 - tx1 : tx0, lx1 = mirror ? W - 1 - tx0 : tx1;
     const int c0 = slab * CS, cs = min(CS, L.C - c0), pp = pooled * pooled;
     float acc[CS];
 #pragma unroll
     for (int j = 0; j < CS; ++j) acc[j] = 0.f;
     for (int chunk0 = 0; chunk0 < n_rois; chunk0 += SKG_ROI_DET_CHUNK) {
-        const int n = skg_roi_det_list(L, boxes, box_image, n_rois, chunk0, l, b, ty0, ty1, tx0, tx1, pooled, sampling, s_hit,
+        const int n = skg_roi_det_list(L, boxes, box_image, n_rois, chunk0, l, b, ty0, ty1, lx0, lx1, pooled, sampling, s_hit,
                                        s_item, &s_n);
         if (!own) continue;
         for (int i = 0; i < n; ++i) {
             const skg_roi_det_item it = s_item[i];
             const float* d = dout + ((int64_t)it.r * L.C + c0) * pp;
-            skg_roi_det_walk(it, H, W, pooled, py, px, [&](int bin, float w) {
+            skg_roi_det_walk(it, H, W, pooled, py, vx, [&](int bin, float w) {
 #pragma unroll
                 for (int j = 0; j < CS; ++j)
                     if (j < cs) acc[j] += w * (d[(int64_t)j * pp + bin] / it.cnt);
@@ -494,12 +526,13 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_kernel(const skg_ro
 // Channels-last gradient maps of dtype DT: a lane owns 16 bytes of consecutive channels (4 fp32 / 8 half) of the slab for
 // 64 / NG pixels of the 8 x 8 tile; d out of a listed RoI's slab is staged through LDS with 16-byte loads (divided by the
 // sample count on the way: the gr of the atomics kernel) and the gradient leaves as 16-byte stores.
-template <int DT>
+template <int DT, bool MIR>
 __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_nhwc_kernel(const skg_roi_levels L, const skg_roi_det_grid G,
                                                                          const float* __restrict__ boxes,
                                                                          const int32_t* __restrict__ box_image, int n_rois,
                                                                          int pooled, int sampling,
-                                                                         const float* __restrict__ dout) {
+                                                                         const float* __restrict__ dout,
+                                                                         const int32_t* __restrict__ image_mirror) {
     typedef skg_roi_elem<DT> E;
     typedef typename E::T T;
     constexpr int VG = 16 / (int)sizeof(T);                    // channels per lane
@@ -518,6 +551,8 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_nhwc_kernel(const s
     const int c0 = slab * SKG_ROI_NHWC_SLAB, cs = min(SKG_ROI_NHWC_SLAB, L.C - c0);    // cs: a multiple of 8
     const int pp = pooled * pooled, S = pp | 1;
     const int cl = ((int)threadIdx.x % NV) * VG, grp = (int)threadIdx.x / NV;
+    const bool mirror = MIR && image_mirror[b] != 0;
+    const int lx0 = mirror ? W - 1 - tx1 : tx0, lx1 = mirror ? W - 1 - tx0 : tx1;
     int py[NP], px[NP];
     bool own[NP];
     float acc[NP][VG];
@@ -530,7 +565,7 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_nhwc_kernel(const s
         for (int j = 0; j < VG; ++j) acc[k][j] = 0.f;
     }
     for (int chunk0 = 0; chunk0 < n_rois; chunk0 += SKG_ROI_DET_CHUNK) {
-        const int n = skg_roi_det_list(L, boxes, box_image, n_rois, chunk0, l, b, ty0, ty1, tx0, tx1, pooled, sampling, s_hit,
+        const int n = skg_roi_det_list(L, boxes, box_image, n_rois, chunk0, l, b, ty0, ty1, lx0, lx1, pooled, sampling, s_hit,
                                        s_item, &s_n);
         for (int i = 0; i < n; ++i) {
             const skg_roi_det_item it = s_item[i];
@@ -548,7 +583,7 @@ __global__ __launch_bounds__(256) void skg_roi_align_bwd_det_nhwc_kernel(const s
 #pragma unroll
             for (int k = 0; k < NP; ++k) {
                 if (!own[k]) continue;
-                skg_roi_det_walk(it, H, W, pooled, py[k], px[k], [&](int bin, float w) {
+                skg_roi_det_walk(it, H, W, pooled, py[k], mirror ? W - 1 - px[k] : px[k], [&](int bin, float w) {
 #pragma unroll
                     for (int j = 0; j < VG; ++j) acc[k][j] += w * tile[(cl + j) * S + bin];
                 });
@@ -592,23 +627,24 @@ static int skg_roi_levels_fill(skg_roi_levels& L, const void* const* feats_host,
     return 0;
 }
 
-// The argument check of all five launching entries, in the order that decides which code wins; fills L.
+// The argument check of every launching entry, in the order that decides which code wins; fills L.
 //   nhwc: the channels-last limits -- C % 8 and pooled <= SKG_ROI_NHWC_MAX_POOLED, `io` (out / dout) and every level base
 //         16-byte aligned;
 //   det:  a deterministic entry -- n_images is checked, and without a RoI it still launches (the maps are written), where
 //         the others have nothing to do; the level bases are left to its grid loop, which reports them level by level
 //         between the workgroup counts.
 //   dt0, dt1: the entry's dtype codes (an entry with one passes it twice, an fp32-only entry SKG_DTYPE_F32).
+//   image_mirror: the per-image mirror flags (device, n_images of them) or null; with flags n_images is checked too.
 // Returns SKG_E_* or 0; *nothing: 0 was returned because there is no RoI and the entry is not deterministic (no launch).
 static int skg_roi_check(bool nhwc, bool det, skg_roi_levels& L, const void* const* feats_host, int dt0, int dt1,
                          const int32_t* H_host, const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
                          int k_max, float canonical_scale, int canonical_level, const float* boxes, const int32_t* box_image,
-                         int n_rois, int n_images, int pooled, const void* io, bool* nothing) {
+                         int n_rois, int n_images, int pooled, const void* io, const int32_t* image_mirror, bool* nothing) {
     *nothing = false;
     if (n_levels < 1 || n_levels > SKG_ROI_MAX_LEVELS || C <= 0 || pooled <= 0 || n_rois < 0 || k_max - k_min + 1 != n_levels)
         return SKG_E_ARG;
     if (dt0 < SKG_DTYPE_F32 || dt0 > SKG_DTYPE_BF16 || dt1 < SKG_DTYPE_F32 || dt1 > SKG_DTYPE_BF16) return SKG_E_ARG;
-    if (det && n_images <= 0) return SKG_E_ARG;
+    if ((det || image_mirror) && n_images <= 0) return SKG_E_ARG;
     if (nhwc && ((C & 7) || pooled > SKG_ROI_NHWC_MAX_POOLED)) return SKG_E_ARG;     // 16-byte channel vectors; the LDS tile
     if (n_rois == 0 && !det) { *nothing = true; return 0; }
     if (!feats_host || !H_host || !W_host || !scales_host) return SKG_E_ARG;
@@ -632,11 +668,43 @@ static void skg_roi_with_dtype(int dt, F f) {
     }
 }
 
-// The four entries below: every check, the counter, one launch.
+// f(std::true_type / std::false_type): the MIR argument of a kernel -- flags given or not
+template <class F>
+static void skg_roi_with_mirror(const int32_t* image_mirror, F f) {
+    if (image_mirror) f(std::true_type()); else f(std::false_type());
+}
+
+// The four *_mirror_* entries below: every check, the counter, one launch.  The entries without flags forward to them
+// with a null pointer and launch the instances they always launched.
 
 // [B, C, H, W] kernels: one thread per output element, grid-stride beyond 256 * 64 workgroups
 static dim3 skg_roi_nchw_grid(int n_rois, int C, int pooled) {
     return dim3((unsigned)std::min<int64_t>(((int64_t)n_rois * C * pooled * pooled + 255) / 256, 256 * 64));
+}
+
+extern "C" int skg_roi_align_mirror_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
+                                      const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                                      int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                                      const int32_t* box_image, int n_rois, int pooled, int sampling, void* out,
+                                      int out_dtype, const int32_t* image_mirror, int n_images, void* stream) {
+    skg_roi_levels L;
+    bool nothing;
+    const int rc = skg_roi_check(false, false, L, feats_host, map_dtype, out_dtype, H_host, W_host, scales_host, n_levels, C,
+                                 k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois, n_images, pooled, out,
+                                 image_mirror, &nothing);
+    if (rc || nothing) return rc;
+    g_roi_layout_counts[0].fetch_add(1, std::memory_order_relaxed);
+    skg_roi_with_dtype(map_dtype, [&](auto m) {
+        skg_roi_with_dtype(out_dtype, [&](auto o) {
+            skg_roi_with_mirror(image_mirror, [&](auto mir) {
+                hipLaunchKernelGGL((skg_roi_align_kernel<decltype(m)::value, decltype(o)::value, decltype(mir)::value>),
+                                   skg_roi_nchw_grid(n_rois, C, pooled), dim3(256), 0, (hipStream_t)stream, L, boxes, box_image,
+                                   n_rois, pooled, sampling, static_cast<typename skg_roi_elem<decltype(o)::value>::T*>(out),
+                                   image_mirror);
+            });
+        });
+    });
+    return skg_launch_status();
 }
 
 extern "C" int skg_roi_align_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
@@ -644,20 +712,9 @@ extern "C" int skg_roi_align_x(const void* const* feats_host, int map_dtype, con
                                int k_max, float canonical_scale, int canonical_level, const float* boxes,
                                const int32_t* box_image, int n_rois, int pooled, int sampling, void* out, int out_dtype,
                                void* stream) {
-    skg_roi_levels L;
-    bool nothing;
-    const int rc = skg_roi_check(false, false, L, feats_host, map_dtype, out_dtype, H_host, W_host, scales_host, n_levels, C,
-                                 k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois, 1, pooled, out, &nothing);
-    if (rc || nothing) return rc;
-    g_roi_layout_counts[0].fetch_add(1, std::memory_order_relaxed);
-    skg_roi_with_dtype(map_dtype, [&](auto m) {
-        skg_roi_with_dtype(out_dtype, [&](auto o) {
-            hipLaunchKernelGGL((skg_roi_align_kernel<decltype(m)::value, decltype(o)::value>), skg_roi_nchw_grid(n_rois, C, pooled),
-                               dim3(256), 0, (hipStream_t)stream, L, boxes, box_image, n_rois, pooled, sampling,
-                               static_cast<typename skg_roi_elem<decltype(o)::value>::T*>(out));
-        });
-    });
-    return skg_launch_status();
+    return skg_roi_align_mirror_x(feats_host, map_dtype, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
+                                  canonical_scale, canonical_level, boxes, box_image, n_rois, pooled, sampling, out, out_dtype,
+                                  nullptr, 0, stream);
 }
 
 extern "C" int skg_roi_align_f32(const float* const* feats_host, const int32_t* H_host, const int32_t* W_host,
@@ -670,43 +727,90 @@ extern "C" int skg_roi_align_f32(const float* const* feats_host, const int32_t* 
                            pooled, sampling, out, SKG_DTYPE_F32, stream);
 }
 
+extern "C" int skg_roi_align_bwd_mirror_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                                            const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                            float canonical_scale, int canonical_level, const float* boxes,
+                                            const int32_t* box_image, int n_rois, int pooled, int sampling,
+                                            const float* dout, const int32_t* image_mirror, int n_images, void* stream) {
+    skg_roi_levels L;
+    bool nothing;
+    const int rc = skg_roi_check(false, false, L, reinterpret_cast<const void* const*>(dfeats_host), SKG_DTYPE_F32,
+                                 SKG_DTYPE_F32, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
+                                 canonical_level, boxes, box_image, n_rois, n_images, pooled, dout, image_mirror, &nothing);
+    if (rc || nothing) return rc;
+    g_roi_layout_counts[2].fetch_add(1, std::memory_order_relaxed);
+    skg_roi_with_mirror(image_mirror, [&](auto mir) {
+        hipLaunchKernelGGL(skg_roi_align_bwd_kernel<decltype(mir)::value>, skg_roi_nchw_grid(n_rois, C, pooled), dim3(256), 0,
+                           (hipStream_t)stream, L, boxes, box_image, n_rois, pooled, sampling, dout, image_mirror);
+    });
+    return skg_launch_status();
+}
+
 extern "C" int skg_roi_align_bwd_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
                                      const float* scales_host, int n_levels, int C, int k_min, int k_max,
                                      float canonical_scale, int canonical_level, const float* boxes,
                                      const int32_t* box_image, int n_rois, int pooled, int sampling, const float* dout,
                                      void* stream) {
-    skg_roi_levels L;
-    bool nothing;
-    const int rc = skg_roi_check(false, false, L, reinterpret_cast<const void* const*>(dfeats_host), SKG_DTYPE_F32,
-                                 SKG_DTYPE_F32, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
-                                 canonical_level, boxes, box_image, n_rois, 1, pooled, dout, &nothing);
-    if (rc || nothing) return rc;
-    g_roi_layout_counts[2].fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(skg_roi_align_bwd_kernel, skg_roi_nchw_grid(n_rois, C, pooled), dim3(256), 0, (hipStream_t)stream,
-                       L, boxes, box_image, n_rois, pooled, sampling, dout);
-    return skg_launch_status();
+    return skg_roi_align_bwd_mirror_f32(dfeats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
+                                        canonical_level, boxes, box_image, n_rois, pooled, sampling, dout, nullptr, 0, stream);
 }
 
 // channels-last: one workgroup per (RoI, slab of SKG_ROI_NHWC_SLAB channels)
-extern "C" int skg_roi_align_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
-                                    const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
-                                    int k_max, float canonical_scale, int canonical_level, const float* boxes,
-                                    const int32_t* box_image, int n_rois, int pooled, int sampling, void* out,
-                                    int out_dtype, void* stream) {
+extern "C" int skg_roi_align_mirror_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
+                                           const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                                           int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                                           const int32_t* box_image, int n_rois, int pooled, int sampling, void* out,
+                                           int out_dtype, const int32_t* image_mirror, int n_images, void* stream) {
     skg_roi_levels L;
     bool nothing;
     const int rc = skg_roi_check(true, false, L, feats_host, map_dtype, out_dtype, H_host, W_host, scales_host, n_levels, C,
-                                 k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois, 1, pooled, out, &nothing);
+                                 k_min, k_max, canonical_scale, canonical_level, boxes, box_image, n_rois, n_images, pooled, out,
+                                 image_mirror, &nothing);
     if (rc || nothing) return rc;
     const int n_slabs = (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB;
     if ((int64_t)n_rois * n_slabs > 0x7fffffffLL) return SKG_E_LIMIT;
     g_roi_layout_counts[1].fetch_add(1, std::memory_order_relaxed);
     skg_roi_with_dtype(map_dtype, [&](auto m) {
         skg_roi_with_dtype(out_dtype, [&](auto o) {
-            hipLaunchKernelGGL((skg_roi_align_nhwc_kernel<decltype(m)::value, decltype(o)::value>), dim3((unsigned)(n_rois * n_slabs)),
-                               dim3(256), 0, (hipStream_t)stream, L, boxes, box_image, n_slabs, pooled, sampling,
-                               static_cast<typename skg_roi_elem<decltype(o)::value>::T*>(out));
+            skg_roi_with_mirror(image_mirror, [&](auto mir) {
+                hipLaunchKernelGGL((skg_roi_align_nhwc_kernel<decltype(m)::value, decltype(o)::value, decltype(mir)::value>),
+                                   dim3((unsigned)(n_rois * n_slabs)), dim3(256), 0, (hipStream_t)stream, L, boxes, box_image,
+                                   n_slabs, pooled, sampling, static_cast<typename skg_roi_elem<decltype(o)::value>::T*>(out),
+                                   image_mirror);
+            });
         });
+    });
+    return skg_launch_status();
+}
+
+extern "C" int skg_roi_align_nhwc_x(const void* const* feats_host, int map_dtype, const int32_t* H_host,
+                                    const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
+                                    int k_max, float canonical_scale, int canonical_level, const float* boxes,
+                                    const int32_t* box_image, int n_rois, int pooled, int sampling, void* out,
+                                    int out_dtype, void* stream) {
+    return skg_roi_align_mirror_nhwc_x(feats_host, map_dtype, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
+                                       canonical_scale, canonical_level, boxes, box_image, n_rois, pooled, sampling, out,
+                                       out_dtype, nullptr, 0, stream);
+}
+
+extern "C" int skg_roi_align_bwd_mirror_nhwc_f32(float* const* dfeats_host, const int32_t* H_host, const int32_t* W_host,
+                                                 const float* scales_host, int n_levels, int C, int k_min, int k_max,
+                                                 float canonical_scale, int canonical_level, const float* boxes,
+                                                 const int32_t* box_image, int n_rois, int pooled, int sampling,
+                                                 const float* dout, const int32_t* image_mirror, int n_images,
+                                                 void* stream) {
+    skg_roi_levels L;
+    bool nothing;
+    const int rc = skg_roi_check(true, false, L, reinterpret_cast<const void* const*>(dfeats_host), SKG_DTYPE_F32,
+                                 SKG_DTYPE_F32, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
+                                 canonical_level, boxes, box_image, n_rois, n_images, pooled, dout, image_mirror, &nothing);
+    if (rc || nothing) return rc;
+    const int n_slabs = (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB;
+    if ((int64_t)n_rois * n_slabs > 0x7fffffffLL) return SKG_E_LIMIT;
+    g_roi_layout_counts[3].fetch_add(1, std::memory_order_relaxed);
+    skg_roi_with_mirror(image_mirror, [&](auto mir) {
+        hipLaunchKernelGGL(skg_roi_align_bwd_nhwc_kernel<decltype(mir)::value>, dim3((unsigned)(n_rois * n_slabs)), dim3(256), 0,
+                           (hipStream_t)stream, L, boxes, box_image, n_slabs, pooled, sampling, dout, image_mirror);
     });
     return skg_launch_status();
 }
@@ -716,18 +820,9 @@ extern "C" int skg_roi_align_bwd_nhwc_f32(float* const* dfeats_host, const int32
                                           float canonical_scale, int canonical_level, const float* boxes,
                                           const int32_t* box_image, int n_rois, int pooled, int sampling,
                                           const float* dout, void* stream) {
-    skg_roi_levels L;
-    bool nothing;
-    const int rc = skg_roi_check(true, false, L, reinterpret_cast<const void* const*>(dfeats_host), SKG_DTYPE_F32,
-                                 SKG_DTYPE_F32, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale,
-                                 canonical_level, boxes, box_image, n_rois, 1, pooled, dout, &nothing);
-    if (rc || nothing) return rc;
-    const int n_slabs = (C + SKG_ROI_NHWC_SLAB - 1) / SKG_ROI_NHWC_SLAB;
-    if ((int64_t)n_rois * n_slabs > 0x7fffffffLL) return SKG_E_LIMIT;
-    g_roi_layout_counts[3].fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(skg_roi_align_bwd_nhwc_kernel, dim3((unsigned)(n_rois * n_slabs)), dim3(256), 0, (hipStream_t)stream,
-                       L, boxes, box_image, n_slabs, pooled, sampling, dout);
-    return skg_launch_status();
+    return skg_roi_align_bwd_mirror_nhwc_f32(dfeats_host, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
+                                             canonical_scale, canonical_level, boxes, box_image, n_rois, pooled, sampling, dout,
+                                             nullptr, 0, stream);
 }
 
 // deterministic backward launches since the last reset: [B, C, H, W], channels-last (skg_roi_align_det_counts)
@@ -740,16 +835,17 @@ extern "C" void skg_roi_align_det_counts(int64_t* out2, int reset) {
     }
 }
 
-// both deterministic entries: every check, then one launch
+// all four deterministic entries: every check, then one launch
 static int skg_roi_align_bwd_det(bool nhwc, void* const* dfeats_host, int grad_dtype, const int32_t* H_host,
                                  const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min, int k_max,
                                  float canonical_scale, int canonical_level, const float* boxes, const int32_t* box_image,
-                                 int n_rois, int n_images, int pooled, int sampling, const float* dout, void* stream) {
+                                 int n_rois, int n_images, int pooled, int sampling, const float* dout,
+                                 const int32_t* image_mirror, void* stream) {
     skg_roi_levels L;
     bool nothing;
     const int rc = skg_roi_check(nhwc, true, L, reinterpret_cast<const void* const*>(dfeats_host), grad_dtype, grad_dtype,
                                  H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale, canonical_level, boxes,
-                                 box_image, n_rois, n_images, pooled, dout, &nothing);
+                                 box_image, n_rois, n_images, pooled, dout, image_mirror, &nothing);
     if (rc) return rc;
     skg_roi_det_grid G;
     const int tw = nhwc ? SKG_ROI_DET_NT : SKG_ROI_DET_TW, th = nhwc ? SKG_ROI_DET_NT : SKG_ROI_DET_TH;
@@ -768,29 +864,36 @@ static int skg_roi_align_bwd_det(bool nhwc, void* const* dfeats_host, int grad_d
     G.start[SKG_ROI_MAX_LEVELS] = (unsigned)blocks;
     g_roi_det_counts[nhwc ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
     skg_roi_with_dtype(grad_dtype, [&](auto d) {
-        const dim3 grid((unsigned)blocks), wg(256);
-        if (nhwc) hipLaunchKernelGGL((skg_roi_align_bwd_det_nhwc_kernel<decltype(d)::value>), grid, wg, 0, (hipStream_t)stream, L, G, boxes, box_image, n_rois, pooled, sampling, dout);
-        else hipLaunchKernelGGL((skg_roi_align_bwd_det_kernel<decltype(d)::value>), grid, wg, 0, (hipStream_t)stream, L, G, boxes, box_image, n_rois, pooled, sampling, dout);
+        skg_roi_with_mirror(image_mirror, [&](auto mir) {
+            const dim3 grid((unsigned)blocks), wg(256);
+            if (nhwc) hipLaunchKernelGGL((skg_roi_align_bwd_det_nhwc_kernel<decltype(d)::value, decltype(mir)::value>), grid, wg, 0, (hipStream_t)stream, L, G, boxes, box_image, n_rois, pooled, sampling, dout, image_mirror);
+            else hipLaunchKernelGGL((skg_roi_align_bwd_det_kernel<decltype(d)::value, decltype(mir)::value>), grid, wg, 0, (hipStream_t)stream, L, G, boxes, box_image, n_rois, pooled, sampling, dout, image_mirror);
+        });
     });
     return skg_launch_status();
 }
 
-extern "C" int skg_roi_align_bwd_det_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host, const int32_t* W_host,
-                                       const float* scales_host, int n_levels, int C, int k_min, int k_max,
-                                       float canonical_scale, int canonical_level, const float* boxes,
-                                       const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling,
-                                       const float* dout, void* stream) {
-    return skg_roi_align_bwd_det(false, dfeats_host, grad_dtype, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
-                                 canonical_scale, canonical_level, boxes, box_image, n_rois, n_images, pooled, sampling, dout,
-                                 stream);
+#define SKG_ROI_DET_ARGS                                                                                                   \
+    void* const* dfeats_host, int grad_dtype, const int32_t* H_host, const int32_t* W_host, const float* scales_host,     \
+    int n_levels, int C, int k_min, int k_max, float canonical_scale, int canonical_level, const float* boxes,            \
+    const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling, const float* dout
+#define SKG_ROI_DET_PASS                                                                                                   \
+    dfeats_host, grad_dtype, H_host, W_host, scales_host, n_levels, C, k_min, k_max, canonical_scale, canonical_level,     \
+    boxes, box_image, n_rois, n_images, pooled, sampling, dout
+
+extern "C" int skg_roi_align_bwd_det_x(SKG_ROI_DET_ARGS, void* stream) {
+    return skg_roi_align_bwd_det(false, SKG_ROI_DET_PASS, nullptr, stream);
 }
 
-extern "C" int skg_roi_align_bwd_det_nhwc_x(void* const* dfeats_host, int grad_dtype, const int32_t* H_host,
-                                            const int32_t* W_host, const float* scales_host, int n_levels, int C, int k_min,
-                                            int k_max, float canonical_scale, int canonical_level, const float* boxes,
-                                            const int32_t* box_image, int n_rois, int n_images, int pooled, int sampling,
-                                            const float* dout, void* stream) {
-    return skg_roi_align_bwd_det(true, dfeats_host, grad_dtype, H_host, W_host, scales_host, n_levels, C, k_min, k_max,
-                                 canonical_scale, canonical_level, boxes, box_image, n_rois, n_images, pooled, sampling, dout,
-                                 stream);
+extern "C" int skg_roi_align_bwd_det_nhwc_x(SKG_ROI_DET_ARGS, void* stream) {
+    return skg_roi_align_bwd_det(true, SKG_ROI_DET_PASS, nullptr, stream);
+}
+
+// (n_images is part of the deterministic signature already: the siblings add the flags alone)
+extern "C" int skg_roi_align_bwd_det_mirror_x(SKG_ROI_DET_ARGS, const int32_t* image_mirror, void* stream) {
+    return skg_roi_align_bwd_det(false, SKG_ROI_DET_PASS, image_mirror, stream);
+}
+
+extern "C" int skg_roi_align_bwd_det_mirror_nhwc_x(SKG_ROI_DET_ARGS, const int32_t* image_mirror, void* stream) {
+    return skg_roi_align_bwd_det(true, SKG_ROI_DET_PASS, image_mirror, stream);
 }

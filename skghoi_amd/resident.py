@@ -14,8 +14,24 @@ per-batch host copy, no pinned allocation, no host synchronisation, no PCIe traf
     rset.check_alignment(head)                      # the cache was produced under THIS head's thresholds and mode
     trainer.Trainer(head, optimizer, None, rset.loader(batch_size=4), lazy_losses=True)(num_epochs)
 
-Not covered: the horizontal-flip augmentation (a pooled tile of the mirrored image is not the mirrored
-tile), reading the resident rows straight into box_head layer 1, and sets larger than device memory.
+The horizontal-flip augmentation (DataFactory, utils.py:85-86, 115-118, 140-143).  A pooled tile of the mirrored image is
+not the mirrored tile, so a flip cannot be made from the plain rows after the fact: the set holds a SECOND variant of every
+image, pooled from the mirrored maps by `cache.produce_shard(..., mirror=True)`, and serves one of the two per image:
+
+    rset = ResidentFeatureSet(shard_paths, raw_detections, targets, flipped_shard_paths=flipped_paths)
+    loader = rset.loader(batch_size=4, flips=trainer.draw_flips(len(rset)))      # the reference's coins, drawn once
+    loader = rset.loader(batch_size=4, flips="epoch")                            # or fresh coins at every set_epoch
+
+Every ragged array then holds 2 * n_images entries, entry n_images + i being the flipped variant of image i: its rows and
+global row from the flipped shards, its boxes / boxes_h / boxes_o flipped once on the host about the image's own width
+(`trainer.horizontal_flip_boxes`), everything else repeated.  The epoch's order becomes i + n_images * coin[i], so a batch
+is still ONE gather launch and the device does no arithmetic for the flip.  What this flip is: the `trainer.hflip_sample`
+semantics -- every cached map mirrored along its last axis, the boxes with it.  What it is not: the backbone run on the
+mirrored image (a convolution of the mirrored image is not the mirror of the convolution once strides and padding are
+asymmetric).  Whoever has those maps puts them through the plain producer and passes the shards as flipped_shard_paths.
+
+Not covered: reading the resident rows straight into box_head layer 1, and sets larger than device
+memory.
 """
 import math
 import weakref
@@ -60,6 +76,14 @@ def epoch_order(n, epoch=0, world_size=1, rank=0, seed=0, shuffle=True, drop_las
     else:
         idx = idx[:total]
     return idx[rank:total:world_size]
+
+
+def epoch_coins(n, epoch=0, seed=0):
+    """The coins of `flips="epoch"`: one 0/1 int64 per image, a function of (seed, epoch) only, from a generator of their
+    own (the global CPU generator is not touched; nor is it the stream `epoch_order` shuffles with)."""
+    g = torch.Generator()
+    g.manual_seed((int(seed) * 1000003 + int(epoch) + 0x464C4950) & ((1 << 63) - 1))
+    return torch.randint(0, 2, (int(n),), generator=g)
 
 
 class _ShardHeader:
@@ -124,10 +148,15 @@ class ResidentFeatureSet:
     `preprocess` runs again on every batch and, being deterministic, reproduces the row order the shard was produced in
     (`check_alignment` verifies it).  targets: per-image dicts of tensors whose leading dimension is the ground-truth
     pair -- boxes_h, boxes_o, labels, and object / hoi when present -- or None.
+    flipped_shard_paths: the shards of the horizontally flipped variant (cache.produce_shard(..., mirror=True)) or None.  They
+    hold the same images in the same order with the same dtype, C, pool, gdim and image_hw; their per-image box counts may
+    differ (a flipped box's width can differ by an ulp, so the NMS may keep another set).  With them every array holds
+    2 * n_images entries -- `box_counts`, `image_shapes` and `arrays` alike -- and entry n_images + i is the flipped variant
+    of image i (module docstring); `loader(flips=...)` picks a variant per image.
     Everything is validated on the host before the first device call (ValueError); a set that does not fit into the free
     device memory raises MemoryError."""
 
-    def __init__(self, shard_paths, detections, targets=None, device="cuda", keep_dtype=False):
+    def __init__(self, shard_paths, detections, targets=None, device="cuda", keep_dtype=False, flipped_shard_paths=None):
         shard_paths = list(shard_paths)
         if not shard_paths:
             raise ValueError("a resident feature set needs at least one shard")
@@ -140,6 +169,27 @@ class ResidentFeatureSet:
                         {"code": "dtype"}.get(f, f), ref.path, getattr(ref, f), h.path, getattr(h, f)))
         self.code, self.C, self.pool, self.gdim, self.row = ref.code, ref.C, ref.pool, ref.gdim, ref.row
         self.n_images = sum(h.n_images for h in hdrs)
+        self.flipped = flipped_shard_paths is not None
+        fhdrs = []
+        if self.flipped:
+            flipped_shard_paths = list(flipped_shard_paths)
+            if not flipped_shard_paths:
+                raise ValueError("flipped_shard_paths holds no shard")
+            fhdrs = [_ShardHeader(p) for p in flipped_shard_paths]
+            for h in fhdrs:
+                for f in ("code", "C", "pool", "gdim"):
+                    if h.n_images and getattr(h, f) != getattr(ref, f):
+                        raise ValueError("flipped shards differ in %s: %s has %d, %s has %d" % (
+                            {"code": "dtype"}.get(f, f), ref.path, getattr(ref, f), h.path, getattr(h, f)))
+            if sum(h.n_images for h in fhdrs) != self.n_images:
+                raise ValueError("the shards hold %d images, the flipped shards %d"
+                                 % (self.n_images, sum(h.n_images for h in fhdrs)))
+            hw, fhw = (np.concatenate([h.image_hw for h in hs]) for hs in (hdrs, fhdrs))
+            if not np.array_equal(hw, fhw):
+                i = int(np.nonzero((hw != fhw).any(axis=1))[0][0])
+                raise ValueError("image %d: image_hw %s in the shards, %s in the flipped shards (not the same images in the "
+                                 "same order)" % (i, tuple(hw[i]), tuple(fhw[i])))
+        self.n_entries = self.n_images * (2 if self.flipped else 1)
         detections = list(detections)
         if len(detections) != self.n_images:
             raise ValueError("the shards hold %d images, %d detections were given" % (self.n_images, len(detections)))
@@ -181,15 +231,23 @@ class ResidentFeatureSet:
                 host.append(("t:" + k, ts, c))
         if 2 + len(host) > _capi.CACHE_MAX_ARRAYS:
             raise ValueError("%d arrays per batch, the gather takes %d" % (2 + len(host), _capi.CACHE_MAX_ARRAYS))
-        self.box_counts = np.concatenate([np.diff(h.box_off) for h in hdrs]).astype(np.int64)
         self.det_counts, self.gt_counts = n_det, n_gt
         self.image_shapes = [(int(a), int(b)) for h in hdrs for a, b in h.image_hw]
+        if self.flipped:                                            # entry n_images + i: the flipped variant of image i
+            from .trainer import horizontal_flip_boxes
+            widths = [w for _, w in self.image_shapes]
+            flip = lambda ts: [horizontal_flip_boxes(w, t) for w, t in zip(widths, ts)]
+            host = [(name, ts + (flip(ts) if name in ("boxes", "t:boxes_h", "t:boxes_o") else ts), np.concatenate([c, c]))
+                    for name, ts, c in host]
+            self.image_shapes = self.image_shapes * 2
+        hdrs = hdrs + fhdrs                                         # storage order: the plain shards, then the flipped ones
+        self.box_counts = np.concatenate([np.diff(h.box_off) for h in hdrs]).astype(np.int64)
         self.n_boxes = int(self.box_counts.sum())
         self.keep_dtype = bool(keep_dtype)
         item = np.dtype(_DT[self.code]).itemsize
         self.arena_bytes = self.n_boxes * self.row * item
-        small = sum(sum(t.numel() * t.element_size() for t in ts) for _, ts, _ in host) + 4 * self.n_images * self.gdim \
-            + 8 * (self.n_images + 1) * 4
+        small = sum(sum(t.numel() * t.element_size() for t in ts) for _, ts, _ in host) + 4 * self.n_entries * self.gdim \
+            + 8 * (self.n_entries + 1) * 4
         # ---- device
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -200,21 +258,21 @@ class ResidentFeatureSet:
         need = self.arena_bytes + small
         free, _ = torch.cuda.mem_get_info(dev)
         if need > free:
-            raise MemoryError("the resident feature set needs %d bytes of device memory, %d are free on %s"
-                              % (need, free, dev))
+            raise MemoryError("the resident feature set needs %d bytes of device memory%s, %d are free on %s"
+                              % (need, " (both variants: the plain and the flipped shards)" if self.flipped else "", free, dev))
         self.arena = torch.empty(max(self.arena_bytes, 16), dtype=torch.uint8, device=dev)
         self._upload_payload(hdrs)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         offs = lambda c: up(np.concatenate([[0], np.cumsum(c)]).astype(np.int64))
         pooled_src = self.arena[:self.arena_bytes].view(_TORCH_DT[self.code]) if self.arena_bytes else \
             self.arena.view(_TORCH_DT[self.code])
-        glob = up(np.concatenate([h.glob for h in hdrs if h.n_images]).astype(np.float32).reshape(self.n_images, self.gdim))
+        glob = up(np.concatenate([h.glob for h in hdrs if h.n_images]).astype(np.float32).reshape(self.n_entries, self.gdim))
         self.box_off = offs(self.box_counts)
         out_dt = _TORCH_DT[self.code] if self.keep_dtype else torch.float32
         self.arrays = [
             _Ragged("pooled", pooled_src, self.box_off, self.box_counts, self.row, self.code,
                     self.code if self.keep_dtype else _capi.DTYPE_F32, out_dt, (self.C, self.pool, self.pool)),
-            _Ragged("global", glob, offs(np.ones(self.n_images, np.int64)), np.ones(self.n_images, np.int64), self.gdim,
+            _Ragged("global", glob, offs(np.ones(self.n_entries, np.int64)), np.ones(self.n_entries, np.int64), self.gdim,
                     _capi.DTYPE_F32, _capi.DTYPE_F32, torch.float32, (self.gdim, 1, 1))]
         shared = {}
         for name, ts, c in host:
@@ -265,25 +323,33 @@ class ResidentFeatureSet:
     def __len__(self):
         return self.n_images
 
-    def loader(self, batch_size=4, shuffle=True, world_size=1, rank=0, seed=0, drop_last=False):
-        return ResidentLoader(self, batch_size, shuffle, world_size, rank, seed, drop_last)
+    def loader(self, batch_size=4, shuffle=True, world_size=1, rank=0, seed=0, drop_last=False, flips=None):
+        """flips: None (no flip), a 0/1 tensor of n_images fixed coins (the reference's: trainer.draw_flips(n), drawn once
+        from the global generator by the caller) or "epoch" (fresh coins at every set_epoch, `epoch_coins`)."""
+        return ResidentLoader(self, batch_size, shuffle, world_size, rank, seed, drop_last, flips)
 
     @torch.no_grad()
     def check_alignment(self, head, batch_size=64):
         """One pass over the set: `head.preprocess`, in the head's CURRENT mode (training appends the ground truth), must keep
         exactly box_off[i + 1] - box_off[i] boxes of every image i.  Raises ValueError naming the first image that differs --
-        the guard against a cache produced under other thresholds, another mode or other detections."""
+        the guard against a cache produced under other thresholds, another mode or other detections.  A set with flipped
+        shards is checked in both variants (the plain one first), and the error names the variant too."""
         if head.training and self.target_keys is None:
             raise ValueError("a head in training mode appends the ground truth: the set was built without targets")
-        first = 0
-        for _, det, _, tg in self.loader(batch_size=min(int(batch_size), _capi.CACHE_MAX_BATCH), shuffle=False):
-            kept = head.preprocess(det, tg)
-            for k, d in enumerate(kept):
-                have, want = int(d["boxes"].shape[0]), int(self.box_counts[first + k])
-                if have != want:
-                    raise ValueError("image %d: the head keeps %d boxes, the cache holds %d rows (produced under other "
-                                     "thresholds, another mode or other detections)" % (first + k, have, want))
-            first += len(det)
+        variants = [(None, "")] if not self.flipped else \
+            [(torch.zeros(self.n_images, dtype=torch.int64), " (plain variant)"),
+             (torch.ones(self.n_images, dtype=torch.int64), " (flipped variant)")]
+        for coins, which in variants:
+            first = 0
+            loader = self.loader(batch_size=min(int(batch_size), _capi.CACHE_MAX_BATCH), shuffle=False, flips=coins)
+            for _, det, _, tg in loader:
+                kept = head.preprocess(det, tg)
+                for k, d in enumerate(kept):
+                    have, want = int(d["boxes"].shape[0]), int(self.box_counts[loader.order[first + k]])
+                    if have != want:
+                        raise ValueError("image %d%s: the head keeps %d boxes, the cache holds %d rows (produced under other "
+                                         "thresholds, another mode or other detections)" % (first + k, which, have, want))
+                first += len(det)
         return self.n_images
 
 
@@ -325,19 +391,41 @@ class ResidentLoader:
     -- precisely: its `features` mapping -- is referenced: tensors taken out of it and kept beyond that will be
     overwritten, clone them.  Asking for a further
     batch while every slot is alive allocates fresh buffers for it instead of overwriting a live batch.
-    `loader.sampler` is the loader itself, so `Trainer.train_epoch` reshuffles it like a DataLoader's sampler."""
+    `loader.sampler` is the loader itself, so `Trainer.train_epoch` reshuffles it like a DataLoader's sampler.
 
-    def __init__(self, rset, batch_size=4, shuffle=True, world_size=1, rank=0, seed=0, drop_last=False):
+    flips (a set with flipped shards only): None, fixed coins or "epoch" (ResidentFeatureSet.loader).  set_epoch turns the
+    sampler's order -- kept in `base_order`, the coins of the epoch in `coins` -- into entries i + n_images * coin[i] before
+    validating and uploading it; `order` holds those entries, and the row counts, the caps and image_shapes follow them."""
+
+    def __init__(self, rset, batch_size=4, shuffle=True, world_size=1, rank=0, seed=0, drop_last=False, flips=None):
         batch_size = int(batch_size)
         if not 1 <= batch_size <= _capi.CACHE_MAX_BATCH:
             raise ValueError("batch_size must be in 1 .. %d" % _capi.CACHE_MAX_BATCH)
+        self.flips = None
+        if flips is not None:
+            if not getattr(rset, "flipped", False):
+                raise ValueError("flips were asked of a set without flipped shards (flipped_shard_paths)")
+            if isinstance(flips, str):
+                if flips != "epoch":
+                    raise ValueError("flips must be None, a 0/1 tensor of %d coins or \"epoch\" (got %r)"
+                                     % (rset.n_images, flips))
+                self.flips = "epoch"
+            else:
+                coins = torch.as_tensor(flips).detach().cpu().reshape(-1)
+                if coins.numel() != rset.n_images:
+                    raise ValueError("%d coins for %d images" % (coins.numel(), rset.n_images))
+                if not bool(((coins == 0) | (coins == 1)).all()):
+                    raise ValueError("coins outside {0, 1}")
+                self.flips = coins.to(torch.int64)
         epoch_order(1, 0, world_size, rank)                        # (validates world_size / rank)
         self.set, self.batch_size, self.shuffle = rset, batch_size, bool(shuffle)
         self.world_size, self.rank, self.seed, self.drop_last = int(world_size), int(rank), int(seed), bool(drop_last)
         self.sampler = self
         self.epoch = 0
         self.num_samples = len(epoch_order(rset.n_images, 0, world_size, rank, seed, False, drop_last))
-        self.order = None                 # host list of the uploaded epoch
+        self.order = None                 # host list of the uploaded epoch (entries: i + n_images * coin[i])
+        self.base_order = None            # the sampler's order of that epoch (images)
+        self.coins = None                 # int64 [n_images]: the coins of that epoch, or None
         self._order_dev = None
         self._ready = None                # epoch whose order is on the device
         self._ring = []
@@ -354,6 +442,11 @@ class ResidentLoader:
         arr = np.asarray(order, dtype=np.int64).reshape(-1)
         if arr.shape[0] != self.num_samples or (arr.shape[0] and (arr.min() < 0 or arr.max() >= rset.n_images)):
             raise ValueError("epoch order outside 0 .. %d" % (rset.n_images - 1))
+        self.base_order, self.coins = order, None
+        if self.flips is not None:
+            self.coins = epoch_coins(rset.n_images, self.epoch, self.seed) if isinstance(self.flips, str) else self.flips
+            arr = arr + rset.n_images * self.coins.numpy()[arr]
+            order = arr.tolist()
         self.order = order
         # host-known row counts: per array the counts of every slot of the epoch and the rows of every batch
         starts = np.arange(0, self.num_samples, self.batch_size)

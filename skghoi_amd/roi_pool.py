@@ -20,10 +20,15 @@ channels-last (`skg_roi_align_bwd_nhwc_f32`).  Every other layout is made [B, C,
 `deterministic` (None: follow `torch.use_deterministic_algorithms`) selects the backward without atomics
 (`skg_roi_align_bwd_det_x` / `skg_roi_align_bwd_det_nhwc_x`): a fixed summation order, the same bits on every run and in both
 layouts, gradients written once in the maps' dtype into uninitialised maps (no zero fill, no fp32 temporaries).
+
+`forward(..., mirror=[bool per image])` pools the flagged images as if their maps were mirrored along W, without the
+`.flip(-1)` copy (`skg_roi_align_mirror_x` and its siblings): the kernels read column W_l - 1 - x wherever they read column x,
+nothing else changes, so the output -- and the map gradients, with either backward -- have the bits of the same module on
+the flipped copy.  The boxes are the caller's, in the frame of the mirrored maps (the contract of `trainer.hflip_sample`).
 """
 import ctypes as C
 import math
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -74,6 +79,7 @@ class _RoIAlignFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, rois, img, *feats):
         scales, k_min, k_max, canon_s, canon_l, pooled, sampling, out_dtype = cfg[:8]
+        mir = cfg[9] if len(cfg) > 9 else None      # int32 flag per image on the device, or None: the entries without flags
         dts = {f.dtype for f in feats}
         nhwc = pooled <= _NHWC_MAX_POOLED and channels_last_route(feats)
         map_code = _HALF_CODES.get(feats[0].dtype) if len(dts) == 1 else None
@@ -88,11 +94,15 @@ class _RoIAlignFn(torch.autograd.Function):
         n_rois, Cc = rois.shape[0], fs[0].shape[1]
         out = torch.empty(n_rois, Cc, pooled, pooled, device=rois.device, dtype=out_dtype)
         ptrs, Hs, Ws, sc = _level_args(fs, scales)
-        name = "skg_roi_align_nhwc_x" if nhwc else "skg_roi_align_x"
+        if mir is None:
+            name, mirror_args = "skg_roi_align_nhwc_x" if nhwc else "skg_roi_align_x", ()
+        else:
+            name = "skg_roi_align_mirror_nhwc_x" if nhwc else "skg_roi_align_mirror_x"
+            mirror_args = (mir.data_ptr(), int(mir.shape[0]))
         _capi.check(getattr(_capi.lib(), name)(ptrs, map_code, Hs, Ws, sc, len(fs), Cc, k_min, k_max, float(canon_s),
                                                int(canon_l), rois.data_ptr(), img.data_ptr(), n_rois, pooled, sampling,
-                                               out.data_ptr(), _OUT_CODES[out_dtype], _stream()), name)
-        ctx.cfg, ctx.rois, ctx.img = cfg, rois, img
+                                               out.data_ptr(), _OUT_CODES[out_dtype], *mirror_args, _stream()), name)
+        ctx.cfg, ctx.rois, ctx.img, ctx.mir = cfg, rois, img, mir
         ctx.shapes = [tuple(f.shape) for f in fs]
         ctx.dtypes = [f.dtype for f in feats]
         ctx.nhwc = nhwc
@@ -103,16 +113,21 @@ class _RoIAlignFn(torch.autograd.Function):
     def backward(ctx, dout):
         scales, k_min, k_max, canon_s, canon_l, pooled, sampling = ctx.cfg[:7]
         dout = dout.float().contiguous()
+        mir = ctx.mir
         fmt = torch.channels_last if ctx.nhwc else torch.contiguous_format    # gradients of channels-last maps stay so
         one = len(set(ctx.dtypes)) == 1 and ctx.dtypes[0] in _OUT_CODES
         if ctx.det:                                 # every element written once, in a fixed order: uninitialised maps
             gdt = ctx.dtypes[0] if one else torch.float32           # mixed / fp64 maps: fp32 gradients, converted below
             name = "skg_roi_align_bwd_det_nhwc_x" if ctx.nhwc else "skg_roi_align_bwd_det_x"
             dtype_arg, images_arg = (_OUT_CODES[gdt],), (ctx.shapes[0][0],)    # the two arguments only these entries take
+            mirror_args = () if mir is None else (mir.data_ptr(),)
         else:                                       # float atomics into zeroed fp32 maps
             gdt = torch.float32
             name = "skg_roi_align_bwd_nhwc_f32" if ctx.nhwc else "skg_roi_align_bwd_f32"
             dtype_arg, images_arg = (), ()
+            mirror_args = () if mir is None else (mir.data_ptr(), int(mir.shape[0]))
+        if mir is not None:
+            name = name.replace("_bwd_det_", "_bwd_det_mirror_") if ctx.det else name.replace("_bwd_", "_bwd_mirror_")
         if ctx.det:
             dfs = [torch.empty(sh, device=dout.device, dtype=gdt, memory_format=fmt) for sh in ctx.shapes]
         elif ctx.nhwc:
@@ -123,7 +138,7 @@ class _RoIAlignFn(torch.autograd.Function):
         _capi.check(getattr(_capi.lib(), name)(ptrs, *dtype_arg, Hs, Ws, sc, len(dfs), ctx.shapes[0][1], k_min, k_max,
                                                float(canon_s), int(canon_l), ctx.rois.data_ptr(), ctx.img.data_ptr(),
                                                ctx.rois.shape[0], *images_arg, pooled, sampling, dout.data_ptr(),
-                                               _stream()), name)
+                                               *mirror_args, _stream()), name)
         if ctx.det and one:
             return (None, None, None) + tuple(dfs)
         return (None, None, None) + tuple(d.to(t) for d, t in zip(dfs, ctx.dtypes))
@@ -175,10 +190,23 @@ class MultiScaleRoIAlign(nn.Module):
         self.scales = [self.infer_scale(f.shape[-2:], (max_h, max_w)) for f in feats]
         self.k_min = int(-math.log2(self.scales[0])); self.k_max = int(-math.log2(self.scales[-1]))
 
-    def forward(self, x: Dict[str, Tensor], boxes: List[Tensor], image_shapes: List[Tuple[int, int]]) -> Tensor:
+    def forward(self, x: Dict[str, Tensor], boxes: List[Tensor], image_shapes: List[Tuple[int, int]],
+                mirror: Optional[Sequence[bool]] = None) -> Tensor:
+        """mirror: None, or one bool per image -- True pools that image as if every one of its maps were mirrored along W
+        (x[k][i].flip(-1)), with the same bits and without the copy; its boxes are given in the mirrored frame.  None and
+        all-False are the call without the keyword: no flag array, the same launches."""
         feats = [x[k] for k in self.featmap_names if k in x]
         if not feats:
             raise KeyError("none of featmap_names %s in the feature dict" % self.featmap_names)
+        if mirror is not None:
+            mirror = list(mirror)
+            if len(mirror) != len(boxes) or len(mirror) != int(feats[0].shape[0]):
+                raise ValueError("mirror has %d flags for %d images (%d lists of boxes)"
+                                 % (len(mirror), int(feats[0].shape[0]), len(boxes)))
+            if not all(isinstance(m, bool) for m in mirror):
+                raise ValueError("mirror must hold one bool per image (got %r)" % (mirror,))
+            if not any(mirror):
+                mirror = None
         dev = feats[0].device
         if dev.type != "cuda":
             raise _capi.SkgError("MultiScaleRoIAlign runs on a HIP device only")
@@ -195,7 +223,8 @@ class MultiScaleRoIAlign(nn.Module):
         L = len(feats)
         k_min, k_max = (self.k_min, self.k_max) if L > 1 else (0, 0)
         cfg = (list(self.scales), k_min, k_max, self.canonical_scale, self.canonical_level, self.output_size,
-               self.sampling_ratio, self._out_dtype(), self._deterministic())
+               self.sampling_ratio, self._out_dtype(), self._deterministic(),
+               None if mirror is None else torch.tensor(mirror, dtype=torch.int32).to(dev, non_blocking=True))
         if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
             return _RoIAlignFn.apply(cfg, rois, img, *feats)
         return _RoIAlignFn.forward(_NoCtx(), cfg, rois, img, *feats)

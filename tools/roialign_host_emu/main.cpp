@@ -8,7 +8,8 @@
 //
 //   cd tools/roialign_host_emu && clang++ -x c++ -std=c++20 -O1 -g -ffp-contract=off -fsanitize=address,undefined -pthread \
 //       -I. -I../../skghoi_amd/csrc -I../../include main.cpp -o emu && ./emu        (a few minutes: 256 threads per workgroup)
-// Exit status 0 and "bad 0" on the last line: everything agreed.  `./emu det` runs the deterministic backward part alone.
+// Exit status 0 and "bad 0" on the last line: everything agreed.  `./emu det` runs the deterministic backward part alone,
+// `./emu mirror` the mirrored entries alone (run_mirror below: against the plain entries on maps mirrored here).
 #include "skg_roialign.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -201,9 +202,111 @@ static int run_det(int dt, int Cc, int L0, int L, int pooled, int sampling, int 
     return (r1 || r2 || d1 || d2 || img1 || !covered) ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------- mirrored images
+// The *_mirror_* entries with flags {1, 0, 1} on three images (image 1 has no boxes) against the plain entries on copies of
+// the maps whose flagged images are mirrored along W: forward outputs byte for byte, deterministic gradients byte for byte
+// against the plain deterministic gradients mirrored back, both layouts, maps prefilled with 0xFF bytes; fp32 atomics within
+// 2e-5 of the deterministic mirrored gradients.  The boxes of DBOX cross and leave both edges, so the sanitizers see every
+// mirrored address.
+template <class T>
+static int run_mirror(int dt, int Cc, int L0, int L, int pooled, int sampling) {
+    const int B = 3, R = 12;
+    const int32_t flags_h[3] = {1, 0, 1};
+    std::mt19937 rng(Cc * 13 + dt);
+    std::normal_distribution<float> nd;
+    int32_t H[8], W[8]; float sc[8];
+    std::vector<T*> m[2], mf[2], g[2], gf[2];                          // [layout]: maps, mirrored copies, gradients of both routes
+    std::vector<float*> ga[2];                                         // fp32 atomics gradients
+    for (int k = 0; k < 2; ++k) { m[k].resize(L); mf[k].resize(L); g[k].resize(L); gf[k].resize(L); ga[k].resize(L); }
+    auto at = [&](int k, int l, int b, int c, int y, int x) {
+        return k == 0 ? (((size_t)b * Cc + c) * H[l] + y) * W[l] + x : (((size_t)b * H[l] + y) * W[l] + x) * Cc + c;
+    };
+    for (int l = 0; l < L; ++l) {
+        const int s = 4 << (l + L0);
+        H[l] = 120 / s; W[l] = 180 / s; sc[l] = 1.f / s;
+        const size_t n = (size_t)B * Cc * H[l] * W[l], bytes = (n * sizeof(T) + 15) / 16 * 16;
+        for (int k = 0; k < 2; ++k) {
+            m[k][l] = (T*)aligned_alloc(16, bytes); mf[k][l] = (T*)aligned_alloc(16, bytes);
+            g[k][l] = (T*)aligned_alloc(16, bytes); gf[k][l] = (T*)aligned_alloc(16, bytes);
+            memset(g[k][l], 0xFF, n * sizeof(T)); memset(gf[k][l], 0xFF, n * sizeof(T));
+            ga[k][l] = (float*)aligned_alloc(16, (n * 4 + 15) / 16 * 16); memset(ga[k][l], 0, n * 4);
+        }
+        for (int b = 0; b < B; ++b) for (int c = 0; c < Cc; ++c) for (int y = 0; y < H[l]; ++y) for (int x = 0; x < W[l]; ++x) {
+            const T v = conv<T>(nd(rng));
+            const int xf = flags_h[b] ? W[l] - 1 - x : x;
+            for (int k = 0; k < 2; ++k) { m[k][l][at(k, l, b, c, y, x)] = v; mf[k][l][at(k, l, b, c, y, xf)] = v; }
+        }
+    }
+    float* boxes = (float*)aligned_alloc(16, R * 16); memcpy(boxes, DBOX, R * 16);
+    int32_t* img = (int32_t*)aligned_alloc(16, 48); memcpy(img, DIMG, 48);
+    int32_t* flags = (int32_t*)aligned_alloc(16, 16); memcpy(flags, flags_h, 12);
+    const int kmin = L > 1 ? 2 + L0 : 0, kmax = L > 1 ? kmin + L - 1 : 0;
+    const size_t no = (size_t)R * Cc * pooled * pooled, ob = (no * sizeof(T) + 15) / 16 * 16;
+    float* dout = (float*)aligned_alloc(16, (no * 4 + 15) / 16 * 16);
+    for (size_t i = 0; i < no; ++i) dout[i] = nd(rng);
+    int bad = 0, rc = 0;
+    size_t fwd_diff = 0, fwd_same_as_plain = 0, det_diff = 0, nonzero = 0;
+    double worst = 0;
+    for (int k = 0; k < 2; ++k) {
+        void* o1 = aligned_alloc(16, ob); void* o2 = aligned_alloc(16, ob); void* o3 = aligned_alloc(16, ob);
+        memset(o1, 0xAB, no * sizeof(T)); memset(o2, 0xCD, no * sizeof(T)); memset(o3, 0xEF, no * sizeof(T));
+        if (k == 0) {
+            rc |= skg_roi_align_mirror_x((const void* const*)m[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, o1, dt, flags, B, nullptr);
+            rc |= skg_roi_align_x((const void* const*)mf[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, o2, dt, nullptr);
+            rc |= skg_roi_align_mirror_x((const void* const*)m[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, o3, dt, nullptr, 0, nullptr);
+            rc |= skg_roi_align_bwd_det_mirror_x((void* const*)g[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, B, pooled, sampling, dout, flags, nullptr);
+            rc |= skg_roi_align_bwd_det_x((void* const*)gf[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, B, pooled, sampling, dout, nullptr);
+            if (dt == 0) rc |= skg_roi_align_bwd_mirror_f32(ga[k].data(), H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, dout, flags, B, nullptr);
+        } else {
+            rc |= skg_roi_align_mirror_nhwc_x((const void* const*)m[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, o1, dt, flags, B, nullptr);
+            rc |= skg_roi_align_nhwc_x((const void* const*)mf[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, o2, dt, nullptr);
+            rc |= skg_roi_align_mirror_nhwc_x((const void* const*)m[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, o3, dt, nullptr, 0, nullptr);
+            rc |= skg_roi_align_bwd_det_mirror_nhwc_x((void* const*)g[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, B, pooled, sampling, dout, flags, nullptr);
+            rc |= skg_roi_align_bwd_det_nhwc_x((void* const*)gf[k].data(), dt, H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, B, pooled, sampling, dout, nullptr);
+            if (dt == 0) rc |= skg_roi_align_bwd_mirror_nhwc_f32(ga[k].data(), H, W, sc, L, Cc, kmin, kmax, 224.f, 4, boxes, img, R, pooled, sampling, dout, flags, B, nullptr);
+        }
+        fwd_diff += memcmp(o1, o2, no * sizeof(T)) != 0;
+        fwd_same_as_plain += memcmp(o1, o3, no * sizeof(T)) == 0;      // (the flags must change something)
+        for (int l = 0; l < L; ++l)
+            for (int b = 0; b < B; ++b) for (int c = 0; c < Cc; ++c) for (int y = 0; y < H[l]; ++y) for (int x = 0; x < W[l]; ++x) {
+                const int xf = flags_h[b] ? W[l] - 1 - x : x;
+                const T a = g[k][l][at(k, l, b, c, y, x)], w = gf[k][l][at(k, l, b, c, y, xf)];
+                det_diff += memcmp(&a, &w, sizeof(T)) != 0;
+                det_diff += k == 1 && memcmp(&a, &g[0][l][at(0, l, b, c, y, x)], sizeof(T)) != 0;    // both layouts: the same bits
+                if (dt == 0) {
+                    float av; memcpy(&av, &a, 4);
+                    worst = fmax(worst, fabs((double)av - ga[k][l][at(k, l, b, c, y, x)]));
+                    nonzero += av != 0.f;
+                }
+            }
+        free(o1); free(o2); free(o3);
+    }
+    printf("  mirror dt %d C %d L %d pooled %d samp %d: rc %d, forward buffers differing %zu (equal to the unflagged run %zu), "
+           "deterministic elements differing %zu, atomics max diff %.3e\n", dt, Cc, L, pooled, sampling, rc, fwd_diff,
+           fwd_same_as_plain, det_diff, worst);
+    if (rc || fwd_diff || fwd_same_as_plain || det_diff || worst > 2e-5 || (dt == 0 && nonzero == 0)) ++bad;
+    for (int k = 0; k < 2; ++k)
+        for (int l = 0; l < L; ++l) { free(m[k][l]); free(mf[k][l]); free(g[k][l]); free(gf[k][l]); free(ga[k][l]); }
+    free(boxes); free(img); free(flags); free(dout);
+    return bad;
+}
+
 int main(int argc, char** argv) {
     int bad = 0;
     const int Cs[3] = {8, 24, 72};
+    if (argc > 1 && !strcmp(argv[1], "mirror")) {                      // ./emu mirror: the mirrored entries alone
+        const int cfg[4][4] = {{0, 4, 7, 2}, {3, 1, 7, 2}, {0, 4, 7, 0}, {0, 4, 2, 2}};
+        for (int ci = 0; ci < 3; ++ci)
+            for (int k = 0; k < 4; ++k) {
+                if (ci == 2 && k > 0) continue;
+                printf("mirror C %d cfg %d\n", Cs[ci], k);
+                bad += run_mirror<float>(0, Cs[ci], cfg[k][0], cfg[k][1], cfg[k][2], cfg[k][3]);
+                bad += run_mirror<_Float16>(1, Cs[ci], cfg[k][0], cfg[k][1], cfg[k][2], cfg[k][3]);
+                bad += run_mirror<uint16_t>(2, Cs[ci], cfg[k][0], cfg[k][1], cfg[k][2], cfg[k][3]);
+            }
+        printf("bad %d\n", bad);
+        return bad != 0;
+    }
     const bool det_only = argc > 1 && !strcmp(argv[1], "det");       // ./emu det: the deterministic backward alone
     for (int ci = 0; ci < 3 && !det_only; ++ci) {
         const int Cc = Cs[ci];

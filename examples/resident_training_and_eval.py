@@ -11,9 +11,15 @@ With --flip the producer also writes the horizontally flipped variant of every t
 variants and the epoch serves one per image by the reference's coins -- `trainer.draw_flips(n)`, drawn once.  This is the
 flip of `trainer.hflip_sample` (the cached maps mirrored, the boxes with them), not the backbone run on the mirrored image.
 
+With --ema DECAY the optimizer keeps an exponential moving average of the weights on the device
+(`trainer.build_optimizer(ema_decay=DECAY, ema_warmup=True)`), the evaluation pass runs under it
+(`with optimizer.averaged(): trainer.test(...)`: parameters and average exchanged in place, exchanged back on exit) and the
+averaged weights are exported as an ordinary state dict (`optimizer.ema_model_state_dict(head)`).
+
 The companion of cached_inference_and_eval.py, which reads its shards batch by batch through FeatureShard.
 """
 import argparse
+import contextlib
 import os
 import sys
 import tempfile
@@ -30,7 +36,7 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=False):
+def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=False, ema=None):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_resident_")
     o2v = synth.hico_object_to_verb()
@@ -75,7 +81,8 @@ def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=Fals
     head.train()
     train_set.check_alignment(head)                                     # (both variants when there are two)
     net = trainer.wrap_ddp(head, dev)
-    opt = trainer.build_optimizer(net, lr=1e-4)
+    opt = trainer.build_optimizer(net, lr=1e-4) if ema is None else \
+        trainer.build_optimizer(net, lr=1e-4, ema_decay=ema, ema_warmup=True)
     torch.manual_seed(seed)
     coins = trainer.draw_flips(n_images) if flip else None              # DataFactory._flip: one coin per sample, drawn once
     tr = trainer.Trainer(net, opt, None, train_set.loader(batch_size=4, shuffle=True, seed=seed, flips=coins),
@@ -89,8 +96,14 @@ def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=Fals
     for t in eval_targets:
         for h in t["hoi"].tolist():
             num_gt[h] += 1
-    summ = trainer.test(head, eval_set.loader(batch_size=1, shuffle=False), evaluate.DeviceHOIEvaluator(num_gt, lut, device=dev),
-                        device=dev)
+    # (with --ema under the averaged weights: exchanged with the live ones in place for the duration of the block)
+    with (opt.averaged() if ema is not None else contextlib.nullcontext()):
+        summ = trainer.test(head, eval_set.loader(batch_size=1, shuffle=False),
+                            evaluate.DeviceHOIEvaluator(num_gt, lut, device=dev), device=dev)
+    if ema is not None:
+        path = os.path.join(out_dir, "head_ema.pt")
+        torch.save(opt.ema_model_state_dict(head), path)                # loads with strict=True into a fresh head
+        print("averaged weights after %d updates (decay %g, warm-up) -> %s" % (opt.ema_updates(), ema, path))
     if flip:
         print("flipped images this epoch: %d of %d" % (int(coins.sum()), n_images))
     print("images %d, arena %.1f MB (%s) + %.1f MB, %d training steps, last losses %s, mAP over classes with GT: %.4f, cache dir %s"
@@ -107,5 +120,7 @@ if __name__ == "__main__":
     ap.add_argument("--dtype", default="bf16", choices=["fp32", "fp16", "bf16"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--flip", action="store_true", help="produce both variants and train with the reference's fixed coins")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="keep a moving average of the weights, evaluate under it and export it")
     a = ap.parse_args()
-    main(a.images, a.per_shard, a.out, dtype=a.dtype, flip=a.flip)
+    main(a.images, a.per_shard, a.out, dtype=a.dtype, flip=a.flip, ema=a.ema)

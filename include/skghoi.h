@@ -808,6 +808,40 @@ int skg_adamw_guarded_f32(const skg_adamw_chunk* chunks, int n_chunks, double lr
 int skg_sizeof_step_status(void);                                   /* sizeof(skg_step_status): for bindings that mirror it */
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Exponential moving average of the parameters, kept ON THE DEVICE behind the optimizer's launches -- what validation,
+ * testing and exported checkpoints use.  A launch of its own (12 bytes per parameter: p and e read, e written), so that
+ * it works unchanged behind skg_adamw_f32, behind skg_adamw_guarded_f32 and behind a host-side step, and leaves their
+ * kernels alone.  chunks[c] = any number of consecutive elements of one parameter and of its average at the same
+ * element offset; one workgroup of 256 lanes per chunk, 16-byte accesses when BOTH pointers of the chunk are 16-byte
+ * aligned, scalar otherwise and for the tail.
+ *
+ * skg_ema_update_f32:  slot = t_host & 1;  n = state->updates[slot], read by every workgroup -- no launch with this
+ * t_host writes that slot;  apply = status == NULL || status->applied != 0, where status is the record the guarded AdamW
+ * launch of the same parameter group wrote EARLIER ON THE SAME STREAM: a skipped step leaves the average alone without
+ * the host ever learning of the skip.  Workgroup 0 writes state->updates[slot ^ 1] = n + apply, so consecutive launches
+ * on one stream must pass consecutive t_host (a launch counter of the average's own: NOT the optimizer's step number,
+ * which a host that has read the step record lowers).  Not applied: nothing else is written.  Applied:
+ * d = warmup ? min(decay, (1 + n) / (10 + n)) : decay in double, w = (float)(1 - d), and per element three separately
+ * rounded fp32 operations  e = e + w * (p - e)  -- never a fused multiply-add: a host restates the result bit for bit.
+ * p is only read.
+ * skg_ema_swap_f32: exchanges p and e element by element, same decomposition; twice is the identity.  Evaluation under
+ * the averaged weights = swap, evaluate, swap: pointers stay, only values move.
+ * Errors, before any launch: SKG_E_ARG for a null chunks with n_chunks > 0, n_chunks < 0, and for the update a decay
+ * outside [0, 1) or NaN, t_host < 0, a null state; SKG_E_ALIGN for state or a non-null status not 8-byte aligned.
+ * n_chunks == 0 returns 0 (nothing launched, state untouched).                                                        */
+typedef struct {
+    float* p; float* e;
+    uint32_t count, reserved;
+} skg_ema_chunk;
+typedef struct {
+    int64_t updates[2];        /* applied updates of the average (double-buffered, see above)                          */
+} skg_ema_state;
+int skg_sizeof_ema_state(void);                                     /* sizeof(skg_ema_state): for bindings that mirror it */
+int skg_ema_update_f32(const skg_ema_chunk* chunks, int n_chunks, double decay, int warmup, int64_t t_host,
+                       const skg_step_status* status, skg_ema_state* state, void* stream);
+int skg_ema_swap_f32(const skg_ema_chunk* chunks, int n_chunks, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Native launch plan of the fused TRAINING step's dense part: GraphHead.forward in training mode (HEAD:769-993; the
  * classifier HEAD:410-411) and its backward -- what the reference leaves to eager PyTorch + autograd inside
  * `net(...)` / `loss.backward()` (utils.py:213-229) -- as ONE host call per phase.  The call enqueues the whole launch

@@ -90,6 +90,16 @@ class StepStatus(C.Structure):
                 ("max_total_norm", _f32), ("reserved2", _i32), ("pending_skips", _i64 * 2)]
 
 
+class EmaChunk(C.Structure):
+    """Mirror of skg_ema_chunk: consecutive elements of one parameter and of its average."""
+    _fields_ = [("p", _vp), ("e", _vp), ("count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EmaState(C.Structure):
+    """Mirror of skg_ema_state: the applied updates of a group's average, double-buffered by launch parity."""
+    _fields_ = [("updates", _i64 * 2)]
+
+
 class CacheArray(C.Structure):
     """Mirror of skg_cache_array: one ragged array of a resident feature set and where its rows of a batch go."""
     _fields_ = [("src", _vp), ("src_off", _vp), ("row_elems", _i64), ("src_dtype", _i32), ("reserved", _i32),
@@ -197,6 +207,9 @@ PROTOTYPES = {
     "skg_adamw_guarded_f32": (C.c_int, [_vp, C.c_int] + [C.c_double] * 7 + [_i64, C.c_double, C.c_int, _vp, C.c_int, _vp,
                                                                           C.c_int, _vp, _vp]),
     "skg_sizeof_step_status": (C.c_int, []),
+    "skg_sizeof_ema_state": (C.c_int, []),
+    "skg_ema_update_f32": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _i64, _vp, _vp, _vp]),
+    "skg_ema_swap_f32": (C.c_int, [_vp, C.c_int, _vp]),
     "skg_ctx_set_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),
     "skg_ctx_get_tuning": (C.c_int, [_vp, C.POINTER(Tuning)]),
     "skg_ctx_make_current": (_vp, [_vp]),
@@ -315,6 +328,8 @@ def lib():
         raise SkgError("skg_exchange is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_exchange(), C.sizeof(Exchange)))
     if l.skg_abi_version() == ABI_VERSION and l.skg_sizeof_step_status() != C.sizeof(StepStatus):
         raise SkgError("skg_step_status is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_step_status(), C.sizeof(StepStatus)))
+    if l.skg_abi_version() == ABI_VERSION and l.skg_sizeof_ema_state() != C.sizeof(EmaState):
+        raise SkgError("skg_ema_state is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_ema_state(), C.sizeof(EmaState)))
     if l.skg_abi_version() == ABI_VERSION and l.skg_sizeof_cache_array() != C.sizeof(CacheArray):
         raise SkgError("skg_cache_array is %d bytes in libskghoi_hip.so, %d in the binding" % (l.skg_sizeof_cache_array(), C.sizeof(CacheArray)))
     if l.skg_abi_version() != ABI_VERSION:

@@ -10,6 +10,9 @@
 //   skg_adamw          : AdamW over every parameter of the training step in one launch (chunk table).
 //   skg_grad_sumsq / skg_adamw_guarded : the same step with global-norm clipping and a skip of non-finite gradients,
 //                        both decided on the device (a deterministic sum-of-squares pass, then AdamW reading g * coef).
+//   skg_ema_update / skg_ema_swap : exponential moving average of the parameters behind the optimizer's launches (it
+//                        follows the guarded step's applied / skipped decision on the device), and the in-place exchange
+//                        of parameters and average for evaluation.
 #include "skg_common.h"
 
 #define CK_THREADS 256
@@ -282,6 +285,92 @@ extern "C" int skg_adamw_guarded_f32(const skg_adamw_chunk* chunks, int n_chunks
 }
 
 extern "C" int skg_sizeof_step_status(void) { return (int)sizeof(skg_step_status); }
+
+// ------------------------------------------------------------------------------------------------ EMA of the parameters
+// e += w * (p - e) over a chunk table of (parameter, average) pairs, a launch of its own behind the optimizer's (plain,
+// guarded or stock: include/skghoi.h).  skg_adamw_kernel's decomposition: one workgroup per chunk, 16-byte accesses when
+// both pointers allow it (uniform per workgroup), scalar otherwise and for the tail.  Three separately rounded fp32
+// operations per element (the library is built with -ffp-contract=off): the host restates them bit for bit.
+__device__ __forceinline__ float skg_ema_one(float e, float p, float w) {
+    const float d = p - e;
+    const float s = w * d;
+    return e + s;
+}
+
+__global__ __launch_bounds__(256) void skg_ema_update_kernel(const skg_ema_chunk* __restrict__ chunks, double decay,
+                                                             int warmup, int slot, const skg_step_status* status,
+                                                             skg_ema_state* state) {
+    // the slot no launch with this t_host writes (workgroup 0 writes the other one)
+    const int64_t n = state->updates[slot];
+    const bool apply = status == nullptr || status->applied != 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) state->updates[slot ^ 1] = n + (apply ? 1 : 0);
+    if (!apply) return;
+    double d = decay;
+    if (warmup) {
+        const double r = (1.0 + (double)n) / (10.0 + (double)n);
+        if (r < d) d = r;
+    }
+    const float w = (float)(1.0 - d);
+    const skg_ema_chunk c = chunks[blockIdx.x];
+    const uint32_t cnt = c.count;
+    const bool vec = ((((uintptr_t)c.p) | ((uintptr_t)c.e)) & 15u) == 0;
+    uint32_t done = 0;
+    if (vec) {
+        const uint32_t n4 = cnt >> 2;
+        const float4* p4 = reinterpret_cast<const float4*>(c.p);
+        float4* e4 = reinterpret_cast<float4*>(c.e);
+        for (uint32_t i = threadIdx.x; i < n4; i += 256) {
+            const float4 p = p4[i];
+            float4 e = e4[i];
+            e.x = skg_ema_one(e.x, p.x, w); e.y = skg_ema_one(e.y, p.y, w);
+            e.z = skg_ema_one(e.z, p.z, w); e.w = skg_ema_one(e.w, p.w, w);
+            e4[i] = e;
+        }
+        done = 4u * n4;
+    }
+    for (uint32_t i = done + threadIdx.x; i < cnt; i += 256) c.e[i] = skg_ema_one(c.e[i], c.p[i], w);
+}
+
+// p <-> e per element: twice is the identity
+__global__ __launch_bounds__(256) void skg_ema_swap_kernel(const skg_ema_chunk* __restrict__ chunks) {
+    const skg_ema_chunk c = chunks[blockIdx.x];
+    const uint32_t cnt = c.count;
+    const bool vec = ((((uintptr_t)c.p) | ((uintptr_t)c.e)) & 15u) == 0;
+    uint32_t done = 0;
+    if (vec) {
+        const uint32_t n4 = cnt >> 2;
+        float4* p4 = reinterpret_cast<float4*>(c.p);
+        float4* e4 = reinterpret_cast<float4*>(c.e);
+        for (uint32_t i = threadIdx.x; i < n4; i += 256) {
+            const float4 p = p4[i], e = e4[i];
+            p4[i] = e; e4[i] = p;
+        }
+        done = 4u * n4;
+    }
+    for (uint32_t i = done + threadIdx.x; i < cnt; i += 256) {
+        const float p = c.p[i], e = c.e[i];
+        c.p[i] = e; c.e[i] = p;
+    }
+}
+
+extern "C" int skg_ema_update_f32(const skg_ema_chunk* chunks, int n_chunks, double decay, int warmup, int64_t t_host,
+                                  const skg_step_status* status, skg_ema_state* state, void* stream) {
+    if (n_chunks < 0 || (n_chunks > 0 && !chunks) || !(decay >= 0.0 && decay < 1.0) || t_host < 0 || !state) return SKG_E_ARG;
+    if (((((uintptr_t)state) | ((uintptr_t)status)) & 7u) != 0) return SKG_E_ALIGN;
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(skg_ema_update_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, chunks, decay,
+                       warmup ? 1 : 0, (int)(t_host & 1), status, state);
+    return skg_launch_status();
+}
+
+extern "C" int skg_ema_swap_f32(const skg_ema_chunk* chunks, int n_chunks, void* stream) {
+    if (n_chunks < 0 || (n_chunks > 0 && !chunks)) return SKG_E_ARG;
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(skg_ema_swap_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, chunks);
+    return skg_launch_status();
+}
+
+extern "C" int skg_sizeof_ema_state(void) { return (int)sizeof(skg_ema_state); }
 
 // ------------------------------------------------------------------------------------------------ bf16 twins
 thread_local skg_twin_map skg_tls_twin = {{nullptr, nullptr}, {nullptr, nullptr}, {0, 0}};

@@ -30,13 +30,16 @@ def limit_host_threads(ranks_on_host: int = 1, cap: int = 4) -> int:
 
 
 def build_optimizer(net: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-4, head_key: str = "interaction_head",
-                    max_grad_norm=None, skip_nonfinite: bool = False):
+                    max_grad_norm=None, skip_nonfinite: bool = False, ema_decay=None, ema_warmup: bool = False):
     """main:109-127: parameters whose name contains `head_key` train at lr, the rest at lr * 0.1.  A bare
     InteractionHead (no wrapper, so no 'interaction_head' in its names) is treated as all-head.
 
     max_grad_norm / skip_nonfinite: global-norm gradient clipping and the skip of a step with non-finite gradients, both
     decided on the device inside the optimizer's launches (SkgAdamW; the reference's sibling engine clips with
-    clip_grad_norm_, hicodet/detections/main_detr.py:320).  Parameters on the GPU only: there is no host version."""
+    clip_grad_norm_, hicodet/detections/main_detr.py:320).  Parameters on the GPU only: there is no host version.
+
+    ema_decay / ema_warmup: an exponential moving average of the trained parameters, kept on the device by the optimizer
+    behind its own launches (SkgAdamW: `averaged()`, `ema_model_state_dict()`); off by default."""
     named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
     head = [p for n, p in named if head_key in n]
     rest = [p for n, p in named if head_key not in n]
@@ -48,11 +51,14 @@ def build_optimizer(net: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-4
     # same update rule; on the GPU the multi-tensor "fused" implementation is one launch per step instead of ~10 per
     # parameter group walk (6 ms of host time for the head's 408 tensors)
     on_gpu = bool(named) and all(p.is_cuda for _, p in named)
+    ema = {} if ema_decay is None and not ema_warmup else dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
     if on_gpu:
         if max_grad_norm is None and not skip_nonfinite:
-            return SkgAdamW(groups, lr=lr, weight_decay=weight_decay, fused=True)
+            return SkgAdamW(groups, lr=lr, weight_decay=weight_decay, fused=True, **ema)
         return SkgAdamW(groups, lr=lr, weight_decay=weight_decay, fused=True, max_grad_norm=max_grad_norm,
-                        skip_nonfinite=skip_nonfinite)
+                        skip_nonfinite=skip_nonfinite, **ema)
+    if ema:
+        raise ValueError("ema_decay / ema_warmup need every trained parameter on the GPU (the average is kept by SkgAdamW)")
     if max_grad_norm is not None or skip_nonfinite:
         raise ValueError("max_grad_norm / skip_nonfinite need every trained parameter on the GPU (the guard runs inside "
                          "SkgAdamW's launches)")
@@ -528,7 +534,8 @@ def _plain_step(optimizer):
     hits, two more events on their queue) than the 0.07 ms it takes off the tail: bf16 1.27 -> 1.33 ms, fp32 2.48 -> 2.51,
     data-parallel route at world size 1 1.35 -> 1.38.  Results are bit-identical either way (tests/test_trainer.py)."""
     from torch.optim import optimizer as _topt
-    return isinstance(optimizer, SkgAdamW) and not optimizer.guarded and not optimizer._optimizer_step_pre_hooks and \
+    return isinstance(optimizer, SkgAdamW) and not optimizer.guarded and optimizer.ema_decay is None and \
+        not optimizer._optimizer_step_pre_hooks and \
         not optimizer._optimizer_step_post_hooks and not _topt._global_optimizer_pre_hooks and \
         not _topt._global_optimizer_post_hooks and _os.environ.get("SKG_ADAMW_IN_BACKWARD", "0") == "1"
 
@@ -788,15 +795,39 @@ class SkgAdamW(CachedFusedAdamW):
     finiteness test -- that route synchronises and, like torch, DOES scale `p.grad` in place.  The optimizer inside the
     backward (backward_slices) is declined: the norm needs every gradient.  Data parallel: call step() after the
     gradients of every parameter this optimizer owns have been exchanged -- all ranks then hold the same gradients and
-    derive, bit for bit, the same norm and the same decision without a further collective."""
+    derive, bit for bit, the same norm and the same decision without a further collective.
+
+    ema_decay (off by default: step() then issues exactly the launches above and allocates nothing else) keeps an
+    EXPONENTIAL MOVING AVERAGE of every parameter on the device: one flat fp32 buffer per parameter group (`ema_of(p)` is a
+    parameter's view of it) and, behind the AdamW launches of every step, one `skg_ema_update_f32` per group --
+    `e += (1 - d) * (p - e)`, three fp32 operations per element, d = ema_decay or with ema_warmup
+    min(ema_decay, (1 + n) / (10 + n)) for the n-th applied update.  On the guarded path the launch reads the group's step
+    record: a step the device skipped leaves the average and its update count alone, without the host learning of it.
+    The average starts, at the first step(), as a copy of the parameters as that step finds them.  `averaged()` is a context
+    manager that EXCHANGES parameters and average in place (one `skg_ema_swap_f32` per group on entry and on exit, also
+    when the body raises): pointers, the parameter arena's aliasing and `p.grad` stay, only values move, and every cache
+    derived from the values (the eval engine's packed weights behind their checksum, the bf16 twin, the arena's bias sums)
+    follows through the change detection it already has.  step() and nesting are errors inside it.  `ema_updates()`,
+    `ema_state_dict()` / `load_ema_state_dict()`, `reset_ema()` and `ema_model_state_dict(module)` read and restore it;
+    `state_dict()` is unchanged.  The in-backward optimizer is declined.  Data parallel: every rank holds the same
+    parameters and takes the same applied / skipped decision, hence the same average bit for bit with no collective."""
 
     CHUNK = 16384
     _DT = None
     _ST = None
 
-    def __init__(self, *args, max_grad_norm=None, skip_nonfinite=False, **kw):
+    def __init__(self, *args, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, **kw):
         super().__init__(*args, **kw)
         self._plans = {}
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= ema_decay < 1.0:
+                raise ValueError("ema_decay must lie in [0, 1) (None: no average), not %r" % (ema_decay,))
+        elif ema_warmup:
+            raise ValueError("ema_warmup=True needs ema_decay")
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self._ema = None                     # the average's buffers, state and chunk tables (made at the first step with it on)
+        self._averaging = False              # inside averaged(): parameters and average are exchanged
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if not max_grad_norm > 0.0:
@@ -869,9 +900,10 @@ class SkgAdamW(CachedFusedAdamW):
 
     def _stock_step(self, closure=None):
         """Everything the one-launch path does not cover.  With the guard on: the same semantics from the host -- torch's
-        clip_grad_norm_ (it scales p.grad in place), one finiteness read-back, the status records updated from here."""
+        clip_grad_norm_ (it scales p.grad in place), one finiteness read-back, the status records updated from here.
+        Returns (loss, applied): here the host knows whether the step was applied."""
         if not self.guarded:
-            return CachedFusedAdamW.step(self, closure)
+            return CachedFusedAdamW.step(self, closure), True
         import numpy as np
         loss = None
         if closure is not None:
@@ -879,7 +911,7 @@ class SkgAdamW(CachedFusedAdamW):
                 loss = closure()
         params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
         if not params:
-            return loss
+            return loss, False
         dev = params[0].device
         if self.max_grad_norm is not None:
             norm = torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
@@ -902,7 +934,7 @@ class SkgAdamW(CachedFusedAdamW):
                 r["max_total_norm"] = norm
             r["pending_skips"] = 0           # (every caller dropped its plans: the next ones re-read the step counts)
         self._gstat.copy_(torch.from_numpy(rec.view(np.int64).reshape(-1, 8)))
-        return loss
+        return loss, apply
 
     def _plan(self, gi, c):
         """Static part of a group's chunk table; None if the group does not qualify."""
@@ -986,6 +1018,8 @@ class SkgAdamW(CachedFusedAdamW):
         import numpy as np
         if self.guarded:                     # the norm needs every gradient: no update before the backward has ended
             return None
+        if self.ema_decay is not None:       # the average follows whole steps, behind step()'s launches
+            return None
         if len(self.param_groups) != 1 or getattr(self, "grad_scale", None) is not None or \
                 getattr(self, "found_inf", None) is not None:
             return None
@@ -1037,6 +1071,18 @@ class SkgAdamW(CachedFusedAdamW):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._averaging:
+            raise RuntimeError("step() inside averaged(): the parameters hold the average")
+        if self.ema_decay is None:
+            return self._step(closure)[0]
+        self._ema_begin()
+        loss, applied = self._step(closure)
+        self._ema_update(applied)
+        return loss
+
+    def _step(self, closure=None):
+        """The optimizer's own launches.  Returns (loss, applied): applied is True / False where the host took the step
+        itself, and on the one-launch paths (plain: always applied; guarded: the device decides) the groups' plans."""
         import numpy as np
         from . import _capi
         from .engine import _stream
@@ -1114,8 +1160,250 @@ class SkgAdamW(CachedFusedAdamW):
                                                   gpart.data_ptr(), _capi.GRADNORM_PARTIALS * len(sums), fs.data_ptr(),
                                                   fs.numel(), gstat.data_ptr() + 64 * gi, _stream()), "skg_adamw_guarded_f32")
             pl["host_step"] = t
-        return None
+        return None, [w[2] for w in work]
 
+    # ---- the moving average of the parameters (include/skghoi.h, skg_ema_update_f32 / skg_ema_swap_f32)
+    _ET = None
+
+    def _ema_layout(self):
+        return tuple((tuple(p.numel() for p in g["params"]), g["params"][0].device if g["params"] else None)
+                     for g in self.param_groups)
+
+    def _ema_alloc(self):
+        """One flat fp32 buffer per parameter group (every parameter's slice starts at a multiple of 4 elements) and one
+        skg_ema_state per group; made again, uninitialised, when the groups changed."""
+        em, lay = self._ema, self._ema_layout()
+        if em is not None and em["layout"] == lay:
+            return em
+        bufs, views, dev0 = [], [], None
+        for g in self.param_groups:
+            params = g["params"]
+            if any(p.dtype != torch.float32 or not p.is_contiguous() for p in params):
+                raise ValueError("ema_decay needs contiguous fp32 parameters")
+            dev = params[0].device if params else torch.device("cpu")
+            dev0 = dev if dev0 is None else dev0
+            offs, total = [], 0
+            for p in params:
+                offs.append(total)
+                total += (p.numel() + 3) // 4 * 4
+            buf = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+            bufs.append(buf)
+            views.append([buf[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)])
+        state = torch.zeros(len(self.param_groups), 2, dtype=torch.int64, device=dev0 or torch.device("cpu"))
+        t = 0 if em is None else em["t"]
+        self._ema = dict(layout=lay, bufs=bufs, views=views, state=state, t=t, init=False, tabs={},
+                         of={id(p): v for g, vs in zip(self.param_groups, views) for p, v in zip(g["params"], vs)})
+        for pl in self._plans.values():
+            pl.pop("ema", None)
+        return self._ema
+
+    def _ema_begin(self):
+        """In front of a step: the average starts as a copy of the parameters as this step finds them."""
+        em = self._ema
+        if em is not None and em["init"] and [len(v) for v in em["views"]] == [len(g["params"]) for g in self.param_groups]:
+            return em                        # (every step: the full comparison of the layout only where something is made)
+        em = self._ema_alloc()
+        if not em["init"]:
+            for g, vs in zip(self.param_groups, em["views"]):
+                if vs:
+                    torch._foreach_copy_(vs, [p.detach() for p in g["params"]])
+            em["state"].zero_()
+            em["init"] = True
+        return em
+
+    def _ema_table(self, gi, params, pl=None):
+        """(device table of skg_ema_chunk, rows) of group gi.  It depends on the parameters' addresses alone: kept with the
+        group's AdamW plan (which is made again when they move), otherwise revalidated against them."""
+        import numpy as np
+        if pl is not None and "ema" in pl:
+            return pl["ema"]
+        em = self._ema
+        ptrs = list(map(_data_ptr, params))
+        c = em["tabs"].get(gi)
+        if c is None or c[0] != ptrs:
+            if SkgAdamW._ET is None:
+                SkgAdamW._ET = np.dtype([("p", "u8"), ("e", "u8"), ("count", "u4"), ("res", "u4")])
+            numel = np.array([p.numel() for p in params], np.int64)
+            nch = (numel + self.CHUNK - 1) // self.CHUNK
+            tix = np.repeat(np.arange(len(params)), nch)
+            first = np.concatenate([[0], np.cumsum(nch)[:-1]])
+            off = (np.arange(int(nch.sum())) - np.repeat(first, nch)) * self.CHUNK
+            tab = np.zeros(len(tix), SkgAdamW._ET)
+            byte = (4 * off).astype(np.uint64)
+            tab["p"] = np.array(ptrs, np.uint64)[tix] + byte
+            tab["e"] = np.array([v.data_ptr() for v in em["views"][gi]], np.uint64)[tix] + byte
+            tab["count"] = np.minimum(self.CHUNK, numel[tix] - off).astype(np.uint32)
+            dtab = torch.from_numpy(tab.view(np.uint8).copy()).to(params[0].device)
+            c = em["tabs"][gi] = (ptrs, (dtab, len(tab)))
+        if pl is not None:
+            pl["ema"] = c[1]
+        return c[1]
+
+    def _ema_update(self, applied):
+        """Behind the step's own launches: one skg_ema_update_f32 per group.  applied = the groups' plans: the one-launch
+        paths (the guarded one hands the group's step record to the launch); True: the host applied the step; False: it
+        left the step out, and so does the average -- no launch, and the launch counter stays (consecutive launches pass
+        consecutive t_host: the counter is the average's own, grad_stats() never moves it)."""
+        if applied is False:
+            return
+        plans = applied if isinstance(applied, list) else None
+        import numpy as np
+        from . import _capi
+        from .engine import _stream
+        em = self._ema
+        t = em["t"]
+        lib = None
+        for gi, group in enumerate(self.param_groups):
+            params = group["params"]
+            if not params:
+                continue
+            pl = plans[gi] if plans is not None else None
+            if pl is not None or params[0].is_cuda:
+                dtab, rows = self._ema_table(gi, params, pl)
+                status = self._gstat.data_ptr() + 64 * gi if plans is not None and self.guarded else 0
+                lib = lib or _capi.lib()
+                _capi.check(lib.skg_ema_update_f32(dtab.data_ptr(), rows, self.ema_decay, int(self.ema_warmup), t, status,
+                                                   em["state"].data_ptr() + 16 * gi, _stream()), "skg_ema_update_f32")
+                continue
+            # host tensors: the launch's contract with torch ops (three separately rounded fp32 operations)
+            st = em["state"]
+            n = int(st[gi, t & 1])
+            st[gi, (t & 1) ^ 1] = n + 1
+            d = min(self.ema_decay, (1.0 + n) / (10.0 + n)) if self.ema_warmup else self.ema_decay
+            w = float(np.float32(1.0 - d))
+            vs = em["views"][gi]
+            diff = torch._foreach_sub([p.detach() for p in params], vs)
+            torch._foreach_mul_(diff, w)
+            torch._foreach_add_(vs, diff)
+        em["t"] = t + 1
+
+    def _ema_swap(self):
+        from . import _capi
+        from .engine import _stream
+        em, synced = self._ema, False
+        for gi, group in enumerate(self.param_groups):
+            params = group["params"]
+            if not params:
+                continue
+            if params[0].is_cuda:
+                dtab, rows = self._ema_table(gi, params)
+                _capi.check(_capi.lib().skg_ema_swap_f32(dtab.data_ptr(), rows, _stream()), "skg_ema_swap_f32")
+                synced = True
+            else:
+                vs, ps = em["views"][gi], [p.detach() for p in params]
+                keep = [v.clone() for v in vs]
+                torch._foreach_copy_(vs, ps)
+                torch._foreach_copy_(ps, keep)
+            # the values moved behind autograd's back: what falls back to the version counters (engine.ParamWatch for
+            # parameters its checksum does not cover) sees it there
+            torch.autograd.graph.increment_version(params)
+        if synced:
+            # other streams read the parameters with no event in between (the head's side stream takes their checksum for
+            # the batch it prepares): the exchange is complete before anything is enqueued behind it, on any stream
+            torch.cuda.current_stream().synchronize()
+
+    def _ema_required(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError("%s: this optimizer was built without ema_decay" % what)
+        if self._averaging:
+            raise RuntimeError("%s inside averaged(): parameters and average are exchanged" % what)
+
+    def averaged(self):
+        """Context manager: inside it the parameters hold the averaged values (and the average's buffers the live ones).
+        Before the first step the average IS the live weights and nothing moves."""
+        import contextlib
+        self._ema_required("averaged()")
+
+        @contextlib.contextmanager
+        def scope():
+            if self._averaging:
+                raise RuntimeError("averaged() inside averaged()")
+            moved = self._ema is not None and self._ema["init"] and self._ema["layout"] == self._ema_layout()
+            self._averaging = True
+            try:
+                if moved:
+                    with torch.no_grad():
+                        self._ema_swap()
+                try:
+                    yield self
+                finally:
+                    if moved:
+                        with torch.no_grad():
+                            self._ema_swap()
+            finally:
+                self._averaging = False
+        return scope()
+
+    def ema_of(self, p):
+        """The average of parameter p (a view of its group's buffer); None before the first step."""
+        self._ema_required("ema_of()")
+        em = self._ema
+        if em is None or not em["init"]:
+            return None
+        return em["of"][id(p)]
+
+    def ema_updates(self):
+        """Applied updates of the average (one device read; it waits for the steps enqueued so far)."""
+        self._ema_required("ema_updates()")
+        em = self._ema
+        if em is None or not em["init"] or em["state"].shape[0] == 0:
+            return 0
+        return int(em["state"][0, em["t"] & 1])
+
+    def reset_ema(self):
+        """The next step() starts the average again from the parameters it finds."""
+        self._ema_required("reset_ema()")
+        if self._ema is not None:
+            self._ema["init"] = False
+
+    def ema_state_dict(self):
+        """decay, warm-up, update count and, per parameter group, the averages in parameter order (copies)."""
+        self._ema_required("ema_state_dict()")
+        em = self._ema
+        init = em is not None and em["init"]
+        return dict(decay=self.ema_decay, warmup=self.ema_warmup, updates=self.ema_updates(),
+                    groups=[[v.detach().clone() for v in vs] for vs in em["views"]] if init else None)
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        self._ema_required("load_ema_state_dict()")
+        decay = float(sd["decay"])
+        if not 0.0 <= decay < 1.0:
+            raise ValueError("ema state: decay %r outside [0, 1)" % (decay,))
+        groups = sd.get("groups")
+        if groups is not None:
+            if len(groups) != len(self.param_groups):
+                raise ValueError("ema state: %d parameter groups, the optimizer has %d" % (len(groups), len(self.param_groups)))
+            for gi, (g, ts) in enumerate(zip(self.param_groups, groups)):
+                if len(ts) != len(g["params"]):
+                    raise ValueError("ema state: group %d holds %d tensors for %d parameters" % (gi, len(ts), len(g["params"])))
+                for k, (p, t) in enumerate(zip(g["params"], ts)):
+                    if tuple(t.shape) != tuple(p.shape):
+                        raise ValueError("ema state: group %d tensor %d has shape %s, the parameter %s"
+                                         % (gi, k, tuple(t.shape), tuple(p.shape)))
+        self.ema_decay, self.ema_warmup = decay, bool(sd["warmup"])
+        if groups is None:
+            return self.reset_ema()
+        em = self._ema_alloc()
+        for vs, ts in zip(em["views"], groups):
+            for v, t in zip(vs, ts):
+                v.copy_(t)
+        em["state"].fill_(int(sd["updates"]))               # both slots: whichever the next launch reads
+        em["init"] = True
+
+    def ema_model_state_dict(self, module):
+        """`module.state_dict()` (same keys, same order) with the averaged values for the parameters this optimizer owns and
+        detached copies of everything else: loads with strict=True into a fresh module."""
+        from collections import OrderedDict
+        self._ema_required("ema_model_state_dict()")
+        em = self._ema
+        of = em["of"] if em is not None and em["init"] else {}
+        named = dict(module.named_parameters(remove_duplicate=False))
+        out = OrderedDict()
+        for k, v in module.state_dict().items():
+            e = of.get(id(named[k])) if k in named else None
+            out[k] = (e if e is not None else v).detach().clone()
+        return out
 
 # ---------------------------------------------------------------------------------------------------- data side
 def seed_everything(seed: int = 42) -> None:
@@ -1286,11 +1574,19 @@ class Trainer:
     written.  "skip": the step is counted and the run goes on (needs lazy_losses=True with the default step: the eager
     NaN guard of `train_step` raises before the optimizer is reached).  With a guarded optimizer the record -- last and
     largest gradient norm, clipped and skipped steps -- is read on every rank (the decision to raise is the same on all
-    of them), printed beside the losses on rank 0 and kept in `last_report["grad_stats"]`."""
+    of them), printed beside the losses on rank 0 and kept in `last_report["grad_stats"]`.
+
+    eval_with_ema: validate() runs under `optimizer.averaged()` -- the validation mAP is that of the AVERAGED weights
+    (SkgAdamW(ema_decay=...)); the training-mAP meter keeps logging what the live weights produced.  With an averaging
+    optimizer the checkpoint gains the key "ema_state_dict" (the reference's five keys are unchanged); a checkpoint
+    without it makes the average start again from the loaded weights."""
 
     def __init__(self, net, optimizer, scheduler=None, train_loader=None, rank=0, cache_dir=None, step_fn=None,
                  print_interval=0, lazy_losses=False, val_loader=None, num_classes=117, train_meter=None, device=None,
-                 on_nonfinite="raise"):
+                 on_nonfinite="raise", eval_with_ema=False):
+        if eval_with_ema and getattr(optimizer, "ema_decay", None) is None:
+            raise ValueError("eval_with_ema=True needs an optimizer that keeps the average (SkgAdamW(ema_decay=...))")
+        self.eval_with_ema = bool(eval_with_ema)
         if on_nonfinite not in ("raise", "skip"):
             raise ValueError("on_nonfinite must be 'raise' or 'skip', not %r" % (on_nonfinite,))
         if on_nonfinite == "skip" and step_fn is None and not lazy_losses:
@@ -1339,8 +1635,15 @@ class Trainer:
         if results:
             meter.append_results([r for r in results if isinstance(r, dict)])
 
-    @torch.no_grad()
     def validate(self):
+        """The validation pass; with eval_with_ema under the optimizer's averaged weights."""
+        if self.eval_with_ema:
+            with self.optimizer.averaged():
+                return self._validate()
+        return self._validate()
+
+    @torch.no_grad()
+    def _validate(self):
         """utils.py:283-299: eval mode over the (sharded) validation loader -- batches carry their targets, so the head takes
         its eval-with-targets pass and the results carry `labels` -- into a fresh 117-class 11-point meter; returns the
         per-class APs (every rank holds them; the reference returns them on rank 0 only)."""
@@ -1395,10 +1698,16 @@ class Trainer:
     def _module(self):
         return self.net.module if isinstance(self.net, nn.parallel.DistributedDataParallel) else self.net
 
+    def _has_ema(self):
+        return getattr(self.optimizer, "ema_decay", None) is not None and hasattr(self.optimizer, "ema_state_dict")
+
     def state(self) -> dict:
-        return dict(iteration=self.iteration, epoch=self.epoch, model_state_dict=self._module().state_dict(),
-                    optim_state_dict=self.optimizer.state_dict(),
-                    scheduler_state_dict=(self.scheduler.state_dict() if self.scheduler is not None else None))
+        out = dict(iteration=self.iteration, epoch=self.epoch, model_state_dict=self._module().state_dict(),
+                   optim_state_dict=self.optimizer.state_dict(),
+                   scheduler_state_dict=(self.scheduler.state_dict() if self.scheduler is not None else None))
+        if self._has_ema():
+            out["ema_state_dict"] = self.optimizer.ema_state_dict()
+        return out
 
     def save_checkpoint(self, path=None) -> str:
         if path is None:
@@ -1413,6 +1722,11 @@ class Trainer:
         self._module().load_state_dict(ckpt["model_state_dict"])
         if ckpt.get("optim_state_dict") is not None:
             self.optimizer.load_state_dict(ckpt["optim_state_dict"])
+        if self._has_ema():
+            if ckpt.get("ema_state_dict") is not None:
+                self.optimizer.load_ema_state_dict(ckpt["ema_state_dict"])
+            else:
+                self.optimizer.reset_ema()   # the average starts again from the loaded weights
         if self.scheduler is not None and ckpt.get("scheduler_state_dict") is not None:
             self.scheduler.load_state_dict(ckpt["scheduler_state_dict"])
         self.epoch = int(ckpt.get("epoch", 0))

@@ -718,6 +718,40 @@ int skg_eval_associate_f32(const float* boxes_h, const float* boxes_o, const int
 int skg_eval_ap11_f64(const float* labels_sorted, const int64_t* class_off, const int64_t* num_gt, int n_classes,
                       const double* thresholds11, double* ap, void* stream);
 
+/* V-COCO role detection, scenarios 1 and 2 at once (the matching rule of the published V-COCO toolkit's role evaluation,
+ * `_do_role_eval` of vsrl_eval.VCOCOeval, which vcoco_evaluation.py:3-10 imports from outside the reference; restated,
+ * parity unpinned at that boundary), for a batch of images in the layout of skg_eval_associate_f32: boxes_h / boxes_o
+ * [sumP, 4], pair_off [n_images + 1], index / pred / scores [L] (index local to the image), cell_off [n_images + 1].
+ * class_ar [n_classes, 2] = (action id in 0 .. 25, role slot in 0 .. 1) of every predicted class.  Ground truth in the
+ * toolkit's encoding: persons [Ng, 4]; actions [Ng, 26] int8 (1 = does it, 0, -1 = not annotated: a person with any -1 is
+ * ignored); role_boxes [Ng, 26, 2, 4] (all four coordinates -1 = no role object annotated); gt_off [n_images + 1].
+ *
+ * IoU = the toolkit's pixel-index overlap in fp32: w = max(min(x2) - max(x1) + 1, 0), areas with + 1 on both sides.
+ * Per cell c of class (aid, rid): a NaN score drops it (label -1).  jmax = the first person of largest IoU with the
+ * detected person box (NaN never wins; without persons the cell is a false positive); an ignored jmax drops the cell.
+ * ov_role: where role_boxes[jmax, aid, rid] is all -1, scenario 1 asks for an empty detected role box (all 0.0 or all
+ * NaN) and scenario 2 accepts anything; else IoU(role ground truth, detected role box).  The cell is a candidate iff
+ * actions[jmax, aid] == 1, IoU_person >= thr and ov_role >= thr; of the candidates of one (image, class, jmax) the
+ * highest score is the true positive (label 1; equal scores: the lower cell index), every other kept cell is 0.
+ * labels_s1 / labels_s2 [L] int8, zeroed by the caller: a cell whose class is outside [0, n_classes) or whose index is
+ * outside its image's pairs keeps 0.  status (device int32, zero it first) receives the largest per-image person count
+ * above SKG_VCOCO_MAX_PERSONS (that image's labels are all 0 then).
+ * Errors, before any launch: SKG_E_ARG for n_images < 0, n_classes outside 1 .. SKG_VCOCO_MAX_CLASSES or a null pointer;
+ * SKG_E_ALIGN for boxes_h / boxes_o / persons / role_boxes not 16-byte aligned.  n_images == 0 launches nothing.        */
+#define SKG_VCOCO_ACTIONS 26
+#define SKG_VCOCO_MAX_CLASSES 52           /* 26 actions x 2 role slots */
+#define SKG_VCOCO_MAX_PERSONS 256
+int skg_eval_vcoco_match_f32(const float* boxes_h, const float* boxes_o, const int32_t* pair_off, const int64_t* index,
+                             const int64_t* pred, const float* scores, const int32_t* cell_off, int n_images,
+                             const int32_t* class_ar, int n_classes, const float* persons, const int8_t* actions,
+                             const float* role_boxes, const int32_t* gt_off, float thr, int8_t* labels_s1,
+                             int8_t* labels_s2, int32_t* status, void* stream);
+/* VOC all-point AP (the toolkit's voc_ap; pocket's DetectionAPMeter 'AUC'), float64, same inputs as skg_eval_ap11_f64:
+ * with tp_i the labels' running sum and prec_i = tp_i / (i + 1), ap[c] = (1 / num_gt[c]) sum_i label_i * max_{j >= i} prec_j
+ * -- the area under the precision-recall curve made monotone from the right.  0 without ground truth or detections.   */
+int skg_eval_ap_voc_f64(const float* labels_sorted, const int64_t* class_off, const int64_t* num_gt, int n_classes,
+                        double* ap, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Order-independent 64-bit checksum of the live parameters (bit patterns weighted by position) over a table of
  * chunks: chunk c covers `count` fp32 words at `ptr` (16-byte aligned) whose first word has global index `first`.

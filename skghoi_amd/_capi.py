@@ -11,6 +11,7 @@ DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(3)          # SKG_DTYPE_*: skg_roi_alig
 DTYPE_BYTES = 3                                      # SKG_DTYPE_BYTES: opaque rows (skg_cache_gather_x only)
 CACHE_MAX_ARRAYS, CACHE_MAX_BATCH = 16, 256          # SKG_CACHE_MAX_*
 MAX_DET_PER_IMAGE = 1024
+VCOCO_ACTIONS, VCOCO_MAX_CLASSES, VCOCO_MAX_PERSONS = 26, 52, 256      # SKG_VCOCO_*
 MAX_NODES = 160
 SPATIAL_LD = 48
 TRANSH_DIM = 50
@@ -256,6 +257,9 @@ PROTOTYPES = {
     "skg_eval_associate_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp,
                                          _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
     "skg_eval_ap11_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "skg_eval_vcoco_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                                           _f32, _vp, _vp, _vp, _vp]),
+    "skg_eval_ap_voc_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
     "skg_transh_sample_ws_ints": (C.c_int64, [C.c_int, C.c_int]),
     "skg_transh_sample_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),

@@ -15,6 +15,16 @@
 //   skg_eval_ap11_f64      : one workgroup per class over the globally sorted detections (class ascending, score
 //                            descending, stable): running true-positive count by block scans, eleven running maxima of
 //                            the precision, float64 like pocket.
+//
+// V-COCO (role AP, scenarios 1 and 2; the published toolkit's `_do_role_eval`, restated in include/skghoi.h -- the toolkit is
+// outside the reference tree, parity unpinned at that boundary):
+//
+//   skg_eval_vcoco_match_f32 : one workgroup per (image, class).  The image's persons and their ignore flags sit in LDS;
+//                              every lane takes cells of the class, finds the person of largest overlap and bids for it
+//                              with the same 64-bit key, once per scenario (two LDS key arrays).
+//   skg_eval_ap_voc_f64      : one workgroup per class over the same sorted labels: the class's true-positive total by a
+//                              block reduction, then one backward pass of reversed block scans carrying the suffix
+//                              true-positive count and the suffix maximum of the precision; float64.
 #include "skg_common.h"
 
 #define EV_MAX_GT 2048            // ground-truth pairs per image the association keeps in LDS
@@ -169,5 +179,186 @@ extern "C" int skg_eval_ap11_f64(const float* labels_sorted, const int64_t* clas
     if (!class_off || !num_gt || !thresholds11 || !ap) return SKG_E_ARG;
     hipLaunchKernelGGL(skg_eval_ap11_kernel, dim3(n_classes), dim3(256), 0, (hipStream_t)stream, labels_sorted, class_off,
                        num_gt, thresholds11, ap);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ V-COCO role matching
+__device__ __forceinline__ float ev_iou_px(const float4 a, const float4 b) {     // the toolkit's get_overlap: pixel indices
+    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x) + 1.f, 0.f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y) + 1.f, 0.f);
+    const float inter = w * h;
+    const float aa = (a.z - a.x + 1.f) * (a.w - a.y + 1.f), ab = (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
+    return inter / (aa + ab - inter);                        // a NaN coordinate makes its area, and so the IoU, NaN
+}
+
+__global__ __launch_bounds__(256) void skg_eval_vcoco_match_kernel(
+    const float* __restrict__ boxes_h, const float* __restrict__ boxes_o, const int32_t* __restrict__ pair_off,
+    const int64_t* __restrict__ index, const int64_t* __restrict__ pred, const float* __restrict__ scores,
+    const int32_t* __restrict__ cell_off, const int32_t* __restrict__ class_ar, const float* __restrict__ persons,
+    const int8_t* __restrict__ actions, const float* __restrict__ role_boxes, const int32_t* __restrict__ gt_off, float thr,
+    int8_t* __restrict__ labels_s1, int8_t* __restrict__ labels_s2, int32_t* __restrict__ status) {
+    __shared__ unsigned long long skey[2][SKG_VCOCO_MAX_PERSONS];
+    __shared__ float4 sper[SKG_VCOCO_MAX_PERSONS];
+    __shared__ int sact[SKG_VCOCO_MAX_PERSONS];              // actions[j, aid]; -2 for an ignored person
+    const int a = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+    const int c0 = cell_off[a], c1 = cell_off[a + 1];
+    const int g0 = gt_off[a], ng = gt_off[a + 1] - g0;
+    const int p0 = pair_off[a], np = pair_off[a + 1] - p0;
+    const int aid = class_ar[2 * k], rid = class_ar[2 * k + 1];
+    const bool known = aid >= 0 && aid < SKG_VCOCO_ACTIONS && rid >= 0 && rid < 2;
+    if (ng > SKG_VCOCO_MAX_PERSONS || !known) {              // uniform: reported, nothing written past the LDS arrays
+        if (tid == 0 && k == 0 && ng > SKG_VCOCO_MAX_PERSONS) atomicMax(status, ng);
+        for (int c = c0 + tid; c < c1; c += 256)
+            if (pred[c] == k) { labels_s1[c] = 0; labels_s2[c] = 0; }
+        return;
+    }
+    for (int g = tid; g < ng; g += 256) {
+        skey[0][g] = 0ull; skey[1][g] = 0ull;
+        sper[g] = *reinterpret_cast<const float4*>(persons + 4 * (int64_t)(g0 + g));
+        const int8_t* act = actions + (int64_t)(g0 + g) * SKG_VCOCO_ACTIONS;
+        bool ignored = false;
+        for (int t = 0; t < SKG_VCOCO_ACTIONS; ++t) ignored |= act[t] == -1;
+        sact[g] = ignored ? -2 : (int)act[aid];
+    }
+    __syncthreads();
+    for (int c = c0 + tid; c < c1; c += 256) {
+        if (pred[c] != k) continue;
+        const float s = scores[c];
+        const int64_t li = index[c];
+        int8_t o1 = 0, o2 = 0;                               // parked for the second pass: o1 = jmax, o2 = candidate bits
+        if (s != s) { o1 = -1; o2 = -1; }                    // NaN score: dropped
+        else if (ng > 0 && (uint64_t)li < (uint64_t)np) {
+            const float4 dh = *reinterpret_cast<const float4*>(boxes_h + 4 * ((int64_t)p0 + li));
+            float best = -1.f; int jmax = 0;
+            for (int g = 0; g < ng; ++g) {
+                const float v = ev_iou_px(sper[g], dh);
+                if (v > best) { best = v; jmax = g; }        // first maximum, NaN never wins
+            }
+            const int act = sact[jmax];
+            if (act == -2) { o1 = -1; o2 = -1; }             // the best person is not annotated: dropped
+            else if (act == 1 && best >= thr) {
+                const float4 dob = *reinterpret_cast<const float4*>(boxes_o + 4 * ((int64_t)p0 + li));
+                const float4 rb = *reinterpret_cast<const float4*>(
+                    role_boxes + 4 * ((((int64_t)(g0 + jmax)) * SKG_VCOCO_ACTIONS + aid) * 2 + rid));
+                float ov1, ov2;
+                if (rb.x == -1.f && rb.y == -1.f && rb.z == -1.f && rb.w == -1.f) {
+                    const bool empty = (dob.x == 0.f && dob.y == 0.f && dob.z == 0.f && dob.w == 0.f) ||
+                                       (dob.x != dob.x && dob.y != dob.y && dob.z != dob.z && dob.w != dob.w);
+                    ov1 = empty ? 1.f : 0.f; ov2 = 1.f;
+                } else {
+                    ov1 = ov2 = ev_iou_px(rb, dob);
+                }
+                const int bits = (ov1 >= thr ? 1 : 0) | (ov2 >= thr ? 2 : 0);
+                if (bits) {
+                    // (score, lower index wins ties) as one ordered 64-bit key; 0 = no bid.  s + 0: -0 bids like +0
+                    const unsigned long long key =
+                        ((unsigned long long)ev_orderable(s + 0.f) << 32) | (unsigned)(0xffffffffu - (unsigned)(c - c0));
+                    if (bits & 1) atomicMax(&skey[0][jmax], key);
+                    if (bits & 2) atomicMax(&skey[1][jmax], key);
+                    o1 = (int8_t)(uint8_t)jmax; o2 = (int8_t)bits;
+                }
+            }
+        }
+        labels_s1[c] = o1; labels_s2[c] = o2;
+    }
+    __syncthreads();
+    for (int c = c0 + tid; c < c1; c += 256) {               // the same lane reads back what it parked
+        if (pred[c] != k) continue;
+        const int bits = labels_s2[c];
+        if (bits <= 0) continue;                             // final already: 0 or -1 in both
+        const int jmax = (int)(uint8_t)labels_s1[c];
+        const unsigned long long key =
+            ((unsigned long long)ev_orderable(scores[c] + 0.f) << 32) | (unsigned)(0xffffffffu - (unsigned)(c - c0));
+        labels_s1[c] = ((bits & 1) && skey[0][jmax] == key) ? 1 : 0;
+        labels_s2[c] = ((bits & 2) && skey[1][jmax] == key) ? 1 : 0;
+    }
+}
+
+extern "C" int skg_eval_vcoco_match_f32(const float* boxes_h, const float* boxes_o, const int32_t* pair_off,
+                                        const int64_t* index, const int64_t* pred, const float* scores,
+                                        const int32_t* cell_off, int n_images, const int32_t* class_ar, int n_classes,
+                                        const float* persons, const int8_t* actions, const float* role_boxes,
+                                        const int32_t* gt_off, float thr, int8_t* labels_s1, int8_t* labels_s2,
+                                        int32_t* status, void* stream) {
+    if (n_images < 0 || n_classes <= 0 || n_classes > SKG_VCOCO_MAX_CLASSES) return SKG_E_ARG;
+    if (!boxes_h || !boxes_o || !pair_off || !index || !pred || !scores || !cell_off || !class_ar || !persons || !actions ||
+        !role_boxes || !gt_off || !labels_s1 || !labels_s2 || !status)
+        return SKG_E_ARG;
+    if (!skg_aligned16(boxes_h) || !skg_aligned16(boxes_o) || !skg_aligned16(persons) || !skg_aligned16(role_boxes))
+        return SKG_E_ALIGN;
+    if (n_images == 0) return 0;
+    hipLaunchKernelGGL(skg_eval_vcoco_match_kernel, dim3(n_images, n_classes), dim3(256), 0, (hipStream_t)stream, boxes_h,
+                       boxes_o, pair_off, index, pred, scores, cell_off, class_ar, persons, actions, role_boxes, gt_off, thr,
+                       labels_s1, labels_s2, status);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ VOC all-point AP
+// Same inputs as skg_eval_ap11_f64.  With tp_i the running sum of the labels and prec_i = tp_i / (i + 1),
+// ap[c] = (1 / num_gt[c]) sum_i label_i * max_{j >= i} prec_j.  The class is walked from its end in tiles of 256 with lane
+// t on position end - 1 - t, so that an inclusive scan over the lanes is a suffix scan over the positions.
+__global__ __launch_bounds__(256) void skg_eval_ap_voc_kernel(const float* __restrict__ labels_sorted,
+                                                              const int64_t* __restrict__ class_off,
+                                                              const int64_t* __restrict__ num_gt, double* __restrict__ ap) {
+    __shared__ double swsum[4], swmax[4], sred[4];
+    __shared__ double sbase_sum, sbase_max;
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t s0 = class_off[c], s1 = class_off[c + 1];
+    const double ng = (double)num_gt[c];
+    if (ng <= 0.0 || s1 <= s0) { if (tid == 0) ap[c] = 0.0; return; }
+    double total = 0.0;                                      // the class's true positives
+    for (int64_t i = s0 + tid; i < s1; i += 256) total += (double)labels_sorted[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, 64);
+    if (lane == 0) sred[wv] = total;
+    if (tid == 0) { sbase_sum = 0.0; sbase_max = 0.0; }
+    __syncthreads();
+    total = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+    double acc = 0.0;
+    for (int64_t e = s1; e > s0; e -= 256) {
+        const int64_t i = e - 1 - tid;
+        const bool valid = i >= s0;
+        const double y = valid ? (double)labels_sorted[i] : 0.0;
+        double inc = y;                                      // labels at positions >= i of this tile
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double o = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += o;
+        }
+        if (lane == 63) swsum[wv] = inc;
+        __syncthreads();
+        double behind = sbase_sum + (inc - y);               // labels at positions > i of the class
+        for (int w = 0; w < wv; ++w) behind += swsum[w];
+        double m = valid ? (total - behind) / (double)(i - s0 + 1) : 0.0;       // prec_i, then its suffix maximum
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double o = __shfl_up(m, off, 64);
+            if (lane >= off) m = fmax(m, o);
+        }
+        if (lane == 63) swmax[wv] = m;
+        __syncthreads();
+        m = fmax(m, sbase_max);
+        for (int w = 0; w < wv; ++w) m = fmax(m, swmax[w]);
+        acc += y * m;
+        __syncthreads();
+        if (tid == 0) {
+            sbase_sum += (swsum[0] + swsum[1]) + (swsum[2] + swsum[3]);
+            sbase_max = fmax(fmax(sbase_max, fmax(swmax[0], swmax[1])), fmax(swmax[2], swmax[3]));
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) sred[wv] = acc;
+    __syncthreads();
+    if (tid == 0) ap[c] = ((sred[0] + sred[1]) + (sred[2] + sred[3])) / ng;
+}
+
+extern "C" int skg_eval_ap_voc_f64(const float* labels_sorted, const int64_t* class_off, const int64_t* num_gt, int n_classes,
+                                   double* ap, void* stream) {
+    if (n_classes < 0) return SKG_E_ARG;
+    if (n_classes == 0) return 0;
+    if (!class_off || !num_gt || !ap) return SKG_E_ARG;
+    hipLaunchKernelGGL(skg_eval_ap_voc_kernel, dim3(n_classes), dim3(256), 0, (hipStream_t)stream, labels_sorted, class_off,
+                       num_gt, ap);
     return skg_launch_status();
 }

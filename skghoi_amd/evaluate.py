@@ -7,6 +7,8 @@ cache.py:28-95 (per-object .mat files of [boxes_h | boxes_o | score] in pixel-in
 cache_template.py:2-15 (V-COCO pickle of CacheTemplate dicts, protocol 2).  `pocket` (BoxPairAssociation,
 DetectionAPMeter) is a third-party package absent from the image and unpinned by the reference; its published
 semantics are restated here -- parity is unpinned at that boundary (oracle: oracle/eval_oracle.py, plain loops).
+V-COCO's AP_role (scenario 1 and 2) is computed in-process by VCOCOEvaluator / DeviceVCOCOEvaluator, the rule of the
+external toolkit restated under the same terms.
 
 Everything works on whatever device the result tensors live on (the association is a handful of small IoU matrices);
 nothing here is on the timed hot path.
@@ -117,6 +119,20 @@ class DetectionAPMeter:
         return out
 
 
+def _launch_ap(algorithm, lab_sorted, class_off, num_gt, ap, thr11):
+    """The per-class APs of globally sorted labels on the device: '11P' = skg_eval_ap11_f64 over the eleven recall
+    thresholds `thr11`, 'AUC' = skg_eval_ap_voc_f64 (VOC all-point area)."""
+    from . import _capi
+    from .engine import _stream
+    if algorithm == "AUC":
+        _capi.check(_capi.lib().skg_eval_ap_voc_f64(lab_sorted.data_ptr(), class_off.data_ptr(), num_gt.data_ptr(),
+                                                    ap.shape[0], ap.data_ptr(), _stream()), "skg_eval_ap_voc_f64")
+    else:
+        _capi.check(_capi.lib().skg_eval_ap11_f64(lab_sorted.data_ptr(), class_off.data_ptr(), num_gt.data_ptr(),
+                                                  ap.shape[0], thr11.data_ptr(), ap.data_ptr(), _stream()),
+                    "skg_eval_ap11_f64")
+
+
 class DeviceAPMeter:
     """The training-mAP / validation meter of the reference's engine (utils.py:208, 229, 263-282: every iteration the
     batch's (scores, prediction, labels) are moved to the host, all-gathered over the ranks and appended to a
@@ -125,13 +141,17 @@ class DeviceAPMeter:
     once, at the end of an epoch -- gathers the ranks' logs in one padded all_gather, sorts on the device and computes the
     per-class 11-point APs with skg_eval_ap11_f64 (float64), on every rank.  Same numbers as DetectionAPMeter over the same
     detections; ties between equal scores of one class resolve by rank, then arrival order (the reference: iteration, then
-    rank).  num_gt=None like the reference's meters: recall over the positives among the logged detections."""
+    rank).  num_gt=None like the reference's meters: recall over the positives among the logged detections.
+    algorithm="AUC": the VOC all-point area instead (skg_eval_ap_voc_f64; DetectionAPMeter's 'AUC' branch)."""
 
-    def __init__(self, num_cls, num_gt=None, device="cuda", group=None):
+    def __init__(self, num_cls, num_gt=None, device="cuda", group=None, algorithm="11P"):
+        if algorithm not in ("11P", "AUC"):
+            raise ValueError("unknown algorithm %s" % algorithm)
         self.num_cls = int(num_cls)
         self.num_gt = None if num_gt is None else [int(v) for v in num_gt]
         self.device = torch.device(device)
         self.group = group
+        self.algorithm = algorithm                               # "AUC": skg_eval_ap_voc_f64 (the host meter's AUC branch)
         self.reset()
 
     def reset(self):
@@ -153,8 +173,6 @@ class DeviceAPMeter:
 
     def eval(self):
         import torch.distributed as dist
-        from . import _capi
-        from .engine import _stream
         dev = self.device
         if self._log:
             mine = torch.stack([torch.cat([s.to(dev).float() for s, _, _ in self._log]),
@@ -169,7 +187,7 @@ class DeviceAPMeter:
         if mine.shape[0] == 0:
             return ap.cpu()
         if dev.type != "cuda":                                  # (CPU tensors: rehearsals over gloo) the host meter
-            m = DetectionAPMeter(self.num_cls, self.num_gt)
+            m = DetectionAPMeter(self.num_cls, self.num_gt, self.algorithm)
             m.append(mine[:, 0], mine[:, 1].long(), mine[:, 2])
             return m.eval()
         scores, cls, labels = mine[:, 0].contiguous(), mine[:, 1].long(), mine[:, 2].contiguous()
@@ -185,10 +203,7 @@ class DeviceAPMeter:
             num_gt = torch.zeros(self.num_cls, device=dev, dtype=torch.float64).index_add_(0, cls, labels.double()).long()
         else:
             num_gt = torch.as_tensor(self.num_gt, dtype=torch.int64, device=dev)
-        thr = torch.linspace(0, 1, 11, dtype=torch.float64).to(dev)
-        _capi.check(_capi.lib().skg_eval_ap11_f64(lab_sorted.data_ptr(), class_off.data_ptr(), num_gt.data_ptr(),
-                                                  self.num_cls, thr.data_ptr(), ap.data_ptr(), _stream()),
-                    "skg_eval_ap11_f64")
+        _launch_ap(self.algorithm, lab_sorted, class_off, num_gt, ap, torch.linspace(0, 1, 11, dtype=torch.float64).to(dev))
         return ap.cpu()
 
 
@@ -196,10 +211,10 @@ class HOIEvaluator:
     """The loop body of utils.test (utils.py:170-196) for any batch size: feed the head's result dict and the image's
     target (`boxes_h`, `boxes_o`, `hoi`), read full / rare / non-rare mAP at the end."""
 
-    def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None):
+    def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, algorithm="11P"):
         self.lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
             else hico_object_n_verb_to_interaction()
-        self.meter = DetectionAPMeter(int(self.lut.max()) + 1, num_gt=num_gt_test, algorithm="11P")
+        self.meter = DetectionAPMeter(int(self.lut.max()) + 1, num_gt=num_gt_test, algorithm=algorithm)
         self.min_iou = min_iou
         self.num_anno_train = None if num_anno_train is None else torch.as_tensor(num_anno_train)
 
@@ -241,9 +256,14 @@ class DeviceHOIEvaluator:
     """utils.test (utils.py:148-198) on the device, for batches of any size: interaction lookup + box-pair association in
     one launch per batch (skg_eval_associate_f32), detections kept on the device, and at the end two stable device sorts
     plus one launch for the 600 eleven-point APs (skg_eval_ap11_f64, float64).  Same numbers as HOIEvaluator (the host
-    restatement the oracle pins); use it when the head runs batched and the results should not travel to the host."""
+    restatement the oracle pins); use it when the head runs batched and the results should not travel to the host.
+    algorithm="AUC": the VOC all-point area instead (skg_eval_ap_voc_f64; the host meter's 'AUC' branch)."""
 
-    def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, device="cuda"):
+    def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, device="cuda",
+                 algorithm="11P"):
+        if algorithm not in ("11P", "AUC"):
+            raise ValueError("unknown algorithm %s" % algorithm)
+        self.algorithm = algorithm                               # "AUC": the 600 APs by skg_eval_ap_voc_f64
         self.device = torch.device(device)
         lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
             else hico_object_n_verb_to_interaction()
@@ -295,7 +315,6 @@ class DeviceHOIEvaluator:
 
     def summary(self):
         from . import _capi
-        from .engine import _stream
         dev = self.device
         if int(self.status.item()):
             raise _capi.SkgError("an image has %d ground-truth pairs; skg_eval_associate_f32 keeps at most 2048 per image"
@@ -311,9 +330,7 @@ class DeviceHOIEvaluator:
             lab_sorted = labels[order].contiguous()
             class_off = torch.zeros(self.num_cls + 1, dtype=torch.int64, device=dev)
             class_off[1:] = torch.cumsum(torch.bincount(hoi, minlength=self.num_cls), 0)
-            _capi.check(_capi.lib().skg_eval_ap11_f64(lab_sorted.data_ptr(), class_off.data_ptr(), self.num_gt.data_ptr(),
-                                                      self.num_cls, self.thr.data_ptr(), ap.data_ptr(), _stream()),
-                        "skg_eval_ap11_f64")
+            _launch_ap(self.algorithm, lab_sorted, class_off, self.num_gt, ap, self.thr)
         ap = ap.cpu()
         out = dict(ap=ap, full=float(ap.mean()))
         if self.num_anno_train is not None:                      # test/..._test.py:30-33
@@ -321,6 +338,277 @@ class DeviceHOIEvaluator:
             non_rare = torch.nonzero(self.num_anno_train >= 10).squeeze(1)
             out["rare"] = float(ap[rare].mean()); out["non_rare"] = float(ap[non_rare].mean())
         return out
+
+
+# ----------------------------------------------------------------------------------------------- V-COCO role AP
+# The 26 V-COCO actions and their roles (role 0 is always the agent), in the order of the toolkit's annotation files.
+VSRL_ACTION_ROLES = [("hold", ["agent", "obj"]), ("stand", ["agent"]), ("sit", ["agent", "instr"]), ("ride", ["agent", "instr"]),
+                     ("walk", ["agent"]), ("look", ["agent", "obj"]), ("hit", ["agent", "instr", "obj"]),
+                     ("eat", ["agent", "obj", "instr"]), ("jump", ["agent", "instr"]), ("lay", ["agent", "instr"]),
+                     ("talk_on_phone", ["agent", "instr"]), ("carry", ["agent", "obj"]), ("throw", ["agent", "obj"]),
+                     ("catch", ["agent", "obj"]), ("cut", ["agent", "instr", "obj"]), ("run", ["agent"]),
+                     ("work_on_computer", ["agent", "instr"]), ("ski", ["agent", "instr"]), ("surf", ["agent", "instr"]),
+                     ("skateboard", ["agent", "instr"]), ("smile", ["agent"]), ("drink", ["agent", "instr"]),
+                     ("kick", ["agent", "obj"]), ("point", ["agent", "instr"]), ("read", ["agent", "obj"]),
+                     ("snowboard", ["agent", "instr"])]
+_N_VSRL = len(VSRL_ACTION_ROLES)
+
+
+def _vcoco_class_table(actions):
+    """[(aid, rid)] of the head's classes '<action> <role>': aid = the action's index in VSRL_ACTION_ROLES, rid = the role's
+    position in the action's role list minus 1 ('hit instr' -> 0, 'hit obj' -> 1, 'eat obj' -> 0, 'eat instr' -> 1)."""
+    names = [a for a, _ in VSRL_ACTION_ROLES]
+    table = []
+    for name in actions:
+        parts = str(name).split()
+        if len(parts) != 2 or parts[0] not in names or parts[1] == "agent" \
+                or parts[1] not in VSRL_ACTION_ROLES[names.index(parts[0])][1]:
+            raise ValueError("%r is no '<action> <role>' of the V-COCO toolkit" % (name,))
+        aid = names.index(parts[0])
+        table.append((aid, VSRL_ACTION_ROLES[aid][1].index(parts[1]) - 1))
+    return table
+
+
+def vcoco_target_from_roidb(entry):
+    """One image's target for the V-COCO evaluators from a toolkit roidb entry (`boxes` [N, 4], `gt_classes` [N],
+    `gt_actions` [N, 26], `gt_role_id` [N, 26, 2]): the rows of class 1 (person) are kept, role ids become boxes, -1 where
+    the id is -1.  Returns {persons [G, 4] float32, actions [G, 26] int64, role_boxes [G, 26, 2, 4] float32}."""
+    boxes = torch.as_tensor(np.asarray(entry["boxes"]), dtype=torch.float32).reshape(-1, 4)
+    person = torch.as_tensor(np.asarray(entry["gt_classes"])).reshape(-1) == 1
+    actions = torch.as_tensor(np.asarray(entry["gt_actions"])).long().reshape(-1, _N_VSRL)[person]
+    role_id = torch.as_tensor(np.asarray(entry["gt_role_id"])).long().reshape(-1, _N_VSRL, 2)[person]
+    if role_id.numel() and int(role_id.max()) >= boxes.shape[0]:
+        raise IndexError("a gt_role_id is outside the entry's boxes")
+    role_boxes = torch.full(tuple(role_id.shape) + (4,), -1., dtype=torch.float32)
+    has = role_id >= 0
+    role_boxes[has] = boxes[role_id[has]]
+    return dict(persons=boxes[person], actions=actions, role_boxes=role_boxes)
+
+
+def _vcoco_target(target, device):
+    persons = torch.as_tensor(target["persons"]).to(device).float().reshape(-1, 4)
+    actions = torch.as_tensor(target["actions"]).to(device).long().reshape(-1, _N_VSRL)
+    role_boxes = torch.as_tensor(target["role_boxes"]).to(device).float().reshape(-1, _N_VSRL, 2, 4)
+    if not persons.shape[0] == actions.shape[0] == role_boxes.shape[0]:
+        raise ValueError("persons, actions and role_boxes of a V-COCO target disagree on the number of persons")
+    return persons, actions, role_boxes
+
+
+def _vsrl_iou(gt, det):
+    """The toolkit's get_overlap in fp32 on [..., 4] boxes: pixel-index widths (+ 1) in the intersection and both areas."""
+    iw = (torch.min(gt[..., 2], det[..., 2]) - torch.max(gt[..., 0], det[..., 0]) + 1.).clamp(min=0)
+    ih = (torch.min(gt[..., 3], det[..., 3]) - torch.max(gt[..., 1], det[..., 1]) + 1.).clamp(min=0)
+    inter = iw * ih
+    a_gt = (gt[..., 2] - gt[..., 0] + 1.) * (gt[..., 3] - gt[..., 1] + 1.)
+    a_det = (det[..., 2] - det[..., 0] + 1.) * (det[..., 3] - det[..., 1] + 1.)
+    return inter / (a_gt + a_det - inter)
+
+
+def _voc_ap(labels_sorted, npos):
+    """The toolkit's voc_ap (VOC all-point AP, float64) of one class's 0/1 labels in score order."""
+    lab = np.asarray(labels_sorted, dtype=np.float64)
+    tp = np.cumsum(lab); fp = np.cumsum(1.0 - lab)
+    rec = tp / float(npos)
+    prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
+    mrec = np.concatenate(([0.0], rec, [1.0])); mpre = np.concatenate(([0.0], prec, [0.0]))
+    mpre = np.maximum.accumulate(mpre[::-1])[::-1]               # monotone from the right
+    idx = np.where(mrec[1:] != mrec[:-1])[0] + 1
+    return float(np.sum((mrec[idx] - mrec[idx - 1]) * mpre[idx]))
+
+
+def _vcoco_summary(table, ap_s1, ap_s2, npos):
+    out = dict(role_ap_s1=ap_s1, role_ap_s2=ap_s2, npos=npos)
+    for tag, ap in (("s1", ap_s1), ("s2", ap_s2)):
+        out["mean_" + tag] = float(torch.nanmean(ap)) if len(table) else float("nan")
+        slots = []                                               # the 25 role slots of the 26 actions, as the toolkit prints them
+        for aid, (_, roles) in enumerate(VSRL_ACTION_ROLES):
+            for rid in range(len(roles) - 1):
+                if (aid, rid) in table:
+                    slots.append(float(ap[table.index((aid, rid))]))
+                else:                                            # not predicted: every ground truth of the slot is missed
+                    slots.append(0.0 if int(npos[aid]) > 0 else float("nan"))
+        out["toolkit_mean_" + tag] = float(torch.nanmean(torch.tensor(slots, dtype=torch.float64)))
+    return out
+
+
+class VCOCOEvaluator:
+    """AP_role of V-COCO in scenario 1 and scenario 2 (`_do_role_eval` of the published toolkit's vsrl_eval.VCOCOeval, which
+    vcoco_evaluation.py:3-10 imports from outside the reference; restated, parity unpinned at that boundary) from the head's
+    result dicts, on the host -- the restatement DeviceVCOCOEvaluator is checked against.
+
+    actions: the head's K class names '<action> <role>' (what vcoco_results takes).  A target is one image in the toolkit's
+    vcocodb encoding (vcoco_target_from_roidb): `persons` [G, 4] xyxy, `actions` [G, 26] (1 / 0 / -1 = not annotated; a
+    person with any -1 is ignored), `role_boxes` [G, 26, 2, 4] (all -1 = no role object annotated).
+
+    Per image and class (aid, rid), with the toolkit's pixel-index IoU in fp32: a cell with a NaN score is dropped; its
+    person is the first ground-truth person of largest IoU (NaN never wins; no persons: false positive); if that person is
+    ignored the cell is dropped; the role overlap is the IoU with role_boxes[jmax, aid, rid], or, where that is all -1, 1 for
+    an empty detected role box (all 0.0 or all NaN) in scenario 1 and always 1 in scenario 2; the cell is a candidate iff the
+    person does the action and both overlaps reach thr; the highest-scoring candidate of a person is the true positive
+    (equal scores: the lower cell index -- the toolkit's order on ties is unspecified), the others are false positives.
+    AP is the VOC all-point area over the kept cells of the class, float64, recall over npos[aid] = the persons doing the
+    action in EVERY image passed to `add`: callers must add every test image, also those without detections.
+
+    The head's own detections are scored: the score-0 template rows that vcoco_results' records carry for every other class
+    do not change scenario 1 (given positive scores and no degenerate role box at the origin) and are left out of
+    scenario 2, where the toolkit can count them for role-less persons."""
+    batched = True                                               # trainer.test feeds lists
+
+    def __init__(self, actions, thr=0.5):
+        self.table = _vcoco_class_table(actions)
+        self.thr = float(thr)
+        self.npos = torch.zeros(_N_VSRL, dtype=torch.int64)
+        self._scores, self._pred, self._labels = [], [], []
+
+    def _labels_of(self, output, target):
+        idx = output["index"].cpu().long()
+        bh = output["boxes_h"].cpu().float()[idx].reshape(-1, 4); bo = output["boxes_o"].cpu().float()[idx].reshape(-1, 4)
+        sc = output["scores"].cpu().float().reshape(-1); pr = output["prediction"].cpu().long().reshape(-1)
+        if ((pr < 0) | (pr >= len(self.table))).any():
+            raise IndexError("a prediction is outside the %d classes" % len(self.table))
+        persons, actions, role_boxes = _vcoco_target(target, "cpu")
+        self.npos += (actions == 1).sum(0)
+        n, G = sc.shape[0], persons.shape[0]
+        labels = torch.zeros(n, 2, dtype=torch.int8)
+        labels[torch.isnan(sc)] = -1
+        if n and G:
+            thr = torch.tensor(self.thr, dtype=torch.float32)
+            ov = _vsrl_iou(persons[None], bh[:, None])                                   # [n, G]
+            ovmax, jmax = torch.where(torch.isnan(ov), torch.full_like(ov, -1.), ov).max(1)      # first maximum
+            labels[(actions == -1).any(1)[jmax]] = -1
+            tab = torch.tensor(self.table, dtype=torch.int64).reshape(-1, 2)
+            aid, rid = tab[pr, 0], tab[pr, 1]
+            role_gt = role_boxes[jmax, aid, rid]
+            roleless = (role_gt == -1).all(1)
+            empty = (bo == 0).all(1) | torch.isnan(bo).all(1)
+            ov_role = _vsrl_iou(role_gt, bo)
+            base = (actions[jmax, aid] == 1) & (ovmax >= thr) & (labels[:, 0] == 0)
+            cand = torch.stack([base & torch.where(roleless, empty, ov_role >= thr),
+                                base & torch.where(roleless, torch.ones_like(empty), ov_role >= thr)], 1)
+            for s in range(2):
+                best = {}                                        # (class, person) -> winning cell
+                for c in torch.nonzero(cand[:, s]).squeeze(1).tolist():
+                    key = (int(pr[c]), int(jmax[c]))
+                    if key not in best or float(sc[c]) > float(sc[best[key]]):
+                        best[key] = c
+                if best:
+                    labels[list(best.values()), s] = 1
+        self._scores.append(sc); self._pred.append(pr); self._labels.append(labels)
+        return labels
+
+    def add(self, outputs, targets):
+        """outputs: the head's result dicts of a batch; targets: per image {persons, actions, role_boxes}.  Returns per image
+        the int8 [n_cells, 2] labels of scenario 1 and 2 (1 true positive, 0 false positive, -1 dropped)."""
+        if len(outputs) != len(targets):
+            raise ValueError("%d outputs for %d targets" % (len(outputs), len(targets)))
+        return [self._labels_of(o, t) for o, t in zip(outputs, targets)]
+
+    def summary(self):
+        """role_ap_s1 / role_ap_s2 [K] float64 (NaN where no person does the action), mean_s1 / mean_s2 over the K classes,
+        npos [26], toolkit_mean_s1 / _s2 over the toolkit's 25 role slots (a slot the head does not predict counts 0)."""
+        K = len(self.table)
+        scores = torch.cat(self._scores) if self._scores else torch.zeros(0)
+        pred = torch.cat(self._pred) if self._pred else torch.zeros(0, dtype=torch.int64)
+        labels = torch.cat(self._labels) if self._labels else torch.zeros(0, 2, dtype=torch.int8)
+        aps = []
+        for s in range(2):
+            ap = torch.full((K,), float("nan"), dtype=torch.float64)
+            for k, (aid, _) in enumerate(self.table):
+                if int(self.npos[aid]) > 0:
+                    m = (pred == k) & (labels[:, s] >= 0)
+                    order = torch.argsort(scores[m], descending=True, stable=True)
+                    ap[k] = _voc_ap(labels[m, s][order].numpy(), int(self.npos[aid]))
+            aps.append(ap)
+        return _vcoco_summary(self.table, aps[0], aps[1], self.npos.clone())
+
+
+class DeviceVCOCOEvaluator:
+    """VCOCOEvaluator on the device, for batches of any size: one skg_eval_vcoco_match_f32 launch per `add` (both scenarios),
+    detections, labels and npos kept on the device, and at the end, per scenario, two stable device sorts plus one
+    skg_eval_ap_voc_f64 launch (float64).  Same labels and APs as the host evaluator; same rule, same interface -- callers
+    must add every test image, also those without detections.  An image with more than 256 persons is reported by
+    `summary()`, like the 2048 ground-truth pairs of DeviceHOIEvaluator."""
+    batched = True
+
+    def __init__(self, actions, thr=0.5, device="cuda"):
+        from . import _capi
+        self.table = _vcoco_class_table(actions)
+        if len(self.table) > _capi.VCOCO_MAX_CLASSES:
+            raise ValueError("%d classes; skg_eval_vcoco_match_f32 takes at most %d" % (len(self.table), _capi.VCOCO_MAX_CLASSES))
+        self.thr = float(thr)
+        self.device = torch.device(device)
+        self.class_ar = torch.tensor(self.table, dtype=torch.int32).reshape(-1, 2).to(self.device).contiguous()
+        self.npos = torch.zeros(_N_VSRL, dtype=torch.int64, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._scores, self._pred, self._labels = [], [], []
+
+    def add(self, outputs, targets):
+        """As VCOCOEvaluator.add; the returned tensors are views of one device tensor."""
+        from . import _capi
+        from .engine import _stream
+        dev = self.device
+        n = len(outputs)
+        if n != len(targets):
+            raise ValueError("%d outputs for %d targets" % (n, len(targets)))
+        if n == 0:
+            return []
+        ppi = [int(o["boxes_h"].shape[0]) for o in outputs]; cpi = [int(o["scores"].shape[0]) for o in outputs]
+        cat = lambda k: torch.cat([o[k].reshape(-1, *o[k].shape[1:]) for o in outputs]).to(dev).contiguous()
+        boxes_h = cat("boxes_h").float().reshape(-1, 4); boxes_o = cat("boxes_o").float().reshape(-1, 4)
+        index = cat("index").long(); pred = cat("prediction").long(); scores = cat("scores").float().contiguous()
+        tg = [_vcoco_target(t, dev) for t in targets]
+        gts = [int(p.shape[0]) for p, _, _ in tg]
+        persons = torch.cat([p for p, _, _ in tg]).contiguous()
+        actions = torch.cat([a for _, a, _ in tg]).to(torch.int8).contiguous()
+        role_boxes = torch.cat([r for _, _, r in tg]).contiguous()
+        self.npos += (actions == 1).sum(0)
+        offs = np.zeros(3 * (n + 1), np.int32)                       # pair_off | cell_off | gt_off, n + 1 entries each
+        offs[1:n + 1] = np.cumsum(ppi); offs[n + 2:2 * n + 2] = np.cumsum(cpi); offs[2 * n + 3:] = np.cumsum(gts)
+        offs_d = torch.from_numpy(offs).to(dev)
+        L = int(sum(cpi))
+        labels = torch.zeros(2, max(L, 1), dtype=torch.int8, device=dev)
+        pad = lambda t: t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+        boxes_h, boxes_o, index, pred, scores, persons, actions, role_boxes = map(
+            pad, (boxes_h, boxes_o, index, pred, scores, persons, actions, role_boxes))
+        _capi.check(_capi.lib().skg_eval_vcoco_match_f32(
+            boxes_h.data_ptr(), boxes_o.data_ptr(), offs_d.data_ptr(), index.data_ptr(), pred.data_ptr(), scores.data_ptr(),
+            offs_d.data_ptr() + 4 * (n + 1), n, self.class_ar.data_ptr(), len(self.table), persons.data_ptr(),
+            actions.data_ptr(), role_boxes.data_ptr(), offs_d.data_ptr() + 8 * (n + 1), self.thr, labels[0].data_ptr(),
+            labels[1].data_ptr(), self.status.data_ptr(), _stream()), "skg_eval_vcoco_match_f32")
+        self._scores.append(scores[:L]); self._pred.append(pred[:L]); self._labels.append(labels[:, :L])
+        return list(labels[:, :L].t().split(cpi))
+
+    def summary(self):
+        """As VCOCOEvaluator.summary (tensors on the host)."""
+        from . import _capi
+        dev = self.device
+        if int(self.status.item()):
+            raise _capi.SkgError("an image has %d persons; skg_eval_vcoco_match_f32 keeps at most %d per image"
+                                 % (int(self.status.item()), _capi.VCOCO_MAX_PERSONS))
+        K = len(self.table)
+        npos = self.npos.cpu()
+        aid = torch.tensor([a for a, _ in self.table], dtype=torch.int64)
+        num_gt = self.npos[aid.to(dev)].contiguous()
+        aps = []
+        if self._scores:
+            scores = torch.cat(self._scores); pred = torch.cat(self._pred); labels = torch.cat(self._labels, dim=1)
+            if ((pred < 0) | (pred >= K)).any():
+                raise IndexError("a prediction is outside the %d classes" % K)
+        for s in range(2):
+            ap = torch.zeros(K, dtype=torch.float64, device=dev)
+            if self._scores and K:
+                keep = labels[s] >= 0                                # dropped cells never reach the ranking
+                sc, cls, lab = scores[keep], pred[keep], labels[s][keep].float()
+                o1 = torch.sort(sc, descending=True, stable=True).indices       # score descending, arrival order on ties
+                o2 = torch.sort(cls[o1], stable=True).indices                   # ... then class ascending, order kept
+                lab_sorted = lab[o1[o2]].contiguous()
+                class_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+                class_off[1:] = torch.cumsum(torch.bincount(cls, minlength=K), 0)
+                _launch_ap("AUC", lab_sorted, class_off, num_gt, ap, None)
+            ap = ap.cpu()
+            ap[npos[aid] == 0] = float("nan")
+            aps.append(ap)
+        return _vcoco_summary(self.table, aps[0], aps[1], npos)
 
 
 # ----------------------------------------------------------------------------------------------- exporters

@@ -1032,6 +1032,10 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             pix[mi][it] = (EPI == SKG_EPI_MUL_RELU && d.P && d.p_idx) ? d.p_idx[row] : row;
             qix[mi][it] = (EPI == SKG_EPI_MUL_RELU && d.Q && d.q_idx) ? d.q_idx[row] : row;
             oix[mi][it] = (EPI != SKG_EPI_RELU_DOT && d.out_rows) ? d.out_rows[row] : row;
+#ifdef SKG_EPI_KO_IDX                                   // (a row every table has: the timing tool's P / Q hold >= 128 rows)
+            pix[mi][it] = qix[mi][it] = wr * 32 * T + mi * 32 + r0l + it * RPI;
+            oix[mi][it] = row;
+#endif
         };
         if constexpr (PRE) {
 #pragma unroll
@@ -1039,34 +1043,49 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) row_indices(mi, it);
         }
+        // Timing builds only (tools/build_variants.sh -DSKG_EPI_KO_*, results are wrong), one part of this path each:
+        // _IDX the three index loads, _GATHER the P / Q / residual loads, _STORE every store, _TRANSPOSE the trip through LDS.
+        // (The stores hide behind a test that is false at run time, so that the products stay live.)
+#ifdef SKG_EPI_KO_STORE
+        const bool st = d.M < 0;
+#else
+        constexpr bool st = true;
+#endif
 #pragma unroll
         for (int mi = 0; mi < T; ++mi) {
+#ifndef SKG_EPI_KO_TRANSPOSE
 #pragma unroll
             for (int ni = 0; ni < T; ++ni)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     est[((r & 3) + 8 * (r >> 2) + 4 * lh) * EST_LD + ni * 32 + li] = acc[mi][ni][r];
+#endif
             const int rowb = m0 + wr * 32 * T + mi * 32 + r0l;
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int row = rowb + it * RPI;
                 if constexpr (!PRE) row_indices(mi, it);
+#ifdef SKG_EPI_KO_TRANSPOSE
+                const float4 a4 = make_float4(acc[mi][0][it], acc[mi][0][it + 8], acc[mi][T - 1][it], acc[mi][T - 1][it + 8]);
+#else
                 const float4 a4 = *reinterpret_cast<const float4*>(est + (it * RPI + r0l) * EST_LD + c4);
+#endif
                 float4 v = make_float4(a4.x + bia4.x, a4.y + bia4.y, a4.z + bia4.z, a4.w + bia4.w);
                 if (EPI == SKG_EPI_RELU_DOT) {
                     v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
                     float sdot = (v.x * dw4.x + v.y * dw4.y) + (v.z * dw4.z + v.w * dw4.w);
-                    if (d.C) *reinterpret_cast<float4*>(d.C + (int64_t)row * d.ldc + col) = v;
+                    if (st && d.C) *reinterpret_cast<float4*>(d.C + (int64_t)row * d.ldc + col) = v;
 #pragma unroll
                     for (int off = LPR / 2; off > 0; off >>= 1) sdot += __shfl_xor(sdot, off, 64);
-                    if ((lane % LPR) == 0) d.dot_partial[(int64_t)(bn * 2 + wc) * d.M + row] = sdot;
+                    if (st && (lane % LPR) == 0) d.dot_partial[(int64_t)(bn * 2 + wc) * d.M + row] = sdot;
                     continue;
                 }
                 const int orow = oix[mi][it];
                 if (EPI == SKG_EPI_MUL_RELU) {
-                    if (d.C_raw) *reinterpret_cast<float4*>(d.C_raw + (int64_t)row * d.ldc_raw + col) = v;
+                    if (st && d.C_raw) *reinterpret_cast<float4*>(d.C_raw + (int64_t)row * d.ldc_raw + col) = v;
                     if (orow < 0) continue;
                     float4 m = mb4;
+#ifndef SKG_EPI_KO_GATHER
                     if (d.P) {
                         const int pi = pix[mi][it];
                         const float4 t = *reinterpret_cast<const float4*>(d.P + (int64_t)pi * d.ldp + col);
@@ -1077,20 +1096,23 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                         const float4 t = *reinterpret_cast<const float4*>(d.Q + (int64_t)qi * d.ldq + col);
                         m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
                     }
+#endif
                     const float4 o = make_float4(fmaxf(v.x * m.x, 0.f), fmaxf(v.y * m.y, 0.f), fmaxf(v.z * m.z, 0.f), fmaxf(v.w * m.w, 0.f));
-                    if (!C16 || d.C) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = o;
-                    if constexpr (C16) { if (c16) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, o.x, o.y, o.z, o.w); }
+                    if (st && (!C16 || d.C)) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = o;
+                    if constexpr (C16) { if (st && c16) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, o.x, o.y, o.z, o.w); }
                     continue;
                 }
                 if (orow < 0) continue;
                 if (EPI == SKG_EPI_BIAS_RELU || EPI == SKG_EPI_BIAS_RES_RELU)
                     v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+#ifndef SKG_EPI_KO_GATHER
                 if (EPI == SKG_EPI_BIAS_RES_RELU) {
                     const float4 t = *reinterpret_cast<const float4*>(d.res + (int64_t)row * d.ldres + col);
                     v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
                 }
-                if (!C16 || d.C) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = v;
-                if constexpr (C16) { if (c16) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, v.x, v.y, v.z, v.w); }
+#endif
+                if (st && (!C16 || d.C)) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = v;
+                if constexpr (C16) { if (st && c16) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, v.x, v.y, v.z, v.w); }
             }
         }
         return;

@@ -1,6 +1,8 @@
 #!/bin/bash
 # developer aid: variant builds of skg_gemm.hip -> build/variants/lib_<name>.so (SKG_LIB selects one at run time)
 # usage: tools/build_variants.sh name="-DSKG_XABL=1 -DSKG_XNST=3" ...
+#        tools/build_variants.sh ko_idx=-DSKG_EPI_KO_IDX ko_gather=-DSKG_EPI_KO_GATHER ko_store=-DSKG_EPI_KO_STORE \
+#            ko_transpose=-DSKG_EPI_KO_TRANSPOSE     (fast-path epilogue knock-outs: tools/gemm_microbench.py 30 head)
 set -e
 cd "$(dirname "$0")/../skghoi_amd/csrc"
 mkdir -p ../../build/variants

@@ -3,7 +3,8 @@
 
   FPN-like feature maps + detections -> producer (device NMS/top-k, MultiScaleRoIAlign, global pool) -> feature shard
   + per-image detection JSON on disk -> batched inference from the cache -> 600-way HOI scores -> 11-point mAP
-  against synthetic ground truth -> HICO-DET .mat cells / V-COCO-style pickle.
+  against synthetic ground truth, in HICO-DET's Default and Known Object settings (full / rare / non-rare)
+  -> HICO-DET .mat cells / V-COCO-style pickle.
 
 Mirrors what a user of the reference does with hicodet/detections/adamixer_preprocessing.py, utils.test and cache.py.
 """
@@ -73,10 +74,13 @@ def main(n_images=16, batch=8, out_dir=None, seed=0):
         num_gt[hoi] += 1
         targets.append(dict(boxes_h=out["boxes_h"][p:p + 1].cpu(), boxes_o=out["boxes_o"][p:p + 1].cpu(),
                             hoi=torch.tensor([hoi])))
-    ev = evaluate.HOIEvaluator(num_gt, lut)
+    num_anno_train = [5 if h % 4 == 0 else 50 for h in range(600)]      # synthetic training counts: every fourth class is rare
+    ev = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True)
     for out, t in zip(outputs, targets):
         ev.add(out, t)
     summ = ev.summary()
+    for name, s in (("Default", summ), ("Known Object", summ["known_object"])):
+        print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
     cells = evaluate.hicodet_mat_cells(outputs, list(range(n_images)), n_images, lut)
     actions = ["verb%d obj" % v for v in range(117)]
     evaluate.save_vcoco_pickle(evaluate.vcoco_results(outputs[:2], [1, 2], actions), out_dir)

@@ -717,6 +717,27 @@ int skg_eval_associate_f32(const float* boxes_h, const float* boxes_o, const int
  * ap[c] = (1/11) sum_k max{precision_i : recall_i >= thresholds11[k]}; 0 without ground truth or detections.          */
 int skg_eval_ap11_f64(const float* labels_sorted, const int64_t* class_off, const int64_t* num_gt, int n_classes,
                       const double* thresholds11, double* ap, void* stream);
+/* HICO-DET's Known Object setting (Chao, Liu, Liu, Zeng, Deng: "Learning to Detect Human-Object Interactions", WACV 2018:
+ * an interaction class is scored only over the images that contain its object category; the Default setting scores it over
+ * all images).  The official evaluation code is outside the reference tree: the published rule is restated here, parity is
+ * unpinned at that boundary.  Launched behind skg_eval_associate_f32 on the same stream, on that launch's hoi_out.
+ *
+ * hoi_object [n_hoi]: the object category o with lut[o, v] == h for some verb v, -1 for an id the lut does not hold.
+ * An image CONTAINS category o iff one of its ground-truth pairs g has hoi_object[gt_hoi[g]] == o; ground-truth ids outside
+ * [0, n_hoi) are ignored (also the -1 padding row of a batch without ground truth), an image without ground truth contains
+ * nothing.  keep[c] = 1 iff hoi[c] is in [0, n_hoi) and the cell's image contains hoi_object[hoi[c]] -- also when the ground
+ * truth reaches that category only through ANOTHER interaction class of the same object -- else 0.  The Known Object AP of
+ * class h is the Default AP's rule (same num_gt, same labels of the Default association, same order) over the kept cells; a
+ * dropped cell is never a true positive (a ground-truth pair of class h puts its object in the image), so per class it is
+ * >= the Default AP.
+ * hoi / keep [L], cell_off / gt_off [n_images + 1], gt_hoi [Ng] as for skg_eval_associate_f32.  Any number of ground-truth
+ * pairs per image (nothing per pair is kept in LDS); n_obj <= SKG_EVAL_MAX_OBJECTS (the LDS bit mask).
+ * Errors, before any device call: SKG_E_ARG for n_images < 0, n_hoi <= 0 or n_obj <= 0; SKG_E_LIMIT for n_obj above
+ * SKG_EVAL_MAX_OBJECTS; n_images == 0 returns 0 and launches nothing; SKG_E_ARG for a null pointer.                      */
+#define SKG_EVAL_MAX_OBJECTS 1024
+int skg_eval_known_object_u8(const int32_t* hoi, const int32_t* cell_off, int n_images, const int32_t* hoi_object,
+                             int n_hoi, int n_obj, const int64_t* gt_hoi, const int32_t* gt_off, uint8_t* keep,
+                             void* stream);
 
 /* V-COCO role detection, scenarios 1 and 2 at once (the matching rule of the published V-COCO toolkit's role evaluation,
  * `_do_role_eval` of vsrl_eval.VCOCOeval, which vcoco_evaluation.py:3-10 imports from outside the reference; restated,

@@ -12,6 +12,7 @@ DTYPE_BYTES = 3                                      # SKG_DTYPE_BYTES: opaque r
 CACHE_MAX_ARRAYS, CACHE_MAX_BATCH = 16, 256          # SKG_CACHE_MAX_*
 MAX_DET_PER_IMAGE = 1024
 VCOCO_ACTIONS, VCOCO_MAX_CLASSES, VCOCO_MAX_PERSONS = 26, 52, 256      # SKG_VCOCO_*
+EVAL_MAX_OBJECTS = 1024                              # SKG_EVAL_MAX_OBJECTS: skg_eval_known_object_u8's LDS bit mask
 MAX_NODES = 160
 SPATIAL_LD = 48
 TRANSH_DIM = 50
@@ -257,6 +258,7 @@ PROTOTYPES = {
     "skg_eval_associate_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp,
                                          _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
     "skg_eval_ap11_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "skg_eval_known_object_u8": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "skg_eval_vcoco_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
                                            _f32, _vp, _vp, _vp, _vp]),
     "skg_eval_ap_voc_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),

@@ -15,6 +15,8 @@
 //   skg_eval_ap11_f64      : one workgroup per class over the globally sorted detections (class ascending, score
 //                            descending, stable): running true-positive count by block scans, eleven running maxima of
 //                            the precision, float64 like pocket.
+//   skg_eval_known_object_u8 : HICO-DET's Known Object setting, launched behind the association: one workgroup per image,
+//                            the object categories of its ground truth as an LDS bit mask, one keep flag per cell.
 //
 // V-COCO (role AP, scenarios 1 and 2; the published toolkit's `_do_role_eval`, restated in include/skghoi.h -- the toolkit is
 // outside the reference tree, parity unpinned at that boundary):
@@ -110,6 +112,47 @@ extern "C" int skg_eval_associate_f32(const float* boxes_h, const float* boxes_o
     hipLaunchKernelGGL(skg_eval_associate_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, boxes_h, boxes_o,
                        object, pair_off, index, pred, scores, cell_off, lut, n_obj, n_verb, gt_h, gt_o, gt_hoi, gt_off,
                        min_iou, hoi_out, labels, status);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ Known Object setting
+// HICO-DET's second setting (Chao et al., WACV 2018; the official evaluation is outside the reference tree, the published
+// rule is restated in include/skghoi.h -- parity unpinned at that boundary): a cell of class h counts only in the images
+// whose ground truth holds the object category of h, through whichever interaction class.  One workgroup per image: the
+// object categories of the image's ground-truth pairs as a bit mask in LDS (nothing per pair: no cap on the pairs), then one
+// flag per cell.
+__global__ __launch_bounds__(256) void skg_eval_known_object_kernel(
+    const int32_t* __restrict__ hoi, const int32_t* __restrict__ cell_off, const int32_t* __restrict__ hoi_object, int n_hoi,
+    int n_obj, const int64_t* __restrict__ gt_hoi, const int32_t* __restrict__ gt_off, uint8_t* __restrict__ keep) {
+    __shared__ unsigned smask[SKG_EVAL_MAX_OBJECTS / 32];
+    const int a = blockIdx.x, tid = threadIdx.x;
+    for (int w = tid; w < (n_obj + 31) / 32; w += 256) smask[w] = 0u;      // n_obj <= SKG_EVAL_MAX_OBJECTS: checked by the entry
+    __syncthreads();
+    const int g1 = gt_off[a + 1];
+    for (int g = gt_off[a] + tid; g < g1; g += 256) {
+        const int64_t h = gt_hoi[g];
+        if (h < 0 || h >= n_hoi) continue;                   // the -1 padding row, ids outside the classes
+        const int o = hoi_object[h];
+        if (o >= 0 && o < n_obj) atomicOr(&smask[o >> 5], 1u << (o & 31));
+    }
+    __syncthreads();
+    const int c1 = cell_off[a + 1];
+    for (int c = cell_off[a] + tid; c < c1; c += 256) {
+        const int h = hoi[c];
+        const int o = (h >= 0 && h < n_hoi) ? hoi_object[h] : -1;
+        keep[c] = (o >= 0 && o < n_obj) ? (uint8_t)((smask[o >> 5] >> (o & 31)) & 1u) : (uint8_t)0;
+    }
+}
+
+extern "C" int skg_eval_known_object_u8(const int32_t* hoi, const int32_t* cell_off, int n_images, const int32_t* hoi_object,
+                                        int n_hoi, int n_obj, const int64_t* gt_hoi, const int32_t* gt_off, uint8_t* keep,
+                                        void* stream) {
+    if (n_images < 0 || n_hoi <= 0 || n_obj <= 0) return SKG_E_ARG;
+    if (n_obj > SKG_EVAL_MAX_OBJECTS) return SKG_E_LIMIT;
+    if (n_images == 0) return 0;
+    if (!hoi || !cell_off || !hoi_object || !gt_hoi || !gt_off || !keep) return SKG_E_ARG;
+    hipLaunchKernelGGL(skg_eval_known_object_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, hoi, cell_off,
+                       hoi_object, n_hoi, n_obj, gt_hoi, gt_off, keep);
     return skg_launch_status();
 }
 

@@ -7,6 +7,8 @@ cache.py:28-95 (per-object .mat files of [boxes_h | boxes_o | score] in pixel-in
 cache_template.py:2-15 (V-COCO pickle of CacheTemplate dicts, protocol 2).  `pocket` (BoxPairAssociation,
 DetectionAPMeter) is a third-party package absent from the image and unpinned by the reference; its published
 semantics are restated here -- parity is unpinned at that boundary (oracle: oracle/eval_oracle.py, plain loops).
+HICO-DET's Known Object setting (the second half of the published table; Chao et al., WACV 2018) is computed in-process by
+the same two evaluators (`known_object=True`), the rule of the official evaluation restated under the same terms.
 V-COCO's AP_role (scenario 1 and 2) is computed in-process by VCOCOEvaluator / DeviceVCOCOEvaluator, the rule of the
 external toolkit restated under the same terms.
 
@@ -207,16 +209,87 @@ class DeviceAPMeter:
         return ap.cpu()
 
 
+# ----------------------------------------------------------------------------------------------- HICO-DET settings
+# HICO-DET is reported in two settings (Chao et al., "Learning to Detect Human-Object Interactions", WACV 2018): Default --
+# every interaction class over all test images, what utils.test computes -- and Known Object -- a class only over the images
+# that contain its object category.  The official evaluation code (MATLAB, fed by the .mat exporter below) is outside the
+# reference tree: the published rule is restated (include/skghoi.h, skg_eval_known_object_u8), parity unpinned at that boundary.
+_SUMMARY_KEYS = ("ap", "full", "rare", "non_rare", "known_object")
+
+
+def hoi_object_of(object_n_verb_to_interaction):
+    """[num_hoi] int64: the object category o with lut[o, v] == h for some verb v; -1 for an id the lut never holds.  An id
+    under two object categories has no Known Object setting: ValueError."""
+    lut = torch.as_tensor(object_n_verb_to_interaction).cpu().long()
+    out = torch.full((max(int(lut.max()) + 1, 0),), -1, dtype=torch.int64)
+    for o, v in torch.nonzero(lut >= 0).tolist():
+        h = int(lut[o, v])
+        if int(out[h]) not in (-1, o):
+            raise ValueError("interaction %d appears under the object categories %d and %d" % (h, int(out[h]), o))
+        out[h] = o
+    return out
+
+
+def _check_splits(splits, num_cls):
+    """{name: class indices} -> {name: int64 tensor}; the zero-shot splits (unseen combination / object / verb) are such
+    index lists over the same APs."""
+    out = {}
+    for name, idx in (splits or {}).items():
+        if name in _SUMMARY_KEYS:
+            raise ValueError("the split name %r collides with a key of summary()" % (name,))
+        idx = [int(i) for i in idx]
+        if not idx:
+            raise ValueError("the split %r is empty" % (name,))
+        if min(idx) < 0 or max(idx) >= num_cls:
+            raise ValueError("the split %r has an index outside [0, %d)" % (name, num_cls))
+        out[name] = torch.tensor(idx, dtype=torch.int64)
+    return out
+
+
+def _hoi_summary(ap, num_anno_train, splits):
+    out = dict(ap=ap, full=float(ap.mean()))
+    if num_anno_train is not None:                               # test/..._test.py:30-33
+        rare = torch.nonzero(num_anno_train < 10).squeeze(1)
+        non_rare = torch.nonzero(num_anno_train >= 10).squeeze(1)
+        out["rare"] = float(ap[rare].mean()); out["non_rare"] = float(ap[non_rare].mean())
+    for name, idx in splits.items():
+        out[name] = float(ap[idx].mean())
+    return out
+
+
 class HOIEvaluator:
     """The loop body of utils.test (utils.py:170-196) for any batch size: feed the head's result dict and the image's
-    target (`boxes_h`, `boxes_o`, `hoi`), read full / rare / non-rare mAP at the end."""
+    target (`boxes_h`, `boxes_o`, `hoi`), read full / rare / non-rare mAP at the end.
 
-    def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, algorithm="11P"):
+    splits={name: class indices}: `summary()` also holds the mean AP over each named list.  known_object=True: `add` also
+    flags the cells the Known Object setting keeps (`last_keep`: [bool tensor] of the most recent call, in the shape of its
+    labels) and `summary()["known_object"]` holds that setting's `ap`, `full`, `rare` / `non_rare` and named splits -- the
+    same AP, num_gt, labels and order over the kept cells only."""
+
+    def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, algorithm="11P",
+                 known_object=False, splits=None):
         self.lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
             else hico_object_n_verb_to_interaction()
-        self.meter = DetectionAPMeter(int(self.lut.max()) + 1, num_gt=num_gt_test, algorithm=algorithm)
+        num_cls = int(self.lut.max()) + 1
+        self.meter = DetectionAPMeter(num_cls, num_gt=num_gt_test, algorithm=algorithm)
         self.min_iou = min_iou
         self.num_anno_train = None if num_anno_train is None else torch.as_tensor(num_anno_train)
+        self.splits = _check_splits(splits, num_cls)
+        self.known_object = bool(known_object)
+        if self.known_object:
+            self.hoi_object = hoi_object_of(self.lut)
+            self.ko_meter = DetectionAPMeter(num_cls, num_gt=num_gt_test, algorithm=algorithm)
+            self.last_keep = []
+
+    def _keep_of(self, inter, t_hoi):
+        """The Known Object flags of one image's cells: the image's ground truth holds the object category of the cell's class."""
+        ho = self.hoi_object.to(inter.device)
+        present = torch.zeros(self.lut.shape[0], dtype=torch.bool, device=inter.device)
+        g = t_hoi.reshape(-1).long()
+        o = ho[g[(g >= 0) & (g < ho.shape[0])]]                  # ids outside the classes are ignored
+        present[o[o >= 0]] = True
+        oc = ho[inter]
+        return (oc >= 0) & present[oc.clamp(min=0)]
 
     def interactions_of(self, output):
         idx = output["index"]
@@ -240,15 +313,16 @@ class HOIEvaluator:
                                               boxes_h[det].view(-1, 4), boxes_o[det].view(-1, 4),
                                               scores[det].view(-1), self.min_iou)
         self.meter.append(scores, inter, labels)
+        if self.known_object:
+            keep = self._keep_of(inter, t_hoi)
+            self.ko_meter.append(scores[keep], inter[keep], labels[keep])
+            self.last_keep = [keep]
         return labels
 
     def summary(self):
-        ap = self.meter.eval()
-        out = dict(ap=ap, full=float(ap.mean()))
-        if self.num_anno_train is not None:                      # test/..._test.py:30-33
-            rare = torch.nonzero(self.num_anno_train < 10).squeeze(1)
-            non_rare = torch.nonzero(self.num_anno_train >= 10).squeeze(1)
-            out["rare"] = float(ap[rare].mean()); out["non_rare"] = float(ap[non_rare].mean())
+        out = _hoi_summary(self.meter.eval(), self.num_anno_train, self.splits)
+        if self.known_object:
+            out["known_object"] = _hoi_summary(self.ko_meter.eval(), self.num_anno_train, self.splits)
         return out
 
 
@@ -257,10 +331,14 @@ class DeviceHOIEvaluator:
     one launch per batch (skg_eval_associate_f32), detections kept on the device, and at the end two stable device sorts
     plus one launch for the 600 eleven-point APs (skg_eval_ap11_f64, float64).  Same numbers as HOIEvaluator (the host
     restatement the oracle pins); use it when the head runs batched and the results should not travel to the host.
-    algorithm="AUC": the VOC all-point area instead (skg_eval_ap_voc_f64; the host meter's 'AUC' branch)."""
+    algorithm="AUC": the VOC all-point area instead (skg_eval_ap_voc_f64; the host meter's 'AUC' branch).
+    splits / known_object: as for HOIEvaluator.  known_object=True adds one skg_eval_known_object_u8 launch per `add`, behind
+    the association and without a host synchronisation (`last_keep`: per-image uint8 views of one device tensor), and at the
+    end the same two sorts and AP launch over the kept cells."""
 
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, device="cuda",
-                 algorithm="11P"):
+                 algorithm="11P", known_object=False, splits=None):
+        from . import _capi
         if algorithm not in ("11P", "AUC"):
             raise ValueError("unknown algorithm %s" % algorithm)
         self.algorithm = algorithm                               # "AUC": the 600 APs by skg_eval_ap_voc_f64
@@ -276,6 +354,14 @@ class DeviceHOIEvaluator:
         self.thr = torch.linspace(0, 1, 11, dtype=torch.float64).to(self.device)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._scores, self._hoi, self._labels = [], [], []
+        self.splits = _check_splits(splits, self.num_cls)
+        self.known_object = bool(known_object)
+        if self.known_object:
+            if self.n_obj > _capi.EVAL_MAX_OBJECTS:
+                raise ValueError("%d object categories; skg_eval_known_object_u8 takes at most %d"
+                                 % (self.n_obj, _capi.EVAL_MAX_OBJECTS))
+            self.hoi_object = hoi_object_of(lut).to(self.device, torch.int32).contiguous()
+            self._keep, self.last_keep = [], []
 
     def add(self, outputs, targets):
         """outputs: the head's result dicts of a batch (HEAD:317-322); targets: per image {boxes_h, boxes_o, hoi}.
@@ -285,6 +371,8 @@ class DeviceHOIEvaluator:
         dev = self.device
         n = len(outputs)
         if n == 0:
+            if self.known_object:
+                self.last_keep = []
             return []
         ppi = [int(o["boxes_h"].shape[0]) for o in outputs]; cpi = [int(o["scores"].shape[0]) for o in outputs]
         cat = lambda k, dt=None: torch.cat([o[k].reshape(-1, *o[k].shape[1:]) for o in outputs]).to(dev).contiguous()
@@ -311,7 +399,26 @@ class DeviceHOIEvaluator:
             gt_h.data_ptr(), gt_o.data_ptr(), gt_hoi.data_ptr(), offs_d.data_ptr() + 8 * (n + 1), self.min_iou,
             hoi.data_ptr(), labels.data_ptr(), self.status.data_ptr(), _stream()), "skg_eval_associate_f32")
         self._scores.append(scores[:L]); self._hoi.append(hoi[:L]); self._labels.append(labels[:L])
+        if self.known_object:                                        # behind the association, on its hoi_out
+            keep = torch.zeros(max(L, 1), dtype=torch.uint8, device=dev)
+            _capi.check(_capi.lib().skg_eval_known_object_u8(
+                hoi.data_ptr(), offs_d.data_ptr() + 4 * (n + 1), n, self.hoi_object.data_ptr(), self.num_cls, self.n_obj,
+                gt_hoi.data_ptr(), offs_d.data_ptr() + 8 * (n + 1), keep.data_ptr(), _stream()), "skg_eval_known_object_u8")
+            self._keep.append(keep[:L]); self.last_keep = list(keep[:L].split(cpi))
         return list(labels[:L].split(cpi))
+
+    def _ap_of(self, scores, hoi, labels):
+        """The per-class APs of (scores, classes, labels) in arrival order: two stable sorts and one launch."""
+        dev = self.device
+        ap = torch.zeros(self.num_cls, dtype=torch.float64, device=dev)
+        o1 = torch.sort(scores, descending=True, stable=True).indices      # score descending, arrival order on ties
+        o2 = torch.sort(hoi[o1], stable=True).indices                      # ... then class ascending, order kept
+        order = o1[o2]
+        lab_sorted = labels[order].contiguous()
+        class_off = torch.zeros(self.num_cls + 1, dtype=torch.int64, device=dev)
+        class_off[1:] = torch.cumsum(torch.bincount(hoi, minlength=self.num_cls), 0)
+        _launch_ap(self.algorithm, lab_sorted, class_off, self.num_gt, ap, self.thr)
+        return ap
 
     def summary(self):
         from . import _capi
@@ -319,24 +426,18 @@ class DeviceHOIEvaluator:
         if int(self.status.item()):
             raise _capi.SkgError("an image has %d ground-truth pairs; skg_eval_associate_f32 keeps at most 2048 per image"
                                  % int(self.status.item()))
-        ap = torch.zeros(self.num_cls, dtype=torch.float64, device=dev)
+        ap = ap_ko = torch.zeros(self.num_cls, dtype=torch.float64, device=dev)
         if self._scores:
             scores = torch.cat(self._scores); hoi = torch.cat(self._hoi).long(); labels = torch.cat(self._labels)
             if (hoi < 0).any():
                 raise IndexError("a predicted (object, verb) pair is not a valid interaction")
-            o1 = torch.sort(scores, descending=True, stable=True).indices      # score descending, arrival order on ties
-            o2 = torch.sort(hoi[o1], stable=True).indices                      # ... then class ascending, order kept
-            order = o1[o2]
-            lab_sorted = labels[order].contiguous()
-            class_off = torch.zeros(self.num_cls + 1, dtype=torch.int64, device=dev)
-            class_off[1:] = torch.cumsum(torch.bincount(hoi, minlength=self.num_cls), 0)
-            _launch_ap(self.algorithm, lab_sorted, class_off, self.num_gt, ap, self.thr)
-        ap = ap.cpu()
-        out = dict(ap=ap, full=float(ap.mean()))
-        if self.num_anno_train is not None:                      # test/..._test.py:30-33
-            rare = torch.nonzero(self.num_anno_train < 10).squeeze(1)
-            non_rare = torch.nonzero(self.num_anno_train >= 10).squeeze(1)
-            out["rare"] = float(ap[rare].mean()); out["non_rare"] = float(ap[non_rare].mean())
+            ap = self._ap_of(scores, hoi, labels)
+            if self.known_object:                                    # the same rule over the kept cells (their order kept)
+                keep = torch.cat(self._keep).bool()
+                ap_ko = self._ap_of(scores[keep], hoi[keep], labels[keep])
+        out = _hoi_summary(ap.cpu(), self.num_anno_train, self.splits)
+        if self.known_object:
+            out["known_object"] = _hoi_summary(ap_ko.cpu(), self.num_anno_train, self.splits)
         return out
 
 

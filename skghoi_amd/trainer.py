@@ -1505,7 +1505,9 @@ def _with_lookahead(loader, enabled=True, depth=1):
 def test(net, test_loader, evaluator, device=None, lookahead=True):
     """utils.py:148-198 (`test`): eval mode, ONE image per forward (`assert len(output) == 1`), every result associated
     with the image's ground-truth pairs and logged into the 600-class 11-point meter; returns `evaluator.summary()`
-    (`ap` per class, `full`, and `rare` / `non_rare` when the evaluator knows the training counts).
+    (`ap` per class, `full`, and `rare` / `non_rare` when the evaluator knows the training counts; one mean per named class
+    list of the evaluator's `splits`; with `known_object=True` a `known_object` dict of the same keys, HICO-DET's second
+    setting).
 
     test_loader yields batches whose LAST element is the list of targets ({boxes_h, boxes_o, hoi}) and whose other
     elements are the network's arguments -- for the bare interaction head (inference from cached features / detections):

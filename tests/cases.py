@@ -4,6 +4,8 @@ OUTPUTS are committed under tests/golden/.
 
 Edge cases follow SURVEY.md section 8(c): n_h == 0, n == 1, only humans, zero-area box (NaN scrub), score ties,
 NMS-active input, V-COCO configuration (K = 24, human_idx = 1), skipped images inside a batch (Q9 offset bug).
+The CLUTTERED cases add overlapping detections (NMS and caps active, partial human-object IoU, ground truth that meets
+several detections on both sides of the association threshold); tests/test_cluttered_cases_host.py says what they must show.
 """
 import numpy as np
 import torch
@@ -46,6 +48,47 @@ def _nms_image(C, p, human_idx):
     return dict(boxes=torch.from_numpy(base), labels=torch.from_numpy(labels), scores=torch.from_numpy(scores),
                 feat3=torch.from_numpy(rs.standard_normal((1, 256, 6, 9)).astype(np.float32)), hw=(800, 1200),
                 pooled_seed=771)
+
+
+def cluttered_detections(rs, n, human_idx, n_cls):
+    """Boxes in clusters (heavy overlap inside a cluster), few classes, quantised scores (many ties)."""
+    k = max(1, n // 4)
+    centres = rs.uniform(50, 700, (k, 2)); sizes = rs.uniform(30, 300, (k, 2))
+    c = rs.randint(0, k, n)
+    xy = centres[c] + rs.normal(0, 12, (n, 2)); wh = np.abs(sizes[c] + rs.normal(0, 15, (n, 2))) + 1
+    boxes = np.concatenate([xy - wh / 2, xy + wh / 2], 1).astype(np.float32)
+    labels = rs.choice([human_idx, human_idx, 3, 7, 11][:n_cls], n).astype(np.int64)
+    scores = (rs.randint(1, 20, n) / 20.0).astype(np.float32)
+    return dict(boxes=torch.from_numpy(boxes), labels=torch.from_numpy(labels), scores=torch.from_numpy(scores))
+
+
+CLUTTERED_HW = [(800, 1200), (750, 1000), (900, 840)]
+
+
+def _cluttered_images(seed, counts, human_idx):
+    """Three images of `cluttered_detections` (every box at least 1 px wide and high: the zero-area boxes stay in "nanbox")
+    with a feature map each, sizes CLUTTERED_HW."""
+    rs = np.random.RandomState(seed)
+    imgs = []
+    for n, hw in zip(counts, CLUTTERED_HW):
+        d = cluttered_detections(rs, n, human_idx, 5)
+        d.update(feat3=torch.from_numpy(rs.standard_normal((1, 256, 6, 9)).astype(np.float32)), hw=hw)
+        imgs.append(d)
+    return imgs
+
+
+# The cluttered cases, all at test width (C = 8, p = 2, 6 x 9 feature maps).  Detections overlap inside clusters, so class-wise
+# NMS removes boxes, the caps truncate, and the human-object IoU and directional features of the 46-d encoding are non-trivial.
+# With targets, the ground truth is a +-`jitter` px move of a detection: it overlaps SEVERAL detections of its cluster, at IoUs
+# on both sides of the 0.5 association threshold (HEAD:703-719).  NMS at 0.7 there, so that near-duplicates (and, in training,
+# detections next to an appended ground-truth box) survive.  The seeds are chosen so that the conditions asserted by
+# tests/test_cluttered_cases_host.py hold; "<case>@<seed>" builds the case with another one.
+CLUTTERED = {
+    "cluttered_eval": dict(seed=9213, counts=(40, 23, 9), caps=(5, 6), nms=0.5),
+    "cluttered_vcoco": dict(seed=9335, counts=(40, 23, 9), caps=(5, 6), nms=0.5, vcoco=True),
+    "val_cluttered": dict(seed=9404, counts=(30, 18, 8), caps=(5, 6), nms=0.7, n_gt=6, jitter=25.0, training=False),
+    "train_cluttered": dict(seed=9528, counts=(30, 18, 8), caps=(5, 6), nms=0.7, n_gt=3, jitter=25.0, training=True),
+}
 
 
 def pooled_for(case, n_rows):
@@ -171,6 +214,16 @@ def build_case(name):
                 break
         imgs = _grid_images(shapes, 8, 2, 1 if vcoco else 49, 81 if vcoco else 80, 78000 + 10 * seed)
         c.update(training=True, n_gt=int(rs.randint(1, 6)), rng_seed=4000 + seed, weight_seed=3 + seed % 2)
+    elif name in CLUTTERED:
+        # overlapping detections (see CLUTTERED): what the disjoint grid of synth.make_image never shows the reference
+        spec = CLUTTERED[name]
+        if spec.get("vcoco"):
+            cfg = VCOCO
+        imgs = _cluttered_images(int(alt_seed or spec["seed"]), spec["counts"], cfg["human_idx"])
+        c.update(max_human=spec["caps"][0], max_object=spec["caps"][1], box_nms_thresh=spec["nms"])
+        if "n_gt" in spec:
+            c.update(n_gt=spec["n_gt"], gt_jitter=spec["jitter"], training=spec["training"],
+                     eval_targets=not spec["training"])
     else:
         raise KeyError(name)
     c["cfg"] = cfg
@@ -179,26 +232,33 @@ def build_case(name):
     c["feat3"] = torch.cat([i["feat3"] for i in imgs])
     c["shapes"] = [i["hw"] for i in imgs]
     if c["training"] or c.get("eval_targets"):
-        c["targets"] = [synth.make_targets(d, cfg["human_idx"], c["o2v"], 900 + k, n_gt=c.get("n_gt", 3))
+        c["targets"] = [synth.make_targets(d, cfg["human_idx"], c["o2v"], 900 + k, n_gt=c.get("n_gt", 3),
+                                           jitter=c.get("gt_jitter", 2.0))
                         for k, d in enumerate(c["detections"])]
     return c
 
 
 EVAL_CASES = ["tiny", "ragged3", "skips_eval", "nanbox", "vcoco", "nms", "iter1", "iter0", "full20", "full15x2",
-              "eval_targets", "full20x3", "many8", "many12"]
-TRAIN_CASES = ["train_tiny", "train_skips"]
+              "eval_targets", "full20x3", "many8", "many12", "cluttered_eval", "cluttered_vcoco", "val_cluttered"]
+TRAIN_CASES = ["train_tiny", "train_skips", "train_cluttered"]
 FULL_TRAIN_CASE = "train_full20x4"        # full-size training step: losses / labels / samples + gradient samples
 # every full-width (C = 256, p = 7) training fixture: the uniform BASELINE shape, the V-COCO head, a ragged batch with a skip
 FULL_TRAIN_CASES = [FULL_TRAIN_CASE, "train_vcoco", "train_ragged_full"]
 OUTPUT_ONLY = ["full20", "full15x2", "full20x3", "many8", "many12"] + FULL_TRAIN_CASES   # no bulky intermediates
 GRAD_SAMPLES = 512                        # entries kept per parameter gradient in those fixtures (evenly strided)
+# fixtures with gradient samples from the reference's own autograd: the full-width ones and the cluttered batch at test width
+# (that one keeps its intermediates too, so fewer entries per gradient: the fixture stays under 700 KB)
+GRAD_CASES = FULL_TRAIN_CASES + ["train_cluttered"]
+GRAD_SAMPLES_OF = {"train_cluttered": 128}
+# cases whose fixture drops only the pair features (the one bulky intermediate at ~150 pairs x 2048)
+NO_PAIR_FEATURES = list(CLUTTERED)
 RAISING_CASES = ["skips_raise"]
 ALL_CASES = EVAL_CASES + TRAIN_CASES + FULL_TRAIN_CASES
 
 
-def grad_sample(flat_grad):
-    """The fixed sample of a parameter gradient the full-size fixture stores: GRAD_SAMPLES evenly strided entries of the
-    flattened tensor (all of it when smaller)."""
+def grad_sample(flat_grad, n_samples=GRAD_SAMPLES):
+    """The fixed sample of a parameter gradient a fixture stores: `n_samples` evenly strided entries of the flattened tensor
+    (all of it when smaller).  GRAD_SAMPLES for the full-size fixtures, GRAD_SAMPLES_OF[case] where a case sets its own."""
     n = flat_grad.shape[0]
-    stride = max(1, n // GRAD_SAMPLES)
-    return flat_grad[::stride][:GRAD_SAMPLES]
+    stride = max(1, n // n_samples)
+    return flat_grad[::stride][:n_samples]

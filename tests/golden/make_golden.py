@@ -69,7 +69,9 @@ def run_reference(case):
     hooks = [gh.adjacency.register_forward_hook(lambda m, i, o: cap["adjacency"].append(o.detach().clone())),
              gh.norm_h.register_forward_hook(lambda m, i, o: cap["norm_h"].append(o.detach().clone())),
              gh.norm_o.register_forward_hook(lambda m, i, o: cap["norm_o"].append(o.detach().clone()))]
-    want_grads = case["name"].partition("@")[0] in cases.FULL_TRAIN_CASES    # gradient samples from the reference's own autograd
+    base_name = case["name"].partition("@")[0]
+    want_grads = base_name in cases.GRAD_CASES                 # gradient samples from the reference's own autograd
+    n_samples = cases.GRAD_SAMPLES_OF.get(base_name, cases.GRAD_SAMPLES)
     try:
         with torch.set_grad_enabled(want_grads), StableTies():
             det = head.preprocess(case["detections"], case["targets"], append_gt=case["training"])
@@ -112,12 +114,19 @@ def run_reference(case):
                         out["timg%d.rel" % i] = re[i]; out["timg%d.rel_norm" % i] = rne[i]
                     if want_grads:
                         head.zero_grad()
-                        (out["hoi_loss"] + out["interactiveness_loss"] + out["transH_loss"]).backward()
+                        # one thread for the backward pass: with several, CPU autograd's sums come out in an order that varies
+                        # from run to run (1e-9 of the gradients' scale), and a rerun would not reproduce the file bit for bit
+                        n_threads = torch.get_num_threads()
+                        torch.set_num_threads(1)
+                        try:
+                            (out["hoi_loss"] + out["interactiveness_loss"] + out["transH_loss"]).backward()
+                        finally:
+                            torch.set_num_threads(n_threads)
                         for k, prm in head.named_parameters():
                             if prm.grad is None:
                                 continue
                             g = prm.grad.detach().reshape(-1)
-                            out["grad." + k + ".sample"] = cases.grad_sample(g).clone()
+                            out["grad." + k + ".sample"] = cases.grad_sample(g, n_samples).clone()
                             out["grad." + k + ".absmax"] = g.abs().max()
                             out["grad." + k + ".norm"] = g.double().norm()
     finally:
@@ -143,24 +152,42 @@ def run_reference(case):
     return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in out.items()}
 
 
+def stored(name, flat):
+    """What of the reference's outputs `flat` the fixture of case `name` keeps."""
+    base_name = name.partition("@")[0]
+    if base_name in cases.OUTPUT_ONLY:
+        # output-only fixture: drop the bulky intermediates, keep what pins the result
+        keep = ("logits_p", "logits_s", "n_results", "n_tables")
+        keep += ("hoi_loss", "interactiveness_loss", "transH_loss")
+        flat = {k: v for k, v in flat.items()
+                if k in keep or k.endswith((".ent", ".scores", ".index", ".prediction", ".labels", ".adjacency",
+                                            ".weights", ".pos_scores", ".neg_scores", ".unary_labels"))
+                or k.startswith(("pre", "grad."))}
+    if base_name in cases.NO_PAIR_FEATURES:
+        flat = {k: v for k, v in flat.items() if k != "pair_features"}   # the one bulky intermediate; everything else stays
+    if base_name in cases.GRAD_SAMPLES_OF:
+        # 408 gradients x (sample, absmax, norm) as four arrays instead of 1224 (the archive spends ~300 bytes per member)
+        names = [k[5:-7] for k in flat if k.startswith("grad.") and k.endswith(".sample")]
+        packed = {k: v for k, v in flat.items() if not k.startswith("grad.")}
+        packed["grad.names"] = np.array(names)
+        packed["grad.sizes"] = np.array([flat["grad.%s.sample" % k].size for k in names], np.int64)
+        packed["grad.samples"] = np.concatenate([flat["grad.%s.sample" % k] for k in names])
+        packed["grad.absmax"] = np.array([flat["grad.%s.absmax" % k] for k in names], np.float32)
+        packed["grad.norm"] = np.array([flat["grad.%s.norm" % k] for k in names], np.float64)
+        flat = packed
+    return flat
+
+
 def main(names):
     for name in names:
         case = cases.build_case(name)
-        flat = run_reference(case)
-        if name.partition("@")[0] in cases.OUTPUT_ONLY:
-            # output-only fixture: drop the bulky intermediates, keep what pins the result
-            keep = ("logits_p", "logits_s", "n_results", "n_tables")
-            keep += ("hoi_loss", "interactiveness_loss", "transH_loss")
-            flat = {k: v for k, v in flat.items()
-                    if k in keep or k.endswith((".ent", ".scores", ".index", ".prediction", ".labels", ".adjacency",
-                                                ".weights", ".pos_scores", ".neg_scores", ".unary_labels"))
-                    or k.startswith(("pre", "grad."))}
+        flat = stored(name, run_reference(case))
         path = os.path.join(OUT, name + ".npz")
         np.savez_compressed(path, **flat)
         print("%-12s %4d arrays  %8.1f KB" % (name, len(flat), os.path.getsize(path) / 1024))
 
 
-FACT_CASES = ("tiny", "ragged3", "train_tiny")
+FACT_CASES = ("tiny", "ragged3", "train_tiny") + tuple(cases.CLUTTERED)
 
 
 def record_reference_facts():
@@ -191,11 +218,11 @@ def record_reference_facts():
     facts["cases"] = {}
     for name in FACT_CASES:
         case = cases.build_case(name)
-        live = run_reference(case)
+        live = stored(name, run_reference(case))
         g = helpers.load_golden(name)
         assert sorted(live) == sorted(g), name
         for k in g:
-            assert np.array_equal(live[k], g[k], equal_nan=True), "fixture stale: %s %s" % (name, k)
+            assert np.array_equal(live[k], g[k], equal_nan=g[k].dtype.kind == "f"), "fixture stale: %s %s" % (name, k)
         facts["cases"][name] = dict(inputs_sha256=helpers.content_digest(case), fixture_sha256=helpers.content_digest(g))
     case = cases.build_case("skips_raise")
     try:

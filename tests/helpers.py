@@ -64,6 +64,23 @@ def golden_tables(g):
     return out
 
 
+def without_gradients(g):
+    """A fixture's forward outputs (the gradient samples of cases.GRAD_CASES have a test of their own:
+    test_oracle_golden.py::test_oracle_full_size_training_step_matches_reference_autograd)."""
+    return {k: v for k, v in g.items() if not k.startswith("grad.")}
+
+
+def golden_gradients(g):
+    """{parameter name: (sample, absmax, norm)} of a fixture with gradient samples from the reference's autograd: one array per
+    figure and parameter (the full-width fixtures), or the four packed arrays of the cases in cases.GRAD_SAMPLES_OF."""
+    if "grad.names" in g:
+        ends = np.cumsum(g["grad.sizes"])
+        return {str(k): (g["grad.samples"][e - n:e], float(g["grad.absmax"][i]), float(g["grad.norm"][i]))
+                for i, (k, n, e) in enumerate(zip(g["grad.names"], g["grad.sizes"], ends))}
+    names = [k[5:-7] for k in g if k.startswith("grad.") and k.endswith(".sample")]
+    return {k: (g["grad.%s.sample" % k], float(g["grad.%s.absmax" % k]), float(g["grad.%s.norm" % k])) for k in names}
+
+
 def run_oracle(case, tables=None, row_loop=False):
     """Oracle forward for a tests/cases.py case.  tables=None -> drawn from the torch CPU RNG under the case's seed
     (the reference's own behaviour)."""

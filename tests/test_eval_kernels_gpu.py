@@ -57,7 +57,7 @@ from oracle import skg_oracle as O
 from skghoi_amd import _capi
 from skghoi_amd.engine import _CHUNK_DTYPE, ParamWatch, _stream
 from kernel_test_helpers import E_ALIGN, E_ARG, ISENT, SENT, _bar, _dev, _meta_dev, _out, _take, _twice
-from test_random_parity_gpu import _cluttered
+from cases import cluttered_detections as _cluttered
 
 pytestmark = pytest.mark.gpu
 

@@ -8,22 +8,11 @@ import torch
 import cases
 import gpu_run
 import helpers
+from cases import cluttered_detections as _cluttered
 from oracle import skg_oracle as O
 from skghoi_amd import synth
 
 pytestmark = pytest.mark.gpu
-
-
-def _cluttered(rs, n, human_idx, n_cls):
-    """Boxes in clusters (heavy overlap inside a cluster), few classes, quantised scores (many ties)."""
-    k = max(1, n // 4)
-    centres = rs.uniform(50, 700, (k, 2)); sizes = rs.uniform(30, 300, (k, 2))
-    c = rs.randint(0, k, n)
-    xy = centres[c] + rs.normal(0, 12, (n, 2)); wh = np.abs(sizes[c] + rs.normal(0, 15, (n, 2))) + 1
-    boxes = np.concatenate([xy - wh / 2, xy + wh / 2], 1).astype(np.float32)
-    labels = rs.choice([human_idx, human_idx, 3, 7, 11][:n_cls], n).astype(np.int64)
-    scores = (rs.randint(1, 20, n) / 20.0).astype(np.float32)
-    return dict(boxes=torch.from_numpy(boxes), labels=torch.from_numpy(labels), scores=torch.from_numpy(scores))
 
 
 @pytest.mark.parametrize("seed", range(4))

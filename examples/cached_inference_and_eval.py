@@ -4,9 +4,11 @@
   FPN-like feature maps + detections -> producer (device NMS/top-k, MultiScaleRoIAlign, global pool) -> feature shard
   + per-image detection JSON on disk -> batched inference from the cache -> 600-way HOI scores -> 11-point mAP
   against synthetic ground truth, in HICO-DET's Default and Known Object settings (full / rare / non-rare)
-  -> HICO-DET .mat cells / V-COCO-style pickle.
+  -> the producer's kept detections judged against the same ground truth (object-detection mAP, maximum recall, pair
+  coverage) -> HICO-DET .mat cells / V-COCO-style pickle.
 
-Mirrors what a user of the reference does with hicodet/detections/adamixer_preprocessing.py, utils.test and cache.py.
+Mirrors what a user of the reference does with hicodet/detections/adamixer_preprocessing.py, utils.test,
+hicodet/detections/eval_detections.py and cache.py.
 """
 import argparse
 import os
@@ -41,7 +43,7 @@ def main(n_images=16, batch=8, out_dir=None, seed=0):
     dets = [dict(boxes=i["boxes"].to(dev), labels=i["labels"].to(dev), scores=i["scores"].to(dev)) for i in imgs]
     shapes = [(H, W)] * n_images
     # ---- producer: one shard per batch + the reference's per-image detection JSON
-    shards = []
+    shards, kept_all = [], []
     for lo in range(0, n_images, batch):
         hi = min(n_images, lo + batch)
         feats = OrderedDict((str(l), torch.randn(hi - lo, 256, H // s, W // s, generator=g).to(dev))
@@ -51,7 +53,7 @@ def main(n_images=16, batch=8, out_dir=None, seed=0):
         for k, d in enumerate(kept):
             cache.write_detections_json(os.path.join(out_dir, "img_%06d.json" % (lo + k)), d["boxes"].cpu(),
                                         d["scores"].cpu(), d["labels"].cpu())
-        shards.append((lo, hi, path))
+        shards.append((lo, hi, path)); kept_all += kept
     # ---- inference from the cache
     pool = cache.CachedPool()
     head.box_roi_pool = pool
@@ -73,7 +75,7 @@ def main(n_images=16, batch=8, out_dir=None, seed=0):
         hoi = int(lut[int(out["object"][p]), int(out["prediction"][j])])
         num_gt[hoi] += 1
         targets.append(dict(boxes_h=out["boxes_h"][p:p + 1].cpu(), boxes_o=out["boxes_o"][p:p + 1].cpu(),
-                            hoi=torch.tensor([hoi])))
+                            object=out["object"][p:p + 1].cpu(), hoi=torch.tensor([hoi])))
     num_anno_train = [5 if h % 4 == 0 else 50 for h in range(600)]      # synthetic training counts: every fourth class is rare
     ev = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True)
     for out, t in zip(outputs, targets):
@@ -81,6 +83,12 @@ def main(n_images=16, batch=8, out_dir=None, seed=0):
     summ = ev.summary()
     for name, s in (("Default", summ), ("Known Object", summ["known_object"])):
         print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
+    # ---- the boxes behind those numbers: what the producer kept, judged against the same ground truth
+    det_ev = evaluate.DeviceDetectionEvaluator(num_classes=80, human_idx=49, num_hoi=600, device=dev)
+    det_ev.add(kept_all, targets)
+    ds = det_ev.summary()
+    print("kept detections: mAP over classes with GT %.4f  mean max recall %.4f  pair recall %.4f" % (
+        ds["map_present"], ds["mean_max_rec_present"], ds["pair_recall"]))
     cells = evaluate.hicodet_mat_cells(outputs, list(range(n_images)), n_images, lut)
     actions = ["verb%d obj" % v for v in range(117)]
     evaluate.save_vcoco_pickle(evaluate.vcoco_results(outputs[:2], [1, 2], actions), out_dir)

@@ -773,6 +773,51 @@ int skg_eval_vcoco_match_f32(const float* boxes_h, const float* boxes_o, const i
 int skg_eval_ap_voc_f64(const float* labels_sorted, const int64_t* class_off, const int64_t* num_gt, int n_classes,
                         double* ap, void* stream);
 
+/* Object-detection quality of the boxes that go into the cache (hicodet/detections/eval_detections.py:91-127: class-wise
+ * NMS of the ground-truth boxes, pocket BoxAssociation per object class), for a batch of images: detections det_boxes
+ * [L, 4], det_scores / det_labels [L], det_off [n_images + 1], taken as they are (score filter, NMS and top-k are the
+ * caller's: pass what the head's preprocess kept, or raw detections); the head's targets gt_h / gt_o [Ng, 4], gt_object
+ * [Ng], gt_off [n_images + 1] (pairs), boxes in the frame the head sees them.  torchvision (tie order of equal scores) and
+ * pocket (BoxAssociation) are outside the reference tree: restated, parity unpinned at those boundaries.
+ *
+ * Ground-truth box set of an image with G pairs: the 2G boxes cat(gt_h, gt_o) with classes cat(human_idx x G, gt_object),
+ * class-wise greedy NMS at nms_thresh with all scores equal -- torchvision batched_nms's arithmetic in fp32: boxes shifted by
+ * (float)class * (max_coord + 1), candidates in ascending index order (the project's rule for ties), box j suppressed by an
+ * earlier kept box i iff IoU(i, j) > nms_thresh; a NaN coordinate in any of the 2G boxes makes every offset NaN and nothing
+ * is suppressed.  gt_keep [2 * Ng]: entry 2 * gt_off[a] + j is 1 iff box j of image a (0 <= j < 2G, humans first) survives.
+ * num_gt [num_classes] int64 is ADDED to (integer atomics; zero it before the first call): one per kept box of a class in
+ * [0, num_classes); kept boxes of a class outside are counted in status[1] instead.
+ * Association: a detection with a NaN score is dropped (labels -1, matched_gt -1; it never bids).  Every other detection of
+ * class c in [0, num_classes) looks for the kept box of class c with the largest plain (unshifted) IoU(box, detection),
+ * first maximum, NaN never wins; it is matched iff that IoU >= min_iou.  Of the detections matched to one box the highest
+ * score is the true positive (labels 1; equal scores, -0 like +0: the lower detection index), every other detection is 0.
+ * matched_gt [L] int32: the image-local index j of the matched box, -1 for none (also for a class outside the range).
+ * An image with 2G > SKG_EVAL_DET_MAX_GT (the boxes sit in LDS) is refused: its labels are 0, its matched_gt -1, its gt_keep
+ * 0, num_gt is not touched, and status[0] receives the largest such 2G (atomicMax).  status: two device int32, zero them
+ * before the first call.  Every element of labels, matched_gt and gt_keep is written exactly once; any number of detections
+ * per image.
+ * Errors, before any device call: SKG_E_ARG for n_images < 0, num_classes <= 0, human_idx outside [0, num_classes) or a null
+ * pointer; SKG_E_ALIGN for det_boxes / gt_h / gt_o not 16-byte aligned.  n_images == 0 returns 0 and launches nothing.  */
+#define SKG_EVAL_DET_MAX_GT 1024
+int skg_eval_det_match_f32(const float* det_boxes, const float* det_scores, const int64_t* det_labels, const int32_t* det_off,
+                           int n_images, const float* gt_h, const float* gt_o, const int64_t* gt_object,
+                           const int32_t* gt_off, int human_idx, int num_classes, float min_iou, float nms_thresh,
+                           int8_t* labels, int32_t* matched_gt, uint8_t* gt_keep, int64_t* num_gt, int32_t* status,
+                           void* stream);
+/* Pair coverage (not in the reference): the share of the ground-truth interactions the head can still find at all, the
+ * ceiling of every HOI recall.  Ground-truth pair g is COVERED iff there are two DIFFERENT detections d1 != d2 of its image,
+ * neither dropped, with det_labels[d1] == human_idx and IoU(gt_h[g], det_boxes[d1]) >= min_iou, and det_labels[d2] ==
+ * gt_object[g] and IoU(gt_o[g], det_boxes[d2]) >= min_iou -- both candidate sets non-empty and not the same single
+ * detection: the head never pairs a box with itself.  All ground-truth boxes count, the suppressed duplicates too.
+ * labels_in [L]: the labels of skg_eval_det_match_f32 over the same detections; a detection with labels_in < 0 is dropped
+ * (the kernel does not test the scores again).  covered [Ng] uint8, every element written once.  Any number of detections
+ * and pairs per image (the detections pass through LDS in chunks).
+ * Errors, before any device call: SKG_E_ARG for n_images < 0 or a null pointer; SKG_E_ALIGN for det_boxes / gt_h / gt_o not
+ * 16-byte aligned.  n_images == 0 returns 0 and launches nothing.                                                       */
+int skg_eval_pair_cover_u8(const float* det_boxes, const int64_t* det_labels, const int8_t* labels_in, const int32_t* det_off,
+                           int n_images, const float* gt_h, const float* gt_o, const int64_t* gt_object,
+                           const int32_t* gt_off, int human_idx, float min_iou, uint8_t* covered, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Order-independent 64-bit checksum of the live parameters (bit patterns weighted by position) over a table of
  * chunks: chunk c covers `count` fp32 words at `ptr` (16-byte aligned) whose first word has global index `first`.

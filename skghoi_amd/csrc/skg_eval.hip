@@ -27,6 +27,16 @@
 //   skg_eval_ap_voc_f64      : one workgroup per class over the same sorted labels: the class's true-positive total by a
 //                              block reduction, then one backward pass of reversed block scans carrying the suffix
 //                              true-positive count and the suffix maximum of the precision; float64.
+//
+// Object detections (the boxes that go into the cache; hicodet/detections/eval_detections.py:91-127, restated in
+// include/skghoi.h -- torchvision's tie order, pocket's BoxAssociation and 'INT' are outside the image, parity unpinned there):
+//
+//   skg_eval_det_match_f32   : one workgroup per image.  The image's 2G ground-truth boxes sit in LDS; class-wise greedy NMS
+//                              over them in index order (the preprocess kernel's coordinate trick and barrier order), then
+//                              every lane takes detections, finds the kept box of its class of largest IoU and bids for it
+//                              with the same 64-bit key.
+//   skg_eval_pair_cover_u8   : one workgroup per image, one lane per ground-truth pair, the detections through LDS in chunks:
+//                              is the human box and the object box of the pair covered by two different detections.
 #include "skg_common.h"
 
 #define EV_MAX_GT 2048            // ground-truth pairs per image the association keeps in LDS
@@ -403,5 +413,208 @@ extern "C" int skg_eval_ap_voc_f64(const float* labels_sorted, const int64_t* cl
     if (!class_off || !num_gt || !ap) return SKG_E_ARG;
     hipLaunchKernelGGL(skg_eval_ap_voc_kernel, dim3(n_classes), dim3(256), 0, (hipStream_t)stream, labels_sorted, class_off,
                        num_gt, ap);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ object detections
+// The rule is stated in include/skghoi.h (skg_eval_det_match_f32).  LDS of the match kernel: 1024 boxes (16 KB), their classes
+// as int64 (8 KB), the bid keys (8 KB), the suppression bytes (1 KB): 33 KB static, under the 64 KB a workgroup may declare.
+#define EVD_CHUNK 256             // detections per LDS chunk of the pair-coverage kernel
+
+// one ground-truth box on the coordinate trick's offset: batched_nms's `boxes + (idxs.to(boxes) * (max_coord + 1))[:, None]`
+__device__ __forceinline__ float4 evd_shifted(const float4 b, int64_t cls, float unit) {
+    const float off = (float)cls * unit;
+    return make_float4(b.x + off, b.y + off, b.z + off, b.w + off);
+}
+
+__global__ __launch_bounds__(256) void skg_eval_det_match_kernel(
+    const float* __restrict__ det_boxes, const float* __restrict__ det_scores, const int64_t* __restrict__ det_labels,
+    const int32_t* __restrict__ det_off, const float* __restrict__ gt_h, const float* __restrict__ gt_o,
+    const int64_t* __restrict__ gt_object, const int32_t* __restrict__ gt_off, int human_idx, int num_classes, float min_iou,
+    float nms_thresh, int8_t* __restrict__ labels, int32_t* __restrict__ matched_gt, uint8_t* __restrict__ gt_keep,
+    unsigned long long* __restrict__ num_gt, int32_t* __restrict__ status) {
+    __shared__ float4 sbox[SKG_EVAL_DET_MAX_GT];             // cat(boxes_h, boxes_o) of the image, unshifted
+    __shared__ int64_t scls[SKG_EVAL_DET_MAX_GT];
+    __shared__ unsigned long long skey[SKG_EVAL_DET_MAX_GT];
+    __shared__ unsigned char ssup[SKG_EVAL_DET_MAX_GT];
+    __shared__ float sred[4];
+    __shared__ int snan;
+    const int a = blockIdx.x, tid = threadIdx.x;
+    const int d0 = det_off[a], d1 = det_off[a + 1];
+    const int g0 = gt_off[a];
+    const int G = max(gt_off[a + 1] - g0, 0);
+    if (G > SKG_EVAL_DET_MAX_GT / 2) {                       // uniform, ahead of every barrier: reported, nothing staged
+        if (tid == 0) atomicMax(status, G > 0x3fffffff ? 0x7fffffff : 2 * G);
+        for (int d = d0 + tid; d < d1; d += 256) { labels[d] = 0; matched_gt[d] = -1; }
+        for (int64_t j = tid; j < 2 * (int64_t)G; j += 256) gt_keep[2 * (int64_t)g0 + j] = 0;
+        return;
+    }
+    const int nb = 2 * G;
+
+    // ---- phase 1: the ground-truth box set.  Staging, max_coord (NaN propagates like Tensor.max()), greedy NMS in index order
+    if (tid == 0) snan = 0;
+    float lmax = -INFINITY;
+    bool lnan = false;
+    for (int j = tid; j < nb; j += 256) {
+        const bool hum = j < G;
+        const int64_t g = (int64_t)g0 + (hum ? j : j - G);
+        const float4 b = *reinterpret_cast<const float4*>((hum ? gt_h : gt_o) + 4 * g);
+        sbox[j] = b; scls[j] = hum ? (int64_t)human_idx : gt_object[g]; skey[j] = 0ull; ssup[j] = 0;
+        lmax = fmaxf(lmax, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
+        lnan |= (b.x != b.x) | (b.y != b.y) | (b.z != b.z) | (b.w != b.w);
+    }
+    lmax = skg_wave_max(lmax);
+    if ((tid & 63) == 0) sred[tid >> 6] = lmax;
+    __syncthreads();
+    if (lnan) snan = 1;                                      // (every writer stores the same value)
+    __syncthreads();
+    float max_coord = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
+    // one NaN coordinate makes every offset, shifted box, area and IoU NaN: `IoU > thr` never holds, nothing is suppressed
+    if (snan) max_coord = __uint_as_float(0x7fc00000u);
+    const float unit = max_coord + 1.0f;
+    for (int i = 0; i < nb; ++i) {                           // sequential over the candidates, the lanes suppress in parallel
+        if (!ssup[i]) {                                      // uniform (LDS broadcast; final since the previous barrier)
+            const float4 bi = evd_shifted(sbox[i], scls[i], unit);
+            const float ai = (bi.z - bi.x) * (bi.w - bi.y);
+            for (int j = i + 1 + tid; j < nb; j += 256) {
+                if (ssup[j]) continue;
+                const float4 bj = evd_shifted(sbox[j], scls[j], unit);
+                const float aj = (bj.z - bj.x) * (bj.w - bj.y);
+                const float xx1 = fmaxf(bi.x, bj.x), yy1 = fmaxf(bi.y, bj.y);
+                const float xx2 = fminf(bi.z, bj.z), yy2 = fminf(bi.w, bj.w);
+                const float w = fmaxf(xx2 - xx1, 0.f), h = fmaxf(yy2 - yy1, 0.f);
+                const float inter = w * h;
+                const float ovr = inter / (ai + aj - inter);
+                if (ovr > nms_thresh) ssup[j] = 1;
+            }
+        }
+        __syncthreads();
+    }
+    int bad = 0;
+    for (int j = tid; j < nb; j += 256) {
+        const bool kept = ssup[j] == 0;
+        gt_keep[2 * (int64_t)g0 + j] = kept ? 1 : 0;
+        if (kept) {
+            const int64_t c = scls[j];
+            if (c >= 0 && c < num_classes) atomicAdd(&num_gt[c], 1ull);      // integer: order-independent
+            else ++bad;
+        }
+    }
+    if (bad) atomicAdd(status + 1, bad);
+
+    // ---- phase 2: every detection finds the kept box of its class of largest plain IoU and bids for it
+    for (int d = d0 + tid; d < d1; d += 256) {
+        const float s = det_scores[d];
+        const int64_t c = det_labels[d];
+        int match = -1;
+        if (s == s && c >= 0 && c < num_classes) {           // a NaN score never bids
+            const float4 db = *reinterpret_cast<const float4*>(det_boxes + 4 * (int64_t)d);
+            float best = -1.f;
+            for (int j = 0; j < nb; ++j) {
+                if (ssup[j] || scls[j] != c) continue;
+                const float v = ev_iou(sbox[j], db);
+                if (v > best) { best = v; match = j; }       // first maximum, NaN never wins
+            }
+            if (!(best >= min_iou)) match = -1;
+            // (score, lower index wins ties) as one ordered 64-bit key; 0 = no bid.  s + 0: -0 bids like +0
+            if (match >= 0)
+                atomicMax(&skey[match], ((unsigned long long)ev_orderable(s + 0.f) << 32) |
+                                            (unsigned)(0xffffffffu - (unsigned)(d - d0)));
+        }
+        matched_gt[d] = match;                               // final; the same lane reads it back behind the barrier
+    }
+    __syncthreads();
+    for (int d = d0 + tid; d < d1; d += 256) {
+        const float s = det_scores[d];
+        int8_t lab = 0;
+        if (s != s) lab = -1;                                // dropped
+        else {
+            const int m = matched_gt[d];
+            if (m >= 0) {
+                const unsigned long long key =
+                    ((unsigned long long)ev_orderable(s + 0.f) << 32) | (unsigned)(0xffffffffu - (unsigned)(d - d0));
+                lab = skey[m] == key ? 1 : 0;
+            }
+        }
+        labels[d] = lab;
+    }
+}
+
+extern "C" int skg_eval_det_match_f32(const float* det_boxes, const float* det_scores, const int64_t* det_labels,
+                                      const int32_t* det_off, int n_images, const float* gt_h, const float* gt_o,
+                                      const int64_t* gt_object, const int32_t* gt_off, int human_idx, int num_classes,
+                                      float min_iou, float nms_thresh, int8_t* labels, int32_t* matched_gt, uint8_t* gt_keep,
+                                      int64_t* num_gt, int32_t* status, void* stream) {
+    if (n_images < 0 || num_classes <= 0 || human_idx < 0 || human_idx >= num_classes) return SKG_E_ARG;
+    if (!det_boxes || !det_scores || !det_labels || !det_off || !gt_h || !gt_o || !gt_object || !gt_off || !labels ||
+        !matched_gt || !gt_keep || !num_gt || !status)
+        return SKG_E_ARG;
+    if (!skg_aligned16(det_boxes) || !skg_aligned16(gt_h) || !skg_aligned16(gt_o)) return SKG_E_ALIGN;
+    if (n_images == 0) return 0;
+    hipLaunchKernelGGL(skg_eval_det_match_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, det_boxes, det_scores,
+                       det_labels, det_off, gt_h, gt_o, gt_object, gt_off, human_idx, num_classes, min_iou, nms_thresh, labels,
+                       matched_gt, gt_keep, reinterpret_cast<unsigned long long*>(num_gt), status);
+    return skg_launch_status();
+}
+
+// Pair coverage.  One lane per ground-truth pair (tiles of 256 pairs), the image's detections through LDS in chunks of
+// EVD_CHUNK: every loop bound is uniform over the workgroup, so that all 256 lanes reach every barrier.  Dropped detections
+// (labels_in < 0: the match kernel's NaN scores) are staged with a flag and skipped.
+__global__ __launch_bounds__(256) void skg_eval_pair_cover_kernel(
+    const float* __restrict__ det_boxes, const int64_t* __restrict__ det_labels, const int8_t* __restrict__ labels_in,
+    const int32_t* __restrict__ det_off, const float* __restrict__ gt_h, const float* __restrict__ gt_o,
+    const int64_t* __restrict__ gt_object, const int32_t* __restrict__ gt_off, int human_idx, float min_iou,
+    uint8_t* __restrict__ covered) {
+    __shared__ float4 sdb[EVD_CHUNK];
+    __shared__ int64_t sdc[EVD_CHUNK];
+    __shared__ unsigned char sdrop[EVD_CHUNK];
+    const int a = blockIdx.x, tid = threadIdx.x;
+    const int d0 = det_off[a], nd = max(det_off[a + 1] - d0, 0);
+    const int g0 = gt_off[a], G = max(gt_off[a + 1] - g0, 0);
+    for (int gb = 0; gb < G; gb += 256) {                    // uniform
+        const bool valid = gb + tid < G;
+        const int64_t g = (int64_t)g0 + gb + tid;
+        float4 bh = make_float4(0.f, 0.f, 0.f, 0.f), bo = bh;
+        int64_t ob = 0;
+        if (valid) {
+            bh = *reinterpret_cast<const float4*>(gt_h + 4 * g);
+            bo = *reinterpret_cast<const float4*>(gt_o + 4 * g);
+            ob = gt_object[g];
+        }
+        int nh = 0, no = 0, fh = -1, fo = -1;                // qualifying detections per side and the first index of each
+        for (int k0 = 0; k0 < nd; k0 += EVD_CHUNK) {         // uniform
+            const int nk = min(EVD_CHUNK, nd - k0);
+            __syncthreads();                                 // the previous chunk is read
+            for (int k = tid; k < nk; k += 256) {
+                const int64_t d = (int64_t)d0 + k0 + k;
+                sdb[k] = *reinterpret_cast<const float4*>(det_boxes + 4 * d);
+                sdc[k] = det_labels[d];
+                sdrop[k] = labels_in[d] < 0 ? 1 : 0;
+            }
+            __syncthreads();
+            if (valid) {
+                for (int k = 0; k < nk; ++k) {
+                    if (sdrop[k]) continue;
+                    const int64_t c = sdc[k];
+                    if (c == (int64_t)human_idx && ev_iou(bh, sdb[k]) >= min_iou) { if (nh++ == 0) fh = k0 + k; }
+                    if (c == ob && ev_iou(bo, sdb[k]) >= min_iou) { if (no++ == 0) fo = k0 + k; }
+                }
+            }
+        }
+        if (valid) covered[g] = (nh >= 1 && no >= 1 && !(nh == 1 && no == 1 && fh == fo)) ? 1 : 0;
+    }
+}
+
+extern "C" int skg_eval_pair_cover_u8(const float* det_boxes, const int64_t* det_labels, const int8_t* labels_in,
+                                      const int32_t* det_off, int n_images, const float* gt_h, const float* gt_o,
+                                      const int64_t* gt_object, const int32_t* gt_off, int human_idx, float min_iou,
+                                      uint8_t* covered, void* stream) {
+    if (n_images < 0) return SKG_E_ARG;
+    if (!det_boxes || !det_labels || !labels_in || !det_off || !gt_h || !gt_o || !gt_object || !gt_off || !covered)
+        return SKG_E_ARG;
+    if (!skg_aligned16(det_boxes) || !skg_aligned16(gt_h) || !skg_aligned16(gt_o)) return SKG_E_ALIGN;
+    if (n_images == 0) return 0;
+    hipLaunchKernelGGL(skg_eval_pair_cover_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, det_boxes, det_labels,
+                       labels_in, det_off, gt_h, gt_o, gt_object, gt_off, human_idx, min_iou, covered);
     return skg_launch_status();
 }

@@ -11,6 +11,8 @@ HICO-DET's Known Object setting (the second half of the published table; Chao et
 the same two evaluators (`known_object=True`), the rule of the official evaluation restated under the same terms.
 V-COCO's AP_role (scenario 1 and 2) is computed in-process by VCOCOEvaluator / DeviceVCOCOEvaluator, the rule of the
 external toolkit restated under the same terms.
+The detections behind the head (hicodet/detections/eval_detections.py: object-detection mAP and mean maximum recall over the
+kept boxes, generate_gt_detections.py) are judged by DetectionEvaluator / DeviceDetectionEvaluator, which add pair coverage.
 
 Everything works on whatever device the result tensors live on (the association is a handful of small IoU matrices);
 nothing here is on the timed hot path.
@@ -710,6 +712,290 @@ class DeviceVCOCOEvaluator:
             ap[npos[aid] == 0] = float("nan")
             aps.append(ap)
         return _vcoco_summary(self.table, aps[0], aps[1], npos)
+
+
+# ----------------------------------------------------------------------------------------------- object detections
+# The quality of the boxes that go into the cache (hicodet/detections/eval_detections.py: 80-class detection mAP and mean
+# maximum recall, the two numbers of hicodet/detections/README.md), plus pair coverage.  The rule, per image, given the
+# detections to be judged {boxes [N, 4], scores [N], labels [N]} -- taken as they are: what head.preprocess / produce_shard
+# kept, or raw detections; the script's own score filter / NMS / top-k is the caller's -- and the head's target {boxes_h,
+# boxes_o [G, 4], object [G]} (optionally hoi [G]), boxes in the frame the head sees them: the reference's
+# `gt_boxes[:, :2] -= 1` (eval_detections.py:102) belongs to whoever builds the targets.
+#   a. ground-truth box set (eval_detections.py:91-113): cat(boxes_h, boxes_o) with classes cat(human_idx x G, object), class-wise
+#      NMS at nms_thresh with all scores equal, torchvision batched_nms's arithmetic (boxes shifted by class * (max_coord + 1),
+#      fp32, suppress at IoU > thr), candidates in ascending index order; num_gt[c] grows by the kept boxes of class c.
+#   b. association (eval_detections.py:115-127, pocket BoxAssociation): a detection is matched to the kept box of its class of
+#      largest plain IoU (first maximum, NaN never wins) if that reaches min_iou; of the detections matched to one box the
+#      highest score is the true positive, equal scores: the lower index; a NaN score drops the detection (label -1).
+#   c. pair coverage (not in the reference): pair g is covered iff two DIFFERENT non-dropped detections d1 != d2 have
+#      labels[d1] == human_idx, IoU(boxes_h[g], box[d1]) >= min_iou, labels[d2] == object[g], IoU(boxes_o[g], box[d2]) >= min_iou.
+# Unpinned boundaries: torchvision's order of equal scores (here: ascending index), pocket's BoxAssociation and pocket's 'INT'
+# (here "AUC", the VOC all-point area) are outside the reference tree; their published semantics are restated.
+def _equal_score_nms_keep(boxes, classes, thresh):
+    """Class-wise greedy NMS with all scores equal -> bool keep [n]: boxes shifted by class * (max_coord + 1), fp32, box j
+    suppressed by an earlier kept box i iff IoU(i, j) > thresh; a NaN coordinate makes every offset NaN: nothing suppressed."""
+    n = boxes.shape[0]
+    keep = torch.ones(n, dtype=torch.bool)
+    if n == 0:
+        return keep
+    b = boxes.float()
+    b = b + (classes.to(b) * (b.max() + torch.tensor(1).to(b)))[:, None]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    thr = torch.tensor(thresh, dtype=torch.float32)
+    for i in range(n - 1):
+        if not keep[i]:
+            continue
+        r = torch.nonzero(keep[i + 1:]).squeeze(1) + i + 1
+        wh = (torch.min(b[i, 2:], b[r, 2:]) - torch.max(b[i, :2], b[r, :2])).clamp(min=0)
+        inter = wh[:, 0] * wh[:, 1]
+        keep[r[inter / (area[i] + area[r] - inter) > thr]] = False
+    return keep
+
+
+def gt_detections(target, human_idx=49):
+    """The "ground-truth detections" of hicodet/detections/generate_gt_detections.py:32-39: {boxes = cat(boxes_h, boxes_o),
+    labels = cat(human_idx x G, object), scores = 1}.  No deduplication: a person of several pairs appears several times,
+    which the head's NMS removes."""
+    bh = torch.as_tensor(target["boxes_h"]).reshape(-1, 4); bo = torch.as_tensor(target["boxes_o"]).reshape(-1, 4).to(bh)
+    ob = torch.as_tensor(target["object"]).reshape(-1).to(bh.device).long()
+    return dict(boxes=torch.cat([bh, bo]), labels=torch.cat([torch.full_like(ob, human_idx), ob]),
+                scores=torch.ones(2 * bh.shape[0], dtype=torch.float32, device=bh.device))
+
+
+def _det_summary(ap, num_gt, tp, pairs, covered, hoi_pairs, hoi_covered):
+    """The summary both detection evaluators return (host tensors): ap / max_rec float64 [num_classes], num_gt int64."""
+    has = num_gt > 0
+    max_rec = torch.where(has, tp.double() / num_gt.clamp(min=1).double(), torch.zeros_like(ap))
+    nan = float("nan")
+    out = dict(ap=ap, num_gt=num_gt, max_rec=max_rec, map=float(ap.mean()), mean_max_rec=float(max_rec.mean()),
+               map_present=float(ap[has].mean()) if bool(has.any()) else nan,
+               mean_max_rec_present=float(max_rec[has].mean()) if bool(has.any()) else nan,
+               pair_recall=covered / pairs if pairs else nan)
+    if hoi_pairs is not None:
+        out["pair_recall_hoi"] = torch.where(hoi_pairs > 0, hoi_covered.double() / hoi_pairs.clamp(min=1).double(),
+                                             torch.full(hoi_pairs.shape, nan, dtype=torch.float64))
+    return out
+
+
+def _det_target(target, device):
+    bh = torch.as_tensor(target["boxes_h"]).to(device).float().reshape(-1, 4)
+    bo = torch.as_tensor(target["boxes_o"]).to(device).float().reshape(-1, 4)
+    ob = torch.as_tensor(target["object"]).to(device).long().reshape(-1)
+    if not bh.shape[0] == bo.shape[0] == ob.shape[0]:
+        raise ValueError("boxes_h, boxes_o and object of a target disagree on the number of pairs")
+    hoi = None
+    if "hoi" in target:
+        hoi = torch.as_tensor(target["hoi"]).to(device).long().reshape(-1)
+        if hoi.shape[0] != ob.shape[0]:
+            raise ValueError("hoi and object of a target disagree on the number of pairs")
+    return bh, bo, ob, hoi
+
+
+class DetectionEvaluator:
+    """Object-detection AP, maximum recall and pair coverage of the detections behind the head (the rule above), on the host
+    in plain torch and loops -- the restatement DeviceDetectionEvaluator is checked against.
+
+    add(detections, targets): lists, one {boxes, scores, labels} and one {boxes_h, boxes_o, object[, hoi]} per image (every
+    test image, also those without detections: their ground truth counts); returns per image the int8 labels (1 true positive,
+    0 false positive, -1 dropped).  `last_gt_keep` (bool [2G]), `last_matched` (int32 [N]: index into cat(boxes_h, boxes_o),
+    -1 none) and `last_covered` (uint8 [G]) hold the most recent call's per-image results.  A detection or ground-truth class
+    outside [0, num_classes) is an IndexError.
+
+    summary(): ap [num_classes] float64 (`algorithm`: "AUC" = VOC all-point, pocket's 'INT'; or "11P"), num_gt, max_rec
+    (true positives / num_gt, 0 without ground truth), map / mean_max_rec over all classes like the reference's .mean(),
+    map_present / mean_max_rec_present over the classes with ground truth, pair_recall = covered pairs / pairs, and, with
+    num_hoi, pair_recall_hoi [num_hoi] over the targets that carry `hoi` (NaN for a class without pairs; ids outside
+    [0, num_hoi) are ignored)."""
+    batched = True                                               # trainer.test-style loops feed lists
+
+    def __init__(self, num_classes=80, human_idx=49, min_iou=0.5, nms_thresh=0.5, algorithm="AUC", num_hoi=None):
+        if algorithm not in ("11P", "AUC"):
+            raise ValueError("unknown algorithm %s" % algorithm)
+        if not 0 <= int(human_idx) < int(num_classes):
+            raise ValueError("human_idx %d is outside the %d classes" % (human_idx, num_classes))
+        self.num_classes, self.human_idx = int(num_classes), int(human_idx)
+        self.min_iou, self.nms_thresh, self.algorithm = float(min_iou), float(nms_thresh), algorithm
+        self.num_hoi = None if num_hoi is None else int(num_hoi)
+        self.num_gt = torch.zeros(self.num_classes, dtype=torch.int64)
+        self._scores, self._cls, self._labels = [], [], []
+        self._pairs = self._covered = 0
+        self._hoi_pairs = None if num_hoi is None else torch.zeros(self.num_hoi, dtype=torch.int64)
+        self._hoi_covered = None if num_hoi is None else torch.zeros(self.num_hoi, dtype=torch.int64)
+        self.last_gt_keep, self.last_matched, self.last_covered = [], [], []
+
+    def _one(self, det, target):
+        C = self.num_classes
+        boxes = torch.as_tensor(det["boxes"]).cpu().float().reshape(-1, 4)
+        sc = torch.as_tensor(det["scores"]).cpu().float().reshape(-1); cls = torch.as_tensor(det["labels"]).cpu().long().reshape(-1)
+        bh, bo, ob, hoi = _det_target(target, "cpu")
+        if ((cls < 0) | (cls >= C)).any() or ((ob < 0) | (ob >= C)).any():
+            raise IndexError("a detection or ground-truth class is outside [0, %d)" % C)
+        n, G = sc.shape[0], ob.shape[0]
+        gt_boxes = torch.cat([bh, bo]); gt_cls = torch.cat([torch.full_like(ob, self.human_idx), ob])
+        keep = _equal_score_nms_keep(gt_boxes, gt_cls, self.nms_thresh)
+        self.num_gt += torch.bincount(gt_cls[keep], minlength=C)
+        dropped = torch.isnan(sc)
+        labels = torch.zeros(n, dtype=torch.int8); labels[dropped] = -1
+        matched = torch.full((n,), -1, dtype=torch.int32)
+        covered = torch.zeros(G, dtype=torch.uint8)
+        thr = torch.tensor(self.min_iou, dtype=torch.float32)
+        if n and G:
+            iou = box_iou(gt_boxes, boxes)                                            # [2G, n]
+            ok = keep[:, None] & (gt_cls[:, None] == cls[None]) & ~torch.isnan(iou)
+            iou = torch.where(ok, iou, torch.full_like(iou, -1.))
+            best = iou.max(0).values
+            first = torch.where(iou == best[None], torch.arange(2 * G)[:, None], torch.tensor(2 * G)).min(0).values
+            m = (best >= thr) & ~dropped
+            matched[m] = first[m].int()
+            win = {}                                             # ground-truth box -> winning detection
+            for d in torch.nonzero(m).squeeze(1).tolist():
+                j = int(first[d])
+                if j not in win or float(sc[d]) > float(sc[win[j]]):
+                    win[j] = d
+            if win:
+                labels[list(win.values())] = 1
+            live = ~dropped
+            ch = (box_iou(bh, boxes) >= thr) & (live & (cls == self.human_idx))[None]              # [G, n]
+            co = (box_iou(bo, boxes) >= thr) & live[None] & (cls[None] == ob[:, None])
+            same = (ch.sum(1) == 1) & (co.sum(1) == 1) & (ch & co).any(1)                   # one detection on both sides
+            covered = (ch.any(1) & co.any(1) & ~same).to(torch.uint8)
+        self._scores.append(sc); self._cls.append(cls); self._labels.append(labels)
+        self._pairs += G; self._covered += int(covered.sum())
+        if self.num_hoi is not None and hoi is not None:
+            inside = (hoi >= 0) & (hoi < self.num_hoi)
+            self._hoi_pairs += torch.bincount(hoi[inside], minlength=self.num_hoi)
+            self._hoi_covered += torch.bincount(hoi[inside & covered.bool()], minlength=self.num_hoi)
+        return labels, keep, matched, covered
+
+    def add(self, detections, targets):
+        if len(detections) != len(targets):
+            raise ValueError("%d detections for %d targets" % (len(detections), len(targets)))
+        res = [self._one(d, t) for d, t in zip(detections, targets)]
+        self.last_gt_keep = [r[1] for r in res]; self.last_matched = [r[2] for r in res]; self.last_covered = [r[3] for r in res]
+        return [r[0] for r in res]
+
+    def summary(self):
+        C = self.num_classes
+        sc = torch.cat(self._scores) if self._scores else torch.zeros(0)
+        cls = torch.cat(self._cls) if self._cls else torch.zeros(0, dtype=torch.int64)
+        lab = torch.cat(self._labels) if self._labels else torch.zeros(0, dtype=torch.int8)
+        live = lab >= 0                                          # dropped detections never reach the ranking
+        sc, cls, lab = sc[live].double(), cls[live], lab[live].double()
+        ap = torch.zeros(C, dtype=torch.float64)
+        for c in cls.unique().tolist():
+            m = cls == c
+            ap[c] = DetectionAPMeter._ap(sc[m], lab[m], int(self.num_gt[c]), self.algorithm)
+        tp = torch.zeros(C, dtype=torch.float64).index_add_(0, cls, lab)
+        return _det_summary(ap, self.num_gt.clone(), tp, self._pairs, self._covered, self._hoi_pairs, self._hoi_covered)
+
+
+class DeviceDetectionEvaluator:
+    """DetectionEvaluator on the device, for batches of any size: one skg_eval_det_match_f32 launch (ground-truth NMS,
+    association, num_gt by integer atomics) and one skg_eval_pair_cover_u8 launch per `add`, no host synchronisation there;
+    scores, classes, labels and coverage flags stay on the device.  `summary()` drops the -1 cells, sorts twice (stable) and
+    launches the AP kernel of `algorithm`; max_rec comes from an index_add_ of the labels.  Same labels, flags and numbers as
+    the host evaluator, same interface; the `last_*` lists are views of device tensors.  An image with more than
+    SKG_EVAL_DET_MAX_GT ground-truth boxes (2 per pair) and a class outside [0, num_classes) are reported by `summary()`."""
+    batched = True
+
+    def __init__(self, num_classes=80, human_idx=49, min_iou=0.5, nms_thresh=0.5, algorithm="AUC", num_hoi=None, device="cuda"):
+        if algorithm not in ("11P", "AUC"):
+            raise ValueError("unknown algorithm %s" % algorithm)
+        if not 0 <= int(human_idx) < int(num_classes):
+            raise ValueError("human_idx %d is outside the %d classes" % (human_idx, num_classes))
+        self.num_classes, self.human_idx = int(num_classes), int(human_idx)
+        self.min_iou, self.nms_thresh, self.algorithm = float(min_iou), float(nms_thresh), algorithm
+        self.num_hoi = None if num_hoi is None else int(num_hoi)
+        self.device = torch.device(device)
+        self.num_gt = torch.zeros(self.num_classes, dtype=torch.int64, device=self.device)
+        self.status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.thr = torch.linspace(0, 1, 11, dtype=torch.float64).to(self.device)
+        self._scores, self._cls, self._labels, self._covered, self._hoi = [], [], [], [], []
+        self.last_gt_keep, self.last_matched, self.last_covered = [], [], []
+
+    def add(self, detections, targets):
+        """As DetectionEvaluator.add; the returned tensors are views of one device tensor."""
+        from . import _capi
+        from .engine import _stream
+        dev = self.device
+        n = len(detections)
+        if n != len(targets):
+            raise ValueError("%d detections for %d targets" % (n, len(targets)))
+        self.last_gt_keep, self.last_matched, self.last_covered = [], [], []
+        if n == 0:
+            return []
+        boxes = torch.cat([torch.as_tensor(d["boxes"]).to(dev).float().reshape(-1, 4) for d in detections]).contiguous()
+        per = [int(torch.as_tensor(d["scores"]).numel()) for d in detections]
+        scores = torch.cat([torch.as_tensor(d["scores"]).to(dev).float().reshape(-1) for d in detections]).contiguous()
+        cls = torch.cat([torch.as_tensor(d["labels"]).to(dev).long().reshape(-1) for d in detections]).contiguous()
+        if not boxes.shape[0] == scores.shape[0] == cls.shape[0]:
+            raise ValueError("boxes, scores and labels of the detections disagree on their number")
+        tg = [_det_target(t, dev) for t in targets]
+        gts = [int(t[2].shape[0]) for t in tg]
+        gt_h = torch.cat([t[0] for t in tg]).contiguous(); gt_o = torch.cat([t[1] for t in tg]).contiguous()
+        gt_ob = torch.cat([t[2] for t in tg]).contiguous()
+        offs = np.zeros(2 * (n + 1), np.int32)                       # det_off | gt_off, n + 1 entries each
+        offs[1:n + 1] = np.cumsum(per); offs[n + 2:] = np.cumsum(gts)
+        offs_d = torch.from_numpy(offs).to(dev)
+        L, Ng = int(sum(per)), int(sum(gts))
+        labels = torch.zeros(max(L, 1), dtype=torch.int8, device=dev)
+        matched = torch.full((max(L, 1),), -1, dtype=torch.int32, device=dev)
+        gt_keep = torch.zeros(max(2 * Ng, 1), dtype=torch.uint8, device=dev)
+        covered = torch.zeros(max(Ng, 1), dtype=torch.uint8, device=dev)
+        pad = lambda t: t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+        boxes_p, scores_p, cls_p, gt_h, gt_o, gt_ob = map(pad, (boxes, scores, cls, gt_h, gt_o, gt_ob))
+        _capi.check(_capi.lib().skg_eval_det_match_f32(
+            boxes_p.data_ptr(), scores_p.data_ptr(), cls_p.data_ptr(), offs_d.data_ptr(), n, gt_h.data_ptr(), gt_o.data_ptr(),
+            gt_ob.data_ptr(), offs_d.data_ptr() + 4 * (n + 1), self.human_idx, self.num_classes, self.min_iou, self.nms_thresh,
+            labels.data_ptr(), matched.data_ptr(), gt_keep.data_ptr(), self.num_gt.data_ptr(), self.status.data_ptr(),
+            _stream()), "skg_eval_det_match_f32")
+        _capi.check(_capi.lib().skg_eval_pair_cover_u8(
+            boxes_p.data_ptr(), cls_p.data_ptr(), labels.data_ptr(), offs_d.data_ptr(), n, gt_h.data_ptr(), gt_o.data_ptr(),
+            gt_ob.data_ptr(), offs_d.data_ptr() + 4 * (n + 1), self.human_idx, self.min_iou, covered.data_ptr(), _stream()),
+            "skg_eval_pair_cover_u8")
+        self._scores.append(scores); self._cls.append(cls); self._labels.append(labels[:L]); self._covered.append(covered[:Ng])
+        if self.num_hoi is not None:                                 # -1: a pair of a target without `hoi`
+            self._hoi.append(torch.cat([t[3] if t[3] is not None else torch.full_like(t[2], -1) for t in tg]))
+        self.last_gt_keep = list(gt_keep[:2 * Ng].split([2 * g for g in gts]))
+        self.last_matched = list(matched[:L].split(per)); self.last_covered = list(covered[:Ng].split(gts))
+        return list(labels[:L].split(per))
+
+    def summary(self):
+        """As DetectionEvaluator.summary (tensors on the host)."""
+        from . import _capi
+        dev, C = self.device, self.num_classes
+        over, outside = self.status.cpu().tolist()
+        if over:
+            raise _capi.SkgError("an image has %d ground-truth boxes; skg_eval_det_match_f32 keeps at most %d per image"
+                                 % (over, _capi.EVAL_DET_MAX_GT))
+        ap = torch.zeros(C, dtype=torch.float64, device=dev)
+        tp = torch.zeros(C, dtype=torch.float64, device=dev)
+        pairs = covered = 0
+        if self._scores:
+            scores = torch.cat(self._scores); cls = torch.cat(self._cls); labels = torch.cat(self._labels)
+            if outside or bool(((cls < 0) | (cls >= C)).any()):
+                raise IndexError("a detection or ground-truth class is outside [0, %d)" % C)
+            live = labels >= 0                                       # dropped detections never reach the ranking
+            sc, cl, lab = scores[live], cls[live], labels[live].float()
+            if sc.numel():
+                o1 = torch.sort(sc, descending=True, stable=True).indices       # score descending, arrival order on ties
+                o2 = torch.sort(cl[o1], stable=True).indices                    # ... then class ascending, order kept
+                lab_sorted = lab[o1[o2]].contiguous()
+                class_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+                class_off[1:] = torch.cumsum(torch.bincount(cl, minlength=C), 0)
+                _launch_ap(self.algorithm, lab_sorted, class_off, self.num_gt, ap, self.thr)
+                tp.index_add_(0, cl, lab.double())
+            cov = torch.cat(self._covered)
+            pairs, covered = int(cov.numel()), int(cov.sum())
+        hoi_pairs = hoi_covered = None
+        if self.num_hoi is not None:
+            hoi_pairs = torch.zeros(self.num_hoi, dtype=torch.int64); hoi_covered = hoi_pairs.clone()
+            if self._hoi:
+                hoi = torch.cat(self._hoi)
+                inside = (hoi >= 0) & (hoi < self.num_hoi)
+                hoi_pairs = torch.bincount(hoi[inside], minlength=self.num_hoi).cpu()
+                hoi_covered = torch.bincount(hoi[inside & cov.bool()], minlength=self.num_hoi).cpu()
+        return _det_summary(ap.cpu(), self.num_gt.cpu(), tp.cpu(), pairs, covered, hoi_pairs, hoi_covered)
 
 
 # ----------------------------------------------------------------------------------------------- exporters

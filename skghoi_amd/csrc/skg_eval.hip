@@ -53,6 +53,24 @@ __device__ __forceinline__ uint32_t ev_orderable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// The bid of the matching kernels for LDS atomicMax: (score, then the lower rank on ties) as one ordered 64-bit key; 0 = no
+// bid.  The caller chooses the score bits: `s + 0.f` makes -0 bid like +0.
+__device__ __forceinline__ unsigned long long ev_bid_key(float s, unsigned rank) {
+    return ((unsigned long long)ev_orderable(s) << 32) | (0xffffffffu - rank);
+}
+
+// Inclusive scan of v over the 64 lanes of a wave, by sum or (kMax) by maximum; lane l combines lanes 0 .. l in the fixed
+// order of the doubling steps.
+template <bool kMax>
+__device__ __forceinline__ double ev_wave_scan(double v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(v, off, 64);
+        if (lane >= off) v = kMax ? fmax(v, o) : v + o;
+    }
+    return v;
+}
+
 __global__ __launch_bounds__(256) void skg_eval_associate_kernel(
     const float* __restrict__ boxes_h, const float* __restrict__ boxes_o, const int64_t* __restrict__ object,
     const int32_t* __restrict__ pair_off, const int64_t* __restrict__ index, const int64_t* __restrict__ pred,
@@ -90,19 +108,14 @@ __global__ __launch_bounds__(256) void skg_eval_associate_kernel(
             }
             if (!(best >= min_iou)) match = -1;
         }
-        // (score, lower index wins ties) as one ordered 64-bit key; 0 = no bid
-        const unsigned long long key =
-            ((unsigned long long)ev_orderable(scores[c]) << 32) | (unsigned)(0xffffffffu - (unsigned)(c - c0));
-        if (match >= 0) atomicMax(&skey[match], key);
+        if (match >= 0) atomicMax(&skey[match], ev_bid_key(scores[c], (unsigned)(c - c0)));      // the score's bits as they are
         labels[c] = match >= 0 ? __uint_as_float((unsigned)match + 1u) : 0.f;      // parked: match + 1 as raw bits
     }
     __syncthreads();
     for (int c = c0 + tid; c < c1; c += 256) {
         const unsigned m = __float_as_uint(labels[c]);
         if (m == 0u) continue;
-        const unsigned long long key =
-            ((unsigned long long)ev_orderable(scores[c]) << 32) | (unsigned)(0xffffffffu - (unsigned)(c - c0));
-        labels[c] = (skey[m - 1u] == key) ? 1.f : 0.f;
+        labels[c] = (skey[m - 1u] == ev_bid_key(scores[c], (unsigned)(c - c0))) ? 1.f : 0.f;
     }
 }
 
@@ -189,13 +202,7 @@ __global__ __launch_bounds__(256) void skg_eval_ap11_kernel(const float* __restr
     for (int64_t i0 = s0; i0 < s1; i0 += 256) {
         const int64_t i = i0 + tid;
         const double y = i < s1 ? (double)labels_sorted[i] : 0.0;
-        // inclusive scan of y over the 256 lanes of this tile
-        double inc = y;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const double inc = ev_wave_scan<false>(y, lane);     // per wave; the waves before it are added below
         if (lane == 63) swave[wv] = inc;
         __syncthreads();
         double tp = sbase + inc;
@@ -302,9 +309,7 @@ __global__ __launch_bounds__(256) void skg_eval_vcoco_match_kernel(
                 }
                 const int bits = (ov1 >= thr ? 1 : 0) | (ov2 >= thr ? 2 : 0);
                 if (bits) {
-                    // (score, lower index wins ties) as one ordered 64-bit key; 0 = no bid.  s + 0: -0 bids like +0
-                    const unsigned long long key =
-                        ((unsigned long long)ev_orderable(s + 0.f) << 32) | (unsigned)(0xffffffffu - (unsigned)(c - c0));
+                    const unsigned long long key = ev_bid_key(s + 0.f, (unsigned)(c - c0));      // s + 0: -0 bids like +0
                     if (bits & 1) atomicMax(&skey[0][jmax], key);
                     if (bits & 2) atomicMax(&skey[1][jmax], key);
                     o1 = (int8_t)(uint8_t)jmax; o2 = (int8_t)bits;
@@ -319,8 +324,7 @@ __global__ __launch_bounds__(256) void skg_eval_vcoco_match_kernel(
         const int bits = labels_s2[c];
         if (bits <= 0) continue;                             // final already: 0 or -1 in both
         const int jmax = (int)(uint8_t)labels_s1[c];
-        const unsigned long long key =
-            ((unsigned long long)ev_orderable(scores[c] + 0.f) << 32) | (unsigned)(0xffffffffu - (unsigned)(c - c0));
+        const unsigned long long key = ev_bid_key(scores[c] + 0.f, (unsigned)(c - c0));
         labels_s1[c] = ((bits & 1) && skey[0][jmax] == key) ? 1 : 0;
         labels_s2[c] = ((bits & 2) && skey[1][jmax] == key) ? 1 : 0;
     }
@@ -371,22 +375,13 @@ __global__ __launch_bounds__(256) void skg_eval_ap_voc_kernel(const float* __res
         const int64_t i = e - 1 - tid;
         const bool valid = i >= s0;
         const double y = valid ? (double)labels_sorted[i] : 0.0;
-        double inc = y;                                      // labels at positions >= i of this tile
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
+        const double inc = ev_wave_scan<false>(y, lane);     // labels at positions >= i of this wave's part of the tile
         if (lane == 63) swsum[wv] = inc;
         __syncthreads();
         double behind = sbase_sum + (inc - y);               // labels at positions > i of the class
         for (int w = 0; w < wv; ++w) behind += swsum[w];
-        double m = valid ? (total - behind) / (double)(i - s0 + 1) : 0.0;       // prec_i, then its suffix maximum
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double o = __shfl_up(m, off, 64);
-            if (lane >= off) m = fmax(m, o);
-        }
+        // prec_i, then its suffix maximum
+        double m = ev_wave_scan<true>(valid ? (total - behind) / (double)(i - s0 + 1) : 0.0, lane);
         if (lane == 63) swmax[wv] = m;
         __syncthreads();
         m = fmax(m, sbase_max);
@@ -516,10 +511,7 @@ __global__ __launch_bounds__(256) void skg_eval_det_match_kernel(
                 if (v > best) { best = v; match = j; }       // first maximum, NaN never wins
             }
             if (!(best >= min_iou)) match = -1;
-            // (score, lower index wins ties) as one ordered 64-bit key; 0 = no bid.  s + 0: -0 bids like +0
-            if (match >= 0)
-                atomicMax(&skey[match], ((unsigned long long)ev_orderable(s + 0.f) << 32) |
-                                            (unsigned)(0xffffffffu - (unsigned)(d - d0)));
+            if (match >= 0) atomicMax(&skey[match], ev_bid_key(s + 0.f, (unsigned)(d - d0)));      // s + 0: -0 bids like +0
         }
         matched_gt[d] = match;                               // final; the same lane reads it back behind the barrier
     }
@@ -530,11 +522,7 @@ __global__ __launch_bounds__(256) void skg_eval_det_match_kernel(
         if (s != s) lab = -1;                                // dropped
         else {
             const int m = matched_gt[d];
-            if (m >= 0) {
-                const unsigned long long key =
-                    ((unsigned long long)ev_orderable(s + 0.f) << 32) | (unsigned)(0xffffffffu - (unsigned)(d - d0));
-                lab = skey[m] == key ? 1 : 0;
-            }
+            if (m >= 0) lab = skey[m] == ev_bid_key(s + 0.f, (unsigned)(d - d0)) ? 1 : 0;
         }
         labels[d] = lab;
     }

@@ -66,18 +66,24 @@ def associate_pairs(gt_h, gt_o, det_h, det_o, scores, min_iou=0.5):
     return labels
 
 
+def _check_algorithm(algorithm):
+    if algorithm not in ("11P", "AUC"):
+        raise ValueError("unknown algorithm %s" % algorithm)
+    return algorithm
+
+
 class DetectionAPMeter:
     """pocket.utils.DetectionAPMeter(num_cls, num_gt=..., algorithm='11P'): per-class lists of (score, label),
-    AP = mean over t in {0, 0.1, ..., 1} of max precision at recall >= t (float64)."""
+    AP = mean over t in {0, 0.1, ..., 1} of max precision at recall >= t (float64); algorithm='AUC': the VOC all-point area.
+    The one AP implementation of the host: every host evaluator ranks through it (a class's detections score descending,
+    equal scores in arrival order)."""
 
     def __init__(self, num_cls, num_gt=None, algorithm="11P"):
-        if algorithm not in ("11P", "AUC"):
-            raise ValueError("unknown algorithm %s" % algorithm)
+        self.algorithm = _check_algorithm(algorithm)
         self.num_cls = num_cls
         # num_gt=None (the training / validation meter of utils.py:208, 285): recall is taken over the positives among the
         # logged detections of the class
         self.num_gt = None if num_gt is None else [int(v) for v in num_gt]
-        self.algorithm = algorithm
         self.reset()
 
     def reset(self):
@@ -123,18 +129,58 @@ class DetectionAPMeter:
         return out
 
 
-def _launch_ap(algorithm, lab_sorted, class_off, num_gt, ap, thr11):
-    """The per-class APs of globally sorted labels on the device: '11P' = skg_eval_ap11_f64 over the eleven recall
-    thresholds `thr11`, 'AUC' = skg_eval_ap_voc_f64 (VOC all-point area)."""
+# ----------------------------------------------------------------------------------------------- shared by the device evaluators
+_THR11 = {}                                                      # device -> the eleven recall thresholds of '11P' (float64)
+
+
+def _class_aps_device(algorithm, scores, classes, labels, num_cls, num_gt):
+    """The ranking of every device evaluator: (scores, classes int64 in [0, num_cls), 0/1 labels) of the detections in
+    arrival order and num_gt [num_cls] int64, all on one device -> the per-class APs, float64 [num_cls] on that device.
+    Two stable sorts -- score descending, then class ascending on top of it, so equal scores of a class stay in arrival
+    order -- and one launch: '11P' = skg_eval_ap11_f64, 'AUC' = skg_eval_ap_voc_f64 (VOC all-point area).  Same numbers as
+    DetectionAPMeter over the same triples.  No detections: zeros, nothing launched."""
     from . import _capi
     from .engine import _stream
+    dev = scores.device
+    ap = torch.zeros(num_cls, dtype=torch.float64, device=dev)
+    if scores.numel() == 0 or num_cls == 0:
+        return ap
+    o1 = torch.sort(scores, descending=True, stable=True).indices          # score descending, arrival order on ties
+    o2 = torch.sort(classes[o1], stable=True).indices                      # ... then class ascending, order kept
+    lab_sorted = labels[o1[o2]].float().contiguous()
+    class_off = torch.zeros(num_cls + 1, dtype=torch.int64, device=dev)
+    class_off[1:] = torch.cumsum(torch.bincount(classes, minlength=num_cls), 0)
     if algorithm == "AUC":
         _capi.check(_capi.lib().skg_eval_ap_voc_f64(lab_sorted.data_ptr(), class_off.data_ptr(), num_gt.data_ptr(),
-                                                    ap.shape[0], ap.data_ptr(), _stream()), "skg_eval_ap_voc_f64")
+                                                    num_cls, ap.data_ptr(), _stream()), "skg_eval_ap_voc_f64")
     else:
+        if dev not in _THR11:
+            _THR11[dev] = torch.linspace(0, 1, 11, dtype=torch.float64).to(dev)
         _capi.check(_capi.lib().skg_eval_ap11_f64(lab_sorted.data_ptr(), class_off.data_ptr(), num_gt.data_ptr(),
-                                                  ap.shape[0], thr11.data_ptr(), ap.data_ptr(), _stream()),
+                                                  num_cls, _THR11[dev].data_ptr(), ap.data_ptr(), _stream()),
                     "skg_eval_ap11_f64")
+    return ap
+
+
+def _offset_table(device, *counts):
+    """Per-image count lists (n entries each) -> their running sums packed in one int32 device tensor, n + 1 entries per
+    list starting at 0, and the base address of each list's part (what the kernels take as pair_off / cell_off / gt_off)."""
+    n = len(counts[0])
+    offs = np.zeros((len(counts), n + 1), np.int32)
+    for row, c in zip(offs, counts):
+        row[1:] = np.cumsum(c)
+    offs_d = torch.from_numpy(offs.reshape(-1)).to(device)
+    return offs_d, [offs_d.data_ptr() + 4 * (n + 1) * k for k in range(len(counts))]
+
+
+def _pad_row(t):
+    """An empty tensor as one row of zeros, so that data_ptr() is an address a kernel may be handed; others as they are."""
+    return t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+
+
+def _cat_results(outputs, key, device):
+    """The tensors under `key` of the head's per-image result dicts as one contiguous device tensor."""
+    return torch.cat([o[key].reshape(-1, *o[key].shape[1:]) for o in outputs]).to(device).contiguous()
 
 
 class DeviceAPMeter:
@@ -142,20 +188,18 @@ class DeviceAPMeter:
     batch's (scores, prediction, labels) are moved to the host, all-gathered over the ranks and appended to a
     DetectionAPMeter(num_classes, algorithm='11P') on rank 0) without the per-iteration host synchronisation and collective:
     `append` keeps the batch's three DEVICE tensors (no copy, no sync: the step loop stays asynchronous); `eval()` -- called
-    once, at the end of an epoch -- gathers the ranks' logs in one padded all_gather, sorts on the device and computes the
-    per-class 11-point APs with skg_eval_ap11_f64 (float64), on every rank.  Same numbers as DetectionAPMeter over the same
+    once, at the end of an epoch -- gathers the ranks' logs in one padded all_gather and ranks them on the device
+    (_class_aps_device: the per-class 11-point APs, float64), on every rank.  Same numbers as DetectionAPMeter over the same
     detections; ties between equal scores of one class resolve by rank, then arrival order (the reference: iteration, then
     rank).  num_gt=None like the reference's meters: recall over the positives among the logged detections.
     algorithm="AUC": the VOC all-point area instead (skg_eval_ap_voc_f64; DetectionAPMeter's 'AUC' branch)."""
 
     def __init__(self, num_cls, num_gt=None, device="cuda", group=None, algorithm="11P"):
-        if algorithm not in ("11P", "AUC"):
-            raise ValueError("unknown algorithm %s" % algorithm)
+        self.algorithm = _check_algorithm(algorithm)             # "AUC": skg_eval_ap_voc_f64 (the host meter's AUC branch)
         self.num_cls = int(num_cls)
         self.num_gt = None if num_gt is None else [int(v) for v in num_gt]
         self.device = torch.device(device)
         self.group = group
-        self.algorithm = algorithm                               # "AUC": skg_eval_ap_voc_f64 (the host meter's AUC branch)
         self.reset()
 
     def reset(self):
@@ -187,9 +231,8 @@ class DeviceAPMeter:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
             from .dist import _all_gather_ragged
             mine = torch.cat(_all_gather_ragged(mine.contiguous(), self.group))
-        ap = torch.zeros(self.num_cls, dtype=torch.float64, device=dev)
         if mine.shape[0] == 0:
-            return ap.cpu()
+            return torch.zeros(self.num_cls, dtype=torch.float64)
         if dev.type != "cuda":                                  # (CPU tensors: rehearsals over gloo) the host meter
             m = DetectionAPMeter(self.num_cls, self.num_gt, self.algorithm)
             m.append(mine[:, 0], mine[:, 1].long(), mine[:, 2])
@@ -197,18 +240,11 @@ class DeviceAPMeter:
         scores, cls, labels = mine[:, 0].contiguous(), mine[:, 1].long(), mine[:, 2].contiguous()
         if ((cls < 0) | (cls >= self.num_cls)).any():
             raise IndexError("a logged prediction is outside [0, %d)" % self.num_cls)
-        o1 = torch.sort(scores, descending=True, stable=True).indices
-        o2 = torch.sort(cls[o1], stable=True).indices
-        order = o1[o2]
-        lab_sorted = labels[order].contiguous()
-        class_off = torch.zeros(self.num_cls + 1, dtype=torch.int64, device=dev)
-        class_off[1:] = torch.cumsum(torch.bincount(cls, minlength=self.num_cls), 0)
         if self.num_gt is None:
             num_gt = torch.zeros(self.num_cls, device=dev, dtype=torch.float64).index_add_(0, cls, labels.double()).long()
         else:
             num_gt = torch.as_tensor(self.num_gt, dtype=torch.int64, device=dev)
-        _launch_ap(self.algorithm, lab_sorted, class_off, num_gt, ap, torch.linspace(0, 1, 11, dtype=torch.float64).to(dev))
-        return ap.cpu()
+        return _class_aps_device(self.algorithm, scores, cls, labels, self.num_cls, num_gt).cpu()
 
 
 # ----------------------------------------------------------------------------------------------- HICO-DET settings
@@ -330,20 +366,19 @@ class HOIEvaluator:
 
 class DeviceHOIEvaluator:
     """utils.test (utils.py:148-198) on the device, for batches of any size: interaction lookup + box-pair association in
-    one launch per batch (skg_eval_associate_f32), detections kept on the device, and at the end two stable device sorts
-    plus one launch for the 600 eleven-point APs (skg_eval_ap11_f64, float64).  Same numbers as HOIEvaluator (the host
+    one launch per batch (skg_eval_associate_f32), detections kept on the device, and at the end the shared device ranking
+    (_class_aps_device) for the 600 eleven-point APs, float64.  Same numbers as HOIEvaluator (the host
     restatement the oracle pins); use it when the head runs batched and the results should not travel to the host.
     algorithm="AUC": the VOC all-point area instead (skg_eval_ap_voc_f64; the host meter's 'AUC' branch).
     splits / known_object: as for HOIEvaluator.  known_object=True adds one skg_eval_known_object_u8 launch per `add`, behind
     the association and without a host synchronisation (`last_keep`: per-image uint8 views of one device tensor), and at the
-    end the same two sorts and AP launch over the kept cells."""
+    end the same ranking a second time, over the kept cells."""
+    batched = True                                               # trainer.test feeds lists
 
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, device="cuda",
                  algorithm="11P", known_object=False, splits=None):
         from . import _capi
-        if algorithm not in ("11P", "AUC"):
-            raise ValueError("unknown algorithm %s" % algorithm)
-        self.algorithm = algorithm                               # "AUC": the 600 APs by skg_eval_ap_voc_f64
+        self.algorithm = _check_algorithm(algorithm)             # "AUC": the 600 APs by skg_eval_ap_voc_f64
         self.device = torch.device(device)
         lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
             else hico_object_n_verb_to_interaction()
@@ -353,7 +388,6 @@ class DeviceHOIEvaluator:
         self.num_gt = torch.as_tensor([int(v) for v in num_gt_test], dtype=torch.int64, device=self.device)
         self.min_iou = float(min_iou)
         self.num_anno_train = None if num_anno_train is None else torch.as_tensor(num_anno_train)
-        self.thr = torch.linspace(0, 1, 11, dtype=torch.float64).to(self.device)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._scores, self._hoi, self._labels = [], [], []
         self.splits = _check_splits(splits, self.num_cls)
@@ -377,7 +411,7 @@ class DeviceHOIEvaluator:
                 self.last_keep = []
             return []
         ppi = [int(o["boxes_h"].shape[0]) for o in outputs]; cpi = [int(o["scores"].shape[0]) for o in outputs]
-        cat = lambda k, dt=None: torch.cat([o[k].reshape(-1, *o[k].shape[1:]) for o in outputs]).to(dev).contiguous()
+        cat = lambda k: _cat_results(outputs, k, dev)
         boxes_h = cat("boxes_h").float(); boxes_o = cat("boxes_o").float(); obj = cat("object").long()
         index = cat("index").long(); pred = cat("prediction").long(); scores = cat("scores").float().contiguous()
         gts = [int(t["boxes_h"].shape[0]) for t in targets]
@@ -387,40 +421,23 @@ class DeviceHOIEvaluator:
         if gt_h.shape[0] == 0:
             gt_h = torch.zeros(1, 4, device=dev); gt_o = torch.zeros(1, 4, device=dev)
             gt_hoi = torch.full((1,), -1, dtype=torch.int64, device=dev)
-        offs = np.zeros(3 * (n + 1), np.int32)
-        offs[1:n + 1] = np.cumsum(ppi)                               # pair_off (n used) | cell_off | gt_off
-        offs[n + 2:2 * n + 2] = np.cumsum(cpi); offs[2 * n + 3:] = np.cumsum(gts)
-        offs_d = torch.from_numpy(offs).to(dev)
+        offs_d, (pair_off, cell_off, gt_off) = _offset_table(dev, ppi, cpi, gts)
         L = int(sum(cpi))
         hoi = torch.empty(max(L, 1), dtype=torch.int32, device=dev); labels = torch.zeros(max(L, 1), device=dev)
-        pad4 = lambda t: t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-        boxes_h, boxes_o, obj, index, pred, scores = map(pad4, (boxes_h, boxes_o, obj, index, pred, scores))
+        boxes_h, boxes_o, obj, index, pred, scores = map(_pad_row, (boxes_h, boxes_o, obj, index, pred, scores))
         _capi.check(_capi.lib().skg_eval_associate_f32(
-            boxes_h.data_ptr(), boxes_o.data_ptr(), obj.data_ptr(), offs_d.data_ptr(), index.data_ptr(), pred.data_ptr(),
-            scores.data_ptr(), offs_d.data_ptr() + 4 * (n + 1), n, self.lut.data_ptr(), self.n_obj, self.n_verb,
-            gt_h.data_ptr(), gt_o.data_ptr(), gt_hoi.data_ptr(), offs_d.data_ptr() + 8 * (n + 1), self.min_iou,
-            hoi.data_ptr(), labels.data_ptr(), self.status.data_ptr(), _stream()), "skg_eval_associate_f32")
+            boxes_h.data_ptr(), boxes_o.data_ptr(), obj.data_ptr(), pair_off, index.data_ptr(), pred.data_ptr(),
+            scores.data_ptr(), cell_off, n, self.lut.data_ptr(), self.n_obj, self.n_verb, gt_h.data_ptr(), gt_o.data_ptr(),
+            gt_hoi.data_ptr(), gt_off, self.min_iou, hoi.data_ptr(), labels.data_ptr(), self.status.data_ptr(), _stream()),
+            "skg_eval_associate_f32")
         self._scores.append(scores[:L]); self._hoi.append(hoi[:L]); self._labels.append(labels[:L])
         if self.known_object:                                        # behind the association, on its hoi_out
             keep = torch.zeros(max(L, 1), dtype=torch.uint8, device=dev)
             _capi.check(_capi.lib().skg_eval_known_object_u8(
-                hoi.data_ptr(), offs_d.data_ptr() + 4 * (n + 1), n, self.hoi_object.data_ptr(), self.num_cls, self.n_obj,
-                gt_hoi.data_ptr(), offs_d.data_ptr() + 8 * (n + 1), keep.data_ptr(), _stream()), "skg_eval_known_object_u8")
+                hoi.data_ptr(), cell_off, n, self.hoi_object.data_ptr(), self.num_cls, self.n_obj, gt_hoi.data_ptr(), gt_off,
+                keep.data_ptr(), _stream()), "skg_eval_known_object_u8")
             self._keep.append(keep[:L]); self.last_keep = list(keep[:L].split(cpi))
         return list(labels[:L].split(cpi))
-
-    def _ap_of(self, scores, hoi, labels):
-        """The per-class APs of (scores, classes, labels) in arrival order: two stable sorts and one launch."""
-        dev = self.device
-        ap = torch.zeros(self.num_cls, dtype=torch.float64, device=dev)
-        o1 = torch.sort(scores, descending=True, stable=True).indices      # score descending, arrival order on ties
-        o2 = torch.sort(hoi[o1], stable=True).indices                      # ... then class ascending, order kept
-        order = o1[o2]
-        lab_sorted = labels[order].contiguous()
-        class_off = torch.zeros(self.num_cls + 1, dtype=torch.int64, device=dev)
-        class_off[1:] = torch.cumsum(torch.bincount(hoi, minlength=self.num_cls), 0)
-        _launch_ap(self.algorithm, lab_sorted, class_off, self.num_gt, ap, self.thr)
-        return ap
 
     def summary(self):
         from . import _capi
@@ -433,10 +450,10 @@ class DeviceHOIEvaluator:
             scores = torch.cat(self._scores); hoi = torch.cat(self._hoi).long(); labels = torch.cat(self._labels)
             if (hoi < 0).any():
                 raise IndexError("a predicted (object, verb) pair is not a valid interaction")
-            ap = self._ap_of(scores, hoi, labels)
+            ap = _class_aps_device(self.algorithm, scores, hoi, labels, self.num_cls, self.num_gt)
             if self.known_object:                                    # the same rule over the kept cells (their order kept)
                 keep = torch.cat(self._keep).bool()
-                ap_ko = self._ap_of(scores[keep], hoi[keep], labels[keep])
+                ap_ko = _class_aps_device(self.algorithm, scores[keep], hoi[keep], labels[keep], self.num_cls, self.num_gt)
         out = _hoi_summary(ap.cpu(), self.num_anno_train, self.splits)
         if self.known_object:
             out["known_object"] = _hoi_summary(ap_ko.cpu(), self.num_anno_train, self.splits)
@@ -507,19 +524,11 @@ def _vsrl_iou(gt, det):
     return inter / (a_gt + a_det - inter)
 
 
-def _voc_ap(labels_sorted, npos):
-    """The toolkit's voc_ap (VOC all-point AP, float64) of one class's 0/1 labels in score order."""
-    lab = np.asarray(labels_sorted, dtype=np.float64)
-    tp = np.cumsum(lab); fp = np.cumsum(1.0 - lab)
-    rec = tp / float(npos)
-    prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
-    mrec = np.concatenate(([0.0], rec, [1.0])); mpre = np.concatenate(([0.0], prec, [0.0]))
-    mpre = np.maximum.accumulate(mpre[::-1])[::-1]               # monotone from the right
-    idx = np.where(mrec[1:] != mrec[:-1])[0] + 1
-    return float(np.sum((mrec[idx] - mrec[idx - 1]) * mpre[idx]))
-
-
 def _vcoco_summary(table, ap_s1, ap_s2, npos):
+    """The summary both V-COCO evaluators return (host tensors); the APs of the classes without a person doing the action
+    (npos == 0) become NaN here."""
+    none = npos[torch.tensor([aid for aid, _ in table], dtype=torch.int64)] == 0
+    ap_s1[none] = float("nan"); ap_s2[none] = float("nan")
     out = dict(role_ap_s1=ap_s1, role_ap_s2=ap_s2, npos=npos)
     for tag, ap in (("s1", ap_s1), ("s2", ap_s2)):
         out["mean_" + tag] = float(torch.nanmean(ap)) if len(table) else float("nan")
@@ -615,20 +624,17 @@ class VCOCOEvaluator:
         labels = torch.cat(self._labels) if self._labels else torch.zeros(0, 2, dtype=torch.int8)
         aps = []
         for s in range(2):
-            ap = torch.full((K,), float("nan"), dtype=torch.float64)
-            for k, (aid, _) in enumerate(self.table):
-                if int(self.npos[aid]) > 0:
-                    m = (pred == k) & (labels[:, s] >= 0)
-                    order = torch.argsort(scores[m], descending=True, stable=True)
-                    ap[k] = _voc_ap(labels[m, s][order].numpy(), int(self.npos[aid]))
-            aps.append(ap)
+            meter = DetectionAPMeter(K, num_gt=[int(self.npos[aid]) for aid, _ in self.table], algorithm="AUC")
+            keep = labels[:, s] >= 0                                 # dropped cells never reach the ranking
+            meter.append(scores[keep], pred[keep], labels[keep, s])
+            aps.append(meter.eval())
         return _vcoco_summary(self.table, aps[0], aps[1], self.npos.clone())
 
 
 class DeviceVCOCOEvaluator:
     """VCOCOEvaluator on the device, for batches of any size: one skg_eval_vcoco_match_f32 launch per `add` (both scenarios),
-    detections, labels and npos kept on the device, and at the end, per scenario, two stable device sorts plus one
-    skg_eval_ap_voc_f64 launch (float64).  Same labels and APs as the host evaluator; same rule, same interface -- callers
+    detections, labels and npos kept on the device, and at the end, per scenario, the shared device ranking
+    (_class_aps_device, 'AUC').  Same labels and APs as the host evaluator; same rule, same interface -- callers
     must add every test image, also those without detections.  An image with more than 256 persons is reported by
     `summary()`, like the 2048 ground-truth pairs of DeviceHOIEvaluator."""
     batched = True
@@ -656,7 +662,7 @@ class DeviceVCOCOEvaluator:
         if n == 0:
             return []
         ppi = [int(o["boxes_h"].shape[0]) for o in outputs]; cpi = [int(o["scores"].shape[0]) for o in outputs]
-        cat = lambda k: torch.cat([o[k].reshape(-1, *o[k].shape[1:]) for o in outputs]).to(dev).contiguous()
+        cat = lambda k: _cat_results(outputs, k, dev)
         boxes_h = cat("boxes_h").float().reshape(-1, 4); boxes_o = cat("boxes_o").float().reshape(-1, 4)
         index = cat("index").long(); pred = cat("prediction").long(); scores = cat("scores").float().contiguous()
         tg = [_vcoco_target(t, dev) for t in targets]
@@ -665,19 +671,15 @@ class DeviceVCOCOEvaluator:
         actions = torch.cat([a for _, a, _ in tg]).to(torch.int8).contiguous()
         role_boxes = torch.cat([r for _, _, r in tg]).contiguous()
         self.npos += (actions == 1).sum(0)
-        offs = np.zeros(3 * (n + 1), np.int32)                       # pair_off | cell_off | gt_off, n + 1 entries each
-        offs[1:n + 1] = np.cumsum(ppi); offs[n + 2:2 * n + 2] = np.cumsum(cpi); offs[2 * n + 3:] = np.cumsum(gts)
-        offs_d = torch.from_numpy(offs).to(dev)
+        offs_d, (pair_off, cell_off, gt_off) = _offset_table(dev, ppi, cpi, gts)
         L = int(sum(cpi))
         labels = torch.zeros(2, max(L, 1), dtype=torch.int8, device=dev)
-        pad = lambda t: t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
         boxes_h, boxes_o, index, pred, scores, persons, actions, role_boxes = map(
-            pad, (boxes_h, boxes_o, index, pred, scores, persons, actions, role_boxes))
+            _pad_row, (boxes_h, boxes_o, index, pred, scores, persons, actions, role_boxes))
         _capi.check(_capi.lib().skg_eval_vcoco_match_f32(
-            boxes_h.data_ptr(), boxes_o.data_ptr(), offs_d.data_ptr(), index.data_ptr(), pred.data_ptr(), scores.data_ptr(),
-            offs_d.data_ptr() + 4 * (n + 1), n, self.class_ar.data_ptr(), len(self.table), persons.data_ptr(),
-            actions.data_ptr(), role_boxes.data_ptr(), offs_d.data_ptr() + 8 * (n + 1), self.thr, labels[0].data_ptr(),
-            labels[1].data_ptr(), self.status.data_ptr(), _stream()), "skg_eval_vcoco_match_f32")
+            boxes_h.data_ptr(), boxes_o.data_ptr(), pair_off, index.data_ptr(), pred.data_ptr(), scores.data_ptr(), cell_off, n,
+            self.class_ar.data_ptr(), len(self.table), persons.data_ptr(), actions.data_ptr(), role_boxes.data_ptr(), gt_off,
+            self.thr, labels[0].data_ptr(), labels[1].data_ptr(), self.status.data_ptr(), _stream()), "skg_eval_vcoco_match_f32")
         self._scores.append(scores[:L]); self._pred.append(pred[:L]); self._labels.append(labels[:, :L])
         return list(labels[:, :L].t().split(cpi))
 
@@ -689,29 +691,16 @@ class DeviceVCOCOEvaluator:
             raise _capi.SkgError("an image has %d persons; skg_eval_vcoco_match_f32 keeps at most %d per image"
                                  % (int(self.status.item()), _capi.VCOCO_MAX_PERSONS))
         K = len(self.table)
-        npos = self.npos.cpu()
-        aid = torch.tensor([a for a, _ in self.table], dtype=torch.int64)
-        num_gt = self.npos[aid.to(dev)].contiguous()
-        aps = []
+        num_gt = self.npos[torch.tensor([a for a, _ in self.table], dtype=torch.int64, device=dev)].contiguous()
+        aps = [torch.zeros(K, dtype=torch.float64), torch.zeros(K, dtype=torch.float64)]
         if self._scores:
             scores = torch.cat(self._scores); pred = torch.cat(self._pred); labels = torch.cat(self._labels, dim=1)
             if ((pred < 0) | (pred >= K)).any():
                 raise IndexError("a prediction is outside the %d classes" % K)
-        for s in range(2):
-            ap = torch.zeros(K, dtype=torch.float64, device=dev)
-            if self._scores and K:
+            for s in range(2):
                 keep = labels[s] >= 0                                # dropped cells never reach the ranking
-                sc, cls, lab = scores[keep], pred[keep], labels[s][keep].float()
-                o1 = torch.sort(sc, descending=True, stable=True).indices       # score descending, arrival order on ties
-                o2 = torch.sort(cls[o1], stable=True).indices                   # ... then class ascending, order kept
-                lab_sorted = lab[o1[o2]].contiguous()
-                class_off = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-                class_off[1:] = torch.cumsum(torch.bincount(cls, minlength=K), 0)
-                _launch_ap("AUC", lab_sorted, class_off, num_gt, ap, None)
-            ap = ap.cpu()
-            ap[npos[aid] == 0] = float("nan")
-            aps.append(ap)
-        return _vcoco_summary(self.table, aps[0], aps[1], npos)
+                aps[s] = _class_aps_device("AUC", scores[keep], pred[keep], labels[s][keep], K, num_gt).cpu()
+        return _vcoco_summary(self.table, aps[0], aps[1], self.npos.cpu())
 
 
 # ----------------------------------------------------------------------------------------------- object detections
@@ -809,12 +798,11 @@ class DetectionEvaluator:
     batched = True                                               # trainer.test-style loops feed lists
 
     def __init__(self, num_classes=80, human_idx=49, min_iou=0.5, nms_thresh=0.5, algorithm="AUC", num_hoi=None):
-        if algorithm not in ("11P", "AUC"):
-            raise ValueError("unknown algorithm %s" % algorithm)
+        self.algorithm = _check_algorithm(algorithm)
         if not 0 <= int(human_idx) < int(num_classes):
             raise ValueError("human_idx %d is outside the %d classes" % (human_idx, num_classes))
         self.num_classes, self.human_idx = int(num_classes), int(human_idx)
-        self.min_iou, self.nms_thresh, self.algorithm = float(min_iou), float(nms_thresh), algorithm
+        self.min_iou, self.nms_thresh = float(min_iou), float(nms_thresh)
         self.num_hoi = None if num_hoi is None else int(num_hoi)
         self.num_gt = torch.zeros(self.num_classes, dtype=torch.int64)
         self._scores, self._cls, self._labels = [], [], []
@@ -880,36 +868,33 @@ class DetectionEvaluator:
         cls = torch.cat(self._cls) if self._cls else torch.zeros(0, dtype=torch.int64)
         lab = torch.cat(self._labels) if self._labels else torch.zeros(0, dtype=torch.int8)
         live = lab >= 0                                          # dropped detections never reach the ranking
-        sc, cls, lab = sc[live].double(), cls[live], lab[live].double()
-        ap = torch.zeros(C, dtype=torch.float64)
-        for c in cls.unique().tolist():
-            m = cls == c
-            ap[c] = DetectionAPMeter._ap(sc[m], lab[m], int(self.num_gt[c]), self.algorithm)
+        sc, cls, lab = sc[live], cls[live], lab[live].double()
+        meter = DetectionAPMeter(C, num_gt=self.num_gt, algorithm=self.algorithm)
+        meter.append(sc, cls, lab)
         tp = torch.zeros(C, dtype=torch.float64).index_add_(0, cls, lab)
-        return _det_summary(ap, self.num_gt.clone(), tp, self._pairs, self._covered, self._hoi_pairs, self._hoi_covered)
+        return _det_summary(meter.eval(), self.num_gt.clone(), tp, self._pairs, self._covered, self._hoi_pairs,
+                            self._hoi_covered)
 
 
 class DeviceDetectionEvaluator:
     """DetectionEvaluator on the device, for batches of any size: one skg_eval_det_match_f32 launch (ground-truth NMS,
     association, num_gt by integer atomics) and one skg_eval_pair_cover_u8 launch per `add`, no host synchronisation there;
-    scores, classes, labels and coverage flags stay on the device.  `summary()` drops the -1 cells, sorts twice (stable) and
-    launches the AP kernel of `algorithm`; max_rec comes from an index_add_ of the labels.  Same labels, flags and numbers as
+    scores, classes, labels and coverage flags stay on the device.  `summary()` drops the -1 cells and ranks the others with
+    _class_aps_device; max_rec comes from an index_add_ of the labels.  Same labels, flags and numbers as
     the host evaluator, same interface; the `last_*` lists are views of device tensors.  An image with more than
     SKG_EVAL_DET_MAX_GT ground-truth boxes (2 per pair) and a class outside [0, num_classes) are reported by `summary()`."""
     batched = True
 
     def __init__(self, num_classes=80, human_idx=49, min_iou=0.5, nms_thresh=0.5, algorithm="AUC", num_hoi=None, device="cuda"):
-        if algorithm not in ("11P", "AUC"):
-            raise ValueError("unknown algorithm %s" % algorithm)
+        self.algorithm = _check_algorithm(algorithm)
         if not 0 <= int(human_idx) < int(num_classes):
             raise ValueError("human_idx %d is outside the %d classes" % (human_idx, num_classes))
         self.num_classes, self.human_idx = int(num_classes), int(human_idx)
-        self.min_iou, self.nms_thresh, self.algorithm = float(min_iou), float(nms_thresh), algorithm
+        self.min_iou, self.nms_thresh = float(min_iou), float(nms_thresh)
         self.num_hoi = None if num_hoi is None else int(num_hoi)
         self.device = torch.device(device)
         self.num_gt = torch.zeros(self.num_classes, dtype=torch.int64, device=self.device)
         self.status = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.thr = torch.linspace(0, 1, 11, dtype=torch.float64).to(self.device)
         self._scores, self._cls, self._labels, self._covered, self._hoi = [], [], [], [], []
         self.last_gt_keep, self.last_matched, self.last_covered = [], [], []
 
@@ -934,25 +919,21 @@ class DeviceDetectionEvaluator:
         gts = [int(t[2].shape[0]) for t in tg]
         gt_h = torch.cat([t[0] for t in tg]).contiguous(); gt_o = torch.cat([t[1] for t in tg]).contiguous()
         gt_ob = torch.cat([t[2] for t in tg]).contiguous()
-        offs = np.zeros(2 * (n + 1), np.int32)                       # det_off | gt_off, n + 1 entries each
-        offs[1:n + 1] = np.cumsum(per); offs[n + 2:] = np.cumsum(gts)
-        offs_d = torch.from_numpy(offs).to(dev)
+        offs_d, (det_off, gt_off) = _offset_table(dev, per, gts)
         L, Ng = int(sum(per)), int(sum(gts))
         labels = torch.zeros(max(L, 1), dtype=torch.int8, device=dev)
         matched = torch.full((max(L, 1),), -1, dtype=torch.int32, device=dev)
         gt_keep = torch.zeros(max(2 * Ng, 1), dtype=torch.uint8, device=dev)
         covered = torch.zeros(max(Ng, 1), dtype=torch.uint8, device=dev)
-        pad = lambda t: t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-        boxes_p, scores_p, cls_p, gt_h, gt_o, gt_ob = map(pad, (boxes, scores, cls, gt_h, gt_o, gt_ob))
+        boxes_p, scores_p, cls_p, gt_h, gt_o, gt_ob = map(_pad_row, (boxes, scores, cls, gt_h, gt_o, gt_ob))
         _capi.check(_capi.lib().skg_eval_det_match_f32(
-            boxes_p.data_ptr(), scores_p.data_ptr(), cls_p.data_ptr(), offs_d.data_ptr(), n, gt_h.data_ptr(), gt_o.data_ptr(),
-            gt_ob.data_ptr(), offs_d.data_ptr() + 4 * (n + 1), self.human_idx, self.num_classes, self.min_iou, self.nms_thresh,
-            labels.data_ptr(), matched.data_ptr(), gt_keep.data_ptr(), self.num_gt.data_ptr(), self.status.data_ptr(),
-            _stream()), "skg_eval_det_match_f32")
+            boxes_p.data_ptr(), scores_p.data_ptr(), cls_p.data_ptr(), det_off, n, gt_h.data_ptr(), gt_o.data_ptr(),
+            gt_ob.data_ptr(), gt_off, self.human_idx, self.num_classes, self.min_iou, self.nms_thresh, labels.data_ptr(),
+            matched.data_ptr(), gt_keep.data_ptr(), self.num_gt.data_ptr(), self.status.data_ptr(), _stream()),
+            "skg_eval_det_match_f32")
         _capi.check(_capi.lib().skg_eval_pair_cover_u8(
-            boxes_p.data_ptr(), cls_p.data_ptr(), labels.data_ptr(), offs_d.data_ptr(), n, gt_h.data_ptr(), gt_o.data_ptr(),
-            gt_ob.data_ptr(), offs_d.data_ptr() + 4 * (n + 1), self.human_idx, self.min_iou, covered.data_ptr(), _stream()),
-            "skg_eval_pair_cover_u8")
+            boxes_p.data_ptr(), cls_p.data_ptr(), labels.data_ptr(), det_off, n, gt_h.data_ptr(), gt_o.data_ptr(),
+            gt_ob.data_ptr(), gt_off, self.human_idx, self.min_iou, covered.data_ptr(), _stream()), "skg_eval_pair_cover_u8")
         self._scores.append(scores); self._cls.append(cls); self._labels.append(labels[:L]); self._covered.append(covered[:Ng])
         if self.num_hoi is not None:                                 # -1: a pair of a target without `hoi`
             self._hoi.append(torch.cat([t[3] if t[3] is not None else torch.full_like(t[2], -1) for t in tg]))
@@ -976,15 +957,9 @@ class DeviceDetectionEvaluator:
             if outside or bool(((cls < 0) | (cls >= C)).any()):
                 raise IndexError("a detection or ground-truth class is outside [0, %d)" % C)
             live = labels >= 0                                       # dropped detections never reach the ranking
-            sc, cl, lab = scores[live], cls[live], labels[live].float()
-            if sc.numel():
-                o1 = torch.sort(sc, descending=True, stable=True).indices       # score descending, arrival order on ties
-                o2 = torch.sort(cl[o1], stable=True).indices                    # ... then class ascending, order kept
-                lab_sorted = lab[o1[o2]].contiguous()
-                class_off = torch.zeros(C + 1, dtype=torch.int64, device=dev)
-                class_off[1:] = torch.cumsum(torch.bincount(cl, minlength=C), 0)
-                _launch_ap(self.algorithm, lab_sorted, class_off, self.num_gt, ap, self.thr)
-                tp.index_add_(0, cl, lab.double())
+            cl, lab = cls[live], labels[live]
+            ap = _class_aps_device(self.algorithm, scores[live], cl, lab, C, self.num_gt)
+            tp.index_add_(0, cl, lab.double())
             cov = torch.cat(self._covered)
             pairs, covered = int(cov.numel()), int(cov.sum())
         hoi_pairs = hoi_covered = None

@@ -1513,13 +1513,12 @@ def test(net, test_loader, evaluator, device=None, lookahead=True):
     elements are the network's arguments -- for the bare interaction head (inference from cached features / detections):
     (features, detections, image_shapes, targets).  evaluator: evaluate.DeviceHOIEvaluator (results stay on the device) or
     evaluate.HOIEvaluator (the host restatement); for V-COCO evaluate.DeviceVCOCOEvaluator / VCOCOEvaluator with targets
-    {persons, actions, role_boxes} (AP_role, scenarios 1 and 2).  An evaluator whose `batched` attribute is true is fed
-    lists, `add(outputs, [target])`, like the device evaluator.
+    {persons, actions, role_boxes} (AP_role, scenarios 1 and 2).  An evaluator whose `batched` attribute is true (every one
+    of these but HOIEvaluator) is fed lists, `add(outputs, [target])`.
 
     lookahead: the loop runs one image ahead of the network -- image i + 1 is uploaded BEFORE forward i is enqueued and its
     detection selection, count read-back and TransH table draw run beside forward i on the head's side stream
     (InteractionHead.prefetch_eval), so forward i + 1 begins at its launch plan.  Same results, same RNG stream."""
-    from .evaluate import DeviceHOIEvaluator
     mod = net.module if isinstance(net, nn.parallel.DistributedDataParallel) else net
     if device is None:
         p = next(mod.parameters(), None)
@@ -1527,8 +1526,7 @@ def test(net, test_loader, evaluator, device=None, lookahead=True):
     device = torch.device(device)
     net.eval()
     ahead = getattr(mod, "prefetch_eval", None) if (lookahead and device.type == "cuda") else None
-    # fed lists: the device evaluator, or any evaluator that says so (evaluate.VCOCOEvaluator / DeviceVCOCOEvaluator)
-    batched = isinstance(evaluator, DeviceHOIEvaluator) or bool(getattr(evaluator, "batched", False))
+    batched = bool(getattr(evaluator, "batched", False))     # fed lists: every evaluator that says so
     it = iter(test_loader)
     cur = next(it, None)
     inputs = None if cur is None else relocate_to_device(cur[:-1], device)

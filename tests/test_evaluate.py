@@ -224,3 +224,35 @@ def test_training_meter_on_the_device_matches_the_host_meter(seed):
     h2 = ev.DetectionAPMeter(117, with_gt); h2.append(sc, cl, lb)
     d2 = ev.DeviceAPMeter(117, with_gt, device="cuda"); d2.append(sc.cuda(), cl.cuda(), lb.cuda())
     assert torch.equal(h2.eval(), d2.eval())
+
+
+@pytest.mark.gpu
+def test_shared_device_ranking_at_the_scan_tile_boundaries():
+    """_class_aps_device, the ranking of every device evaluator, against the host meter on the same triples.  Per-class
+    detection counts 0, 1, 255, 256, 257 and 513 sit around the 256-lane tiles of the AP kernels' scans; class 6 has
+    detections and no ground truth.  Two-decimal scores tie inside and across classes, the arrival order is shuffled.
+    '11P' is bit for bit (integer true-positive counts, one division per precision); 'AUC' within the project's 1e-12
+    (the kernel sums the area by tree, the host in order)."""
+    counts = [0, 1, 255, 256, 257, 513, 100]
+    rs = np.random.RandomState(7)
+    cl = np.repeat(np.arange(7), counts)
+    perm = rs.permutation(cl.size)
+    cl = torch.tensor(cl[perm])
+    sc = torch.tensor(np.round(rs.uniform(0, 1, cl.numel()), 2), dtype=torch.float32)
+    lb = torch.tensor((rs.uniform(0, 1, cl.numel()) < 0.3).astype(np.float32))
+    num_gt = [int(lb[cl == c].sum()) + 2 for c in range(7)]; num_gt[6] = 0
+    assert torch.bincount(cl, minlength=7).tolist() == counts and sc.unique().numel() < 102
+    ngt_d = torch.tensor(num_gt, dtype=torch.int64, device="cuda")
+    for algorithm in ("11P", "AUC"):
+        host = ev.DetectionAPMeter(7, num_gt, algorithm); host.append(sc, cl, lb)
+        want = host.eval()
+        got = ev._class_aps_device(algorithm, sc.cuda(), cl.cuda(), lb.cuda(), 7, ngt_d)
+        again = ev._class_aps_device(algorithm, sc.cuda(), cl.cuda(), lb.cuda(), 7, ngt_d)
+        assert got.dtype == torch.float64 and got.is_cuda and torch.equal(got, again)
+        if algorithm == "11P":
+            assert torch.equal(got.cpu(), want)
+        else:
+            assert float((got.cpu() - want).abs().max()) <= 1e-12
+        assert float(want[0]) == 0.0 and float(want[6]) == 0.0 and float(want[2:6].min()) > 0.0
+        empty = ev._class_aps_device(algorithm, sc[:0].cuda(), cl[:0].cuda(), lb[:0].cuda(), 7, ngt_d)
+        assert empty.dtype == torch.float64 and torch.equal(empty.cpu(), torch.zeros(7, dtype=torch.float64))

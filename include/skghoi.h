@@ -432,7 +432,8 @@ int skg_transpose_bf16(const void* in, int64_t ld_in, int rows, int cols, void* 
  * skg_gemm_f32 (both operands k-contiguous): dA = dZ (W^T)^T needs W^T, dW = dZ^T A needs dZ^T and A^T. */
 int skg_transpose_f32(const float* in, int64_t ld_in, int rows, int cols, float* out, int64_t ld_out, void* stream);
 
-/* out[r] = relu((P[pi[r]] + Q[qi[r]] + mbias) * F[fi[r]])  over `cols` columns (read-out MBF fc_1*fc_2, HEAD:970).  */
+/* out[r] = relu((P[pi[r]] + Q[qi[r]] + mbias) * F[fi[r]])  over `cols` columns (read-out MBF fc_1*fc_2, HEAD:970).
+ * relu here and in every GEMM epilogue is torch.relu: NaN stays NaN, +inf stays +inf, -inf and negatives give 0.   */
 int skg_rows_mul_relu_f32(const float* P, const int32_t* p_idx, int64_t ldp, const float* Q, const int32_t* q_idx,
                           int64_t ldq, const float* mbias, const float* F, const int32_t* f_idx, int64_t ldf,
                           int rows, int cols, float* out, int64_t ldo, void* stream);

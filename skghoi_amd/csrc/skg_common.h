@@ -28,6 +28,11 @@ __device__ __forceinline__ float skg_wave_max(float v) {
     return v;
 }
 
+// ReLU as torch.relu / clamp(min=0): NaN stays NaN (fmaxf(NaN, 0) is 0 and would hide it from everything downstream),
+// +inf stays +inf, -inf and negatives give 0.  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950, and no canonicalise
+// in front of it as fmaxf needs on a loaded value.  Every ReLU of the library goes through here.
+__device__ __forceinline__ float skg_relu(float x) { return __builtin_elementwise_maximum(x, 0.f); }
+
 // Block-wide sum for 256-thread blocks (4 waves); `red` is a 4-float LDS scratch.  All threads get the result.
 __device__ __forceinline__ float skg_block_sum256(float v, float* red) {
     v = skg_wave_sum(v);

@@ -1072,7 +1072,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
 #endif
                 float4 v = make_float4(a4.x + bia4.x, a4.y + bia4.y, a4.z + bia4.z, a4.w + bia4.w);
                 if (EPI == SKG_EPI_RELU_DOT) {
-                    v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+                    v = make_float4(skg_relu(v.x), skg_relu(v.y), skg_relu(v.z), skg_relu(v.w));
                     float sdot = (v.x * dw4.x + v.y * dw4.y) + (v.z * dw4.z + v.w * dw4.w);
                     if (st && d.C) *reinterpret_cast<float4*>(d.C + (int64_t)row * d.ldc + col) = v;
 #pragma unroll
@@ -1097,14 +1097,14 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                         m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
                     }
 #endif
-                    const float4 o = make_float4(fmaxf(v.x * m.x, 0.f), fmaxf(v.y * m.y, 0.f), fmaxf(v.z * m.z, 0.f), fmaxf(v.w * m.w, 0.f));
+                    const float4 o = make_float4(skg_relu(v.x * m.x), skg_relu(v.y * m.y), skg_relu(v.z * m.z), skg_relu(v.w * m.w));
                     if (st && (!C16 || d.C)) *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = o;
                     if constexpr (C16) { if (st && c16) skg_store_bf16x4(c16 + (int64_t)orow * ldc16 + col, o.x, o.y, o.z, o.w); }
                     continue;
                 }
                 if (orow < 0) continue;
                 if (EPI == SKG_EPI_BIAS_RELU || EPI == SKG_EPI_BIAS_RES_RELU)
-                    v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+                    v = make_float4(skg_relu(v.x), skg_relu(v.y), skg_relu(v.z), skg_relu(v.w));
 #ifndef SKG_EPI_KO_GATHER
                 if (EPI == SKG_EPI_BIAS_RES_RELU) {
                     const float4 t = *reinterpret_cast<const float4*>(d.res + (int64_t)row * d.ldres + col);
@@ -1159,7 +1159,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                 float s = 0.f;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    v[c] = fmaxf(v[c], 0.f);
+                    v[c] = skg_relu(v[c]);
                     if (rin && col + c < d.N) s += v[c] * d.dot_w[col + c];
                 }
                 if (d.C && rin) {
@@ -1190,7 +1190,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                     if (d.mbias) { const float4 t = *reinterpret_cast<const float4*>(d.mbias + col); m[0] = t.x; m[1] = t.y; m[2] = t.z; m[3] = t.w; }
                     if (d.P) { const float4 t = *reinterpret_cast<const float4*>(d.P + (int64_t)pi * d.ldp + col); m[0] += t.x; m[1] += t.y; m[2] += t.z; m[3] += t.w; }
                     if (d.Q) { const float4 t = *reinterpret_cast<const float4*>(d.Q + (int64_t)qi * d.ldq + col); m[0] += t.x; m[1] += t.y; m[2] += t.z; m[3] += t.w; }
-                    const float4 o = make_float4(fmaxf(v[0] * m[0], 0.f), fmaxf(v[1] * m[1], 0.f), fmaxf(v[2] * m[2], 0.f), fmaxf(v[3] * m[3], 0.f));
+                    const float4 o = make_float4(skg_relu(v[0] * m[0]), skg_relu(v[1] * m[1]), skg_relu(v[2] * m[2]), skg_relu(v[3] * m[3]));
                     if constexpr (C16) { v[0] = o.x; v[1] = o.y; v[2] = o.z; v[3] = o.w; }
                     else *reinterpret_cast<float4*>(d.C + (int64_t)orow * d.ldc + col) = o;
                 } else {
@@ -1200,7 +1200,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                         float mm = d.mbias ? d.mbias[col + c] : 0.f;
                         if (d.P) mm += d.P[(int64_t)pi * d.ldp + col + c];
                         if (d.Q) mm += d.Q[(int64_t)qi * d.ldq + col + c];
-                        const float o = fmaxf(v[c] * mm, 0.f);
+                        const float o = skg_relu(v[c] * mm);
                         if constexpr (C16) v[c] = o;
                         else d.C[(int64_t)orow * d.ldc + col + c] = o;
                     }
@@ -1212,7 +1212,7 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             if (orow < 0) continue;
             if (EPI == SKG_EPI_BIAS_RELU || EPI == SKG_EPI_BIAS_RES_RELU) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f);
+                for (int c = 0; c < 4; ++c) v[c] = skg_relu(v[c]);
             }
             if (EPI == SKG_EPI_BIAS_RES_RELU) {
                 if (full) {
@@ -1366,7 +1366,7 @@ __device__ __forceinline__ void skg_splitk_reduce_one(const skg_gemm_desc& d, in
     for (; s < d.split_k; ++s) v0 += d.split_ws[(int64_t)s * total + i];
     float v = (v0 + v1) + (v2 + v3);
     if (d.bias) v += d.bias[col];
-    if (d.epilogue == SKG_EPI_BIAS_RELU || d.epilogue == SKG_EPI_BIAS_RES_RELU) v = fmaxf(v, 0.f);
+    if (d.epilogue == SKG_EPI_BIAS_RELU || d.epilogue == SKG_EPI_BIAS_RES_RELU) v = skg_relu(v);
     if (d.epilogue == SKG_EPI_BIAS_RES_RELU) v += d.res[(int64_t)row * d.ldres + col];
     const int orow = d.out_rows ? d.out_rows[row] : row;
     if (orow < 0) return;

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void skg_gemm_bf16_kernel(const skg_gemm_bf
                 }
                 if (d.relu) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f);
+                    for (int c = 0; c < 4; ++c) v[c] = skg_relu(v[c]);
                 }
                 if (d.out_bf16) {
                     const uint32_t lo = (uint32_t)skg_f2bf(v[0]) | ((uint32_t)skg_f2bf(v[1]) << 16);
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void skg_gemm_bf16_kernel(const skg_gemm_bf
             for (int c = 0; c < 4; ++c) {
                 if (col + c >= d.N) continue;
                 float x = v[c] + (d.bias ? d.bias[col + c] : 0.f);
-                if (d.relu) x = fmaxf(x, 0.f);
+                if (d.relu) x = skg_relu(x);
                 if (d.out_bf16) reinterpret_cast<unsigned short*>(d.C)[(int64_t)row * d.ldc + col + c] = skg_f2bf(x);
                 else reinterpret_cast<float*>(d.C)[(int64_t)row * d.ldc + col + c] = x;
             }
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void skg_bf16_splitk_reduce_kernel(const skg_g
     float v = 0.f;
     for (int s = 0; s < d.split_k; ++s) v += d.split_ws[(int64_t)s * total + i];
     if (d.bias) v += d.bias[col];
-    if (d.relu) v = fmaxf(v, 0.f);
+    if (d.relu) v = skg_relu(v);
     if (d.out_bf16) reinterpret_cast<unsigned short*>(d.C)[(int64_t)row * d.ldc + col] = skg_f2bf(v);
     else reinterpret_cast<float*>(d.C)[(int64_t)row * d.ldc + col] = v;
 }

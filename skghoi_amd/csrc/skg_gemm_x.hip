@@ -239,12 +239,12 @@ __device__ __forceinline__ void xep_apply(const skg_gemmx_desc& d, const skg_gem
                 m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
             }
             *reinterpret_cast<float4*>(d.C + coff + (int64_t)orow * d.ldc) =
-                make_float4(fmaxf(v.x * m.x, 0.f), fmaxf(v.y * m.y, 0.f), fmaxf(v.z * m.z, 0.f), fmaxf(v.w * m.w, 0.f));
+                make_float4(skg_relu(v.x * m.x), skg_relu(v.y * m.y), skg_relu(v.z * m.z), skg_relu(v.w * m.w));
             return;
         }
         if (orow < 0) return;
         if (d.relu || f.kind == SKG_EPI_BIAS_RES_RELU) {
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            v.x = skg_relu(v.x); v.y = skg_relu(v.y); v.z = skg_relu(v.z); v.w = skg_relu(v.w);
         }
         if (f.kind == SKG_EPI_BIAS_RES_RELU) {
             const float4 t = xld4(f.res + (int64_t)row * f.ldres + col);
@@ -253,7 +253,7 @@ __device__ __forceinline__ void xep_apply(const skg_gemmx_desc& d, const skg_gem
         *reinterpret_cast<float4*>(d.C + coff + (int64_t)orow * d.ldc) = v;
         return;
     }
-    if (d.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (d.relu) { v.x = skg_relu(v.x); v.y = skg_relu(v.y); v.z = skg_relu(v.z); v.w = skg_relu(v.w); }
     float* p = d.C + coff + (int64_t)row * d.ldc;
     if (d.accumulate) { const float4 o = xld4(p); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
     if (d.mask) {                                      // accumulate first, mask last
@@ -360,7 +360,7 @@ __device__ __forceinline__ void xreduce_elem(const skg_gemmx_desc& d, int64_t MN
     float v = 0.f;
     for (int s = 0; s < d.split_k; ++s) v += d.split_ws[(int64_t)s * MN + i];
     if (d.bias) v += d.bias[col];
-    if (d.relu) v = fmaxf(v, 0.f);
+    if (d.relu) v = skg_relu(v);
     float* p = d.C + xoff(col, d.c_nshift, d.c_nstride, 1) + (int64_t)row * d.ldc;
     if (d.accumulate) v += *p;
     if (d.mask && !(d.mask[(int64_t)row * d.ldmask + col] > 0.f)) v = 0.f;      // accumulate first, mask last
@@ -635,7 +635,7 @@ __global__ __launch_bounds__(256, 2) void skg_gemmx_kernel(const skg_gemmx_group
                 }
                 const bool two = col + 1 < d.N;
                 if (d.bias) { v0 += d.bias[col]; if (two) v1 += d.bias[col + 1]; }
-                if (d.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
+                if (d.relu) { v0 = skg_relu(v0); v1 = skg_relu(v1); }
                 // accumulate first, mask last: a gradient that reaches a ReLU output from several consumers is summed
                 // and THEN cut by the ReLU (the mask belongs to the tensor C describes, not to this one contribution)
                 bool k0 = true, k1 = true;
@@ -1155,7 +1155,7 @@ __global__ __launch_bounds__(256, 2) void skg_gemmx_bf16_kernel(const skg_gemmx_
                     float v = acc[mi][ni][4 * gq + t];
                     if (split) { ws[(int64_t)row * d.N + col] = v; continue; }
                     if (d.bias) v += d.bias[col];
-                    if (d.relu) v = fmaxf(v, 0.f);
+                    if (d.relu) v = skg_relu(v);
                     float* p = d.C + xoff(col, d.c_nshift, d.c_nstride, 1) + (int64_t)row * d.ldc;
                     if (d.accumulate) v += *p;
                     if (d.mask && !(d.mask[(int64_t)row * d.ldmask + col] > 0.f)) v = 0.f;
@@ -1563,7 +1563,7 @@ __global__ __launch_bounds__(256, TNB == 2 ? 2 : 1) void skg_gemmx_t16_kernel(co
                     float v = acc[mi][ni][4 * gq + t];
                     if (split) { ws[(int64_t)row * d.N + col] = v; continue; }
                     if (d.bias) v += d.bias[col];
-                    if (d.relu) v = fmaxf(v, 0.f);
+                    if (d.relu) v = skg_relu(v);
                     float* p = d.C + xoff(col, d.c_nshift, d.c_nstride, 1) + (int64_t)row * d.ldc;
                     if (d.accumulate) v += *p;
                     if (d.mask && !(d.mask[(int64_t)row * d.ldmask + col] > 0.f)) v = 0.f;
@@ -1603,7 +1603,7 @@ __global__ __launch_bounds__(256) void skg_gemmx_reduce_kernel(const skg_gemmx_g
         }
         const int row = (int)(i / d.N), col = (int)(i % d.N);
         if (d.bias) { const float4 bv = xld4(d.bias + col); v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w; }
-        if (d.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (d.relu) { v.x = skg_relu(v.x); v.y = skg_relu(v.y); v.z = skg_relu(v.z); v.w = skg_relu(v.w); }
         float* p = d.C + xoff(col, d.c_nshift, d.c_nstride, 1) + (int64_t)row * d.ldc;
         if (d.accumulate) { const float4 o = xld4(p); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
         if (d.mask) {                                      // accumulate first, mask last

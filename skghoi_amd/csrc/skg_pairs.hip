@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void skg_rows_mul_relu_kernel(const float* __r
             m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
         }
         const float4 v = *reinterpret_cast<const float4*>(f + c);
-        const float4 res = make_float4(fmaxf(m.x * v.x, 0.f), fmaxf(m.y * v.y, 0.f), fmaxf(m.z * v.z, 0.f), fmaxf(m.w * v.w, 0.f));
+        const float4 res = make_float4(skg_relu(m.x * v.x), skg_relu(m.y * v.y), skg_relu(m.z * v.z), skg_relu(m.w * v.w));
         if (o) *reinterpret_cast<float4*>(o + c) = res;
         if (o16) skg_store_twin4(o16 + c, res);
     }
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void skg_rows_mul_relu_multi_kernel(const skg_
             m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
         }
         const float4 v = *reinterpret_cast<const float4*>(f + c);
-        const float4 res = make_float4(fmaxf(m.x * v.x, 0.f), fmaxf(m.y * v.y, 0.f), fmaxf(m.z * v.z, 0.f), fmaxf(m.w * v.w, 0.f));
+        const float4 res = make_float4(skg_relu(m.x * v.x), skg_relu(m.y * v.y), skg_relu(m.z * v.z), skg_relu(m.w * v.w));
         *reinterpret_cast<float4*>(o + c) = res;
         if (o16) skg_store_twin4(o16 + c, res);
     }

@@ -246,3 +246,98 @@ def test_bf16_loop_fast_and_slow_path(epi, tiles):
             dwa = o["dw"].double().abs()
             assert ((out["dot_partial"].double().sum(0) - want @ o["dw"].double()).abs() <= tol @ dwa + 1e-5 * (want.abs() @ dwa)).all()
     _same_bits(*outs)
+
+
+# ------------------------------------------------------------------------------------------------ ReLU and non-finite sums
+@functools.lru_cache(maxsize=None)
+def _poisoned(K):
+    """M = 96, N = 136 with rows 3, 10, 11, 50 of A holding NaN, +inf, -inf, NaN; W zero-padded to twin rows (ldw % 8 == 0)."""
+    M, N = 96, 136
+    o = dict(_operands(M, N, K))
+    A = o["A"].clone()
+    A[3, K - 1] = float("nan"); A[10, 0] = float("inf"); A[11, K // 2] = -float("inf"); A[50, 5] = float("nan")
+    Kp = (K + 7) // 8 * 8
+    W = torch.zeros(N, Kp, device="cuda"); W[:, :K] = o["W"]
+    bad = torch.zeros(M, dtype=torch.bool, device="cuda"); bad[[3, 10, 11, 50]] = True
+    o.update(A=A, W=W, Kp=Kp, bad=bad, v=A.double() @ o["W"].double().t() + o["b"].double())
+    return o
+
+
+# split-K exists for the plain epilogues only (the launcher answers E_ARG for the other two)
+RELU_CASES = [(epi, loop, launch) for epi in (E.EPI_BIAS_RELU, E.EPI_MUL_RELU, E.EPI_BIAS_RES_RELU, E.EPI_RELU_DOT)
+              for loop in ("exact", "bf16") for launch in ("tiles64", "tiles128", "split3")
+              if launch != "split3" or epi in (E.EPI_BIAS_RELU, E.EPI_BIAS_RES_RELU)]
+
+
+@pytest.mark.parametrize("epi,loop,launch", RELU_CASES)
+@pytest.mark.parametrize("K", [36, 1088])
+def test_relu_keeps_nan_and_inf_like_torch(K, epi, loop, launch):
+    """Every ReLU of the epilogues (fast and guarded path) and of the split-K reduce returns what torch.relu returns: NaN
+    where the fp64 product through torch.relu has NaN, nowhere else; the 92 clean rows meet the bars of the tests above.
+    RELU_DOT is checked on C and on the summed partials."""
+    M, N = 96, 136
+    o = _poisoned(K)
+    bad, v = o["bad"], o["v"]
+    bf = loop == "bf16"
+    kw, _, _, raw, _ = _problem(o, epi, "P+Q")
+    kw = dict(kw, ldw=o["Kp"])
+    m = _mul_kw(o, "P+Q")[1] if epi == E.EPI_MUL_RELU else None
+    if epi == E.EPI_MUL_RELU:
+        want = torch.relu(v * m)
+    elif epi == E.EPI_BIAS_RES_RELU:
+        want = torch.relu(v) + o["res"].double()
+    else:
+        want = torch.relu(v)
+    assert torch.isnan(want[3]).all() and torch.isnan(want[50]).all() and int(torch.isnan(want).sum()) == 2 * N
+    assert int(torch.isposinf(want[10]).sum()) > 20 and int(torch.isposinf(want[11]).sum()) > 20 and torch.isfinite(want[~bad]).all()
+    old = _capi.set_tuning(small_tiles=1) if launch == "tiles128" else None
+    outs = []
+    try:
+        with (engine.Bf16Weights() if bf else engine._NullCtx()):
+            slabs = engine.dot_partials(M, N, K, K, o["Kp"]) if epi == E.EPI_RELU_DOT else 0
+            for fast in (True, False):
+                out = _outputs(M, N, fast, raw, slabs)
+                if launch == "split3":
+                    out["ws"] = torch.full((3, M, N), 7.0, device="cuda")
+                    kw.update(split_k=3, split_ws=out["ws"])
+                gemm(o["A"], o["W"], o["b"], out["C"], M, N, K, epi, **_launch_kw(kw, out, N))
+                outs.append(out)
+        torch.cuda.synchronize()
+    finally:
+        if old is not None:
+            _capi.set_tuning(**old)
+    Ad, Wd = (o["A"][~bad].bfloat16().double(), o["W"][:, :K].bfloat16().double()) if bf else (o["A"][~bad].double(), o["W"][:, :K].double())
+    vc = Ad @ Wd.t() + o["b"].double()
+    S = Ad.abs() @ Wd.abs().t()
+    for out in outs:
+        assert torch.all(out["C"][:, :out["C_off"]] == 7.0)
+        Cv = out["C"][:, out["C_off"]:].double()
+        assert torch.equal(torch.isnan(Cv), torch.isnan(want)), "%d NaN got, %d wanted" % (int(torch.isnan(Cv).sum()), int(torch.isnan(want).sum()))
+        assert torch.equal(torch.isposinf(Cv), torch.isposinf(want)) and not torch.isneginf(Cv).any()
+        if epi != E.EPI_BIAS_RES_RELU:
+            assert torch.all(Cv[bad][torch.isfinite(want[bad])] == 0)        # what -inf leaves
+        if bf:                                                                # the bars of test_bf16_loop_fast_and_slow_path
+            tol = 1e-5 * S + 1e-6 * vc.abs()
+            if epi == E.EPI_MUL_RELU:
+                msum = o["P"][o["pi"].long()].double().abs() + o["Q"][o["qi"].long()].double().abs()
+                wc = torch.relu(vc * m[~bad])
+                tol = tol * m[~bad].abs() + 1e-6 * (wc.abs() + vc.abs() * msum[~bad])
+            elif epi == E.EPI_BIAS_RES_RELU:
+                wc = torch.relu(vc) + o["res"][~bad].double()
+                tol = tol + 1e-6 * wc.abs()
+            else:
+                wc = torch.relu(vc)
+            assert ((Cv[~bad] - wc).abs() <= tol).all()
+        else:
+            _close(Cv[~bad].float(), want[~bad].float(), 2e-5)
+        if slabs:
+            dot = out["dot_partial"].double().sum(0)
+            wdot = want @ o["dw"].double()
+            assert torch.equal(torch.isnan(dot), torch.isnan(wdot)) and bool(torch.isnan(wdot[bad]).all())
+            if bf:
+                dwa = o["dw"].double().abs()
+                assert ((dot[~bad] - wc @ o["dw"].double()).abs() <= (1e-5 * S + 1e-6 * vc.abs()) @ dwa + 1e-5 * (wc.abs() @ dwa)).all()
+            else:
+                _close(dot[~bad].float(), wdot[~bad].float(), 1e-4)
+    same = lambda a, b: torch.equal(torch.isnan(a), torch.isnan(b)) and bool(torch.all((a == b) | torch.isnan(a)))
+    assert same(outs[0]["C"][:, outs[0]["C_off"]:], outs[1]["C"][:, outs[1]["C_off"]:])      # fast and guarded path: same values

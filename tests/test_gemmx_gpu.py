@@ -86,6 +86,35 @@ def _twin(t):
     return t.to(torch.bfloat16)
 
 
+@pytest.mark.parametrize("kernel", ["f32", "bf16", "t16"])
+@pytest.mark.parametrize("split", [0, 3])
+def test_relu_keeps_nan_and_inf_like_torch(kernel, split):
+    """The ReLU of the forward layer returns what torch.relu returns -- NaN for NaN (also inf - inf and inf * 0), +inf for
+    +inf, 0 for -inf -- in the product's own epilogue and in both reductions of a split product, on every kernel.  Rows 3,
+    10, 11, 50 of A hold NaN, +inf, -inf, NaN; the 92 clean rows meet the file's bar."""
+    M, N, K = 96, 72, 40
+    bf = kernel != "f32"
+    x, W, b = _rnd(M, K, seed=81), _rnd(N, K, seed=82), _rnd(N, seed=83)
+    x[3, K - 1] = float("nan"); x[10, 0] = float("inf"); x[11, K // 2] = -float("inf"); x[50, 5] = float("nan")
+    W[7, 0] = 0.0                                                             # inf * 0 in row 10: NaN
+    out = torch.full((M, N), -7.0).cuda()
+    op = gemmx.forward(x, W, out, bias=b, relu=True)
+    op.split_k = split
+    if kernel == "t16":
+        op.A16, op.B16 = _twin(x), _twin(W)
+    gemmx.path_counts(reset=True)
+    gemmx.launch([op], bf16=bf)
+    assert gemmx.path_counts() == {"f32": (1, 0, 0), "bf16": (0, 1, 0), "t16": (0, 0, 1)}[kernel]
+    want = torch.relu(_q(x, bf) @ _q(W, bf).t() + b.double())
+    bad = torch.zeros(M, dtype=torch.bool).cuda(); bad[[3, 10, 11, 50]] = True
+    assert torch.isnan(want[3]).all() and torch.isnan(want[50]).all() and torch.isnan(want[10, 7]) and torch.isfinite(want[~bad]).all()
+    assert int(torch.isposinf(want[10]).sum()) > 10 and int((want[10] == 0).sum()) > 10 and int((want[11] == 0).sum()) > 10
+    assert torch.equal(torch.isnan(out), torch.isnan(want)), "%d NaN got, %d wanted" % (int(torch.isnan(out).sum()), int(torch.isnan(want).sum()))
+    assert torch.equal(torch.isposinf(out), torch.isposinf(want)) and not torch.isneginf(out).any()
+    assert torch.all(out[bad][torch.isfinite(want[bad])] == 0)
+    _close(out[~bad], want[~bad], "clean rows")
+
+
 @pytest.mark.parametrize("which", ["A", "B", "AB"])
 @pytest.mark.parametrize("kind,M,N,K", [("fwd", 300, 256, 128), ("fwd", 1, 1024, 256), ("fwd", 513, 72, 1032),
                                         ("dx", 300, 256, 128), ("dx", 130, 1024, 56), ("dw", 3200, 256, 128),

@@ -3,7 +3,8 @@
 
   FPN-like feature maps + detections -> producer (device NMS/top-k, MultiScaleRoIAlign, global pool) -> feature shard
   + per-image detection JSON on disk -> batched inference from the cache -> 600-way HOI scores -> 11-point mAP
-  against synthetic ground truth, in HICO-DET's Default and Known Object settings (full / rare / non-rare)
+  against synthetic ground truth, in HICO-DET's Default and Known Object settings (full / rare / non-rare; --errors: the
+  error breakdown of the Default setting, cells by category and ground-truth pairs by status)
   -> the producer's kept detections judged against the same ground truth (object-detection mAP, maximum recall, pair
   coverage) -> HICO-DET .mat cells / V-COCO-style pickle.
 
@@ -28,7 +29,7 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, batch=8, out_dir=None, seed=0):
+def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_cache_")
     o2v = synth.hico_object_to_verb()
@@ -77,12 +78,14 @@ def main(n_images=16, batch=8, out_dir=None, seed=0):
         targets.append(dict(boxes_h=out["boxes_h"][p:p + 1].cpu(), boxes_o=out["boxes_o"][p:p + 1].cpu(),
                             object=out["object"][p:p + 1].cpu(), hoi=torch.tensor([hoi])))
     num_anno_train = [5 if h % 4 == 0 else 50 for h in range(600)]      # synthetic training counts: every fourth class is rare
-    ev = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True)
+    ev = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True, errors=errors)
     for out, t in zip(outputs, targets):
         ev.add(out, t)
     summ = ev.summary()
     for name, s in (("Default", summ), ("Known Object", summ["known_object"])):
         print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
+    if errors:                                                   # where the Default mAP is lost: cells by category, pairs by status
+        print(evaluate.format_error_table(summ))
     # ---- the boxes behind those numbers: what the producer kept, judged against the same ground truth
     det_ev = evaluate.DeviceDetectionEvaluator(num_classes=80, human_idx=49, num_hoi=600, device=dev)
     det_ev.add(kept_all, targets)
@@ -104,5 +107,6 @@ if __name__ == "__main__":
     ap.add_argument("--images", type=int, default=16)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--errors", action="store_true", help="print the error breakdown of the Default setting")
     a = ap.parse_args()
-    main(a.images, a.batch, a.out)
+    main(a.images, a.batch, a.out, errors=a.errors)

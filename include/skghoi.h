@@ -739,6 +739,40 @@ int skg_eval_ap11_f64(const float* labels_sorted, const int64_t* class_off, cons
 int skg_eval_known_object_u8(const int32_t* hoi, const int32_t* cell_off, int n_images, const int32_t* hoi_object,
                              int n_hoi, int n_obj, const int64_t* gt_hoi, const int32_t* gt_off, uint8_t* keep,
                              void* stream);
+/* Error breakdown of the Default setting: where the mAP is lost inside the head.  NOT part of the reference and of no
+ * published protocol: this project's own definition, in the spirit of TIDE-style detection diagnostics -- parity unpinned,
+ * there is nothing to be on a par with.  Launched behind skg_eval_associate_f32 on the same stream, on that launch's hoi_out
+ * (`hoi`) and final `labels`; boxes_h / boxes_o / index / cell_off / gt_* as there, pair_off with n_images + 1 entries.
+ *
+ * Per image: cells c of class h_c = hoi[c] on output pair p = index[c]; ground-truth pairs g of class t_g = gt_hoi[g];
+ * ih(g, p) = IoU(gt_h[g], boxes_h[p]), io(g, p) = IoU(gt_o[g], boxes_o[p]), the association's plain fp32 arithmetic; a
+ * comparison with NaN is false; thr = min_iou.  g is VALID iff 0 <= t_g < n_hoi; an invalid pair takes no part and gets
+ * status 255.  hoi_object [n_hoi] as for skg_eval_known_object_u8.
+ * category[c], the first rule that applies:
+ *   0 tp         labels[c] == 1 (the Default association's true positive)
+ *   1 duplicate  some valid g with t_g == h_c has ih >= thr and io >= thr (matched a pair of its class, lost the bid)
+ *   2 verb       some valid g with t_g != h_c, hoi_object[t_g] >= 0 and hoi_object[t_g] == hoi_object[h_c] has ih >= thr and
+ *                io >= thr (a real interacting pair with this object category, wrong interaction)
+ *   3 object     some valid g with t_g == h_c has ih >= thr (right human for the class, object box wrong)
+ *   4 human      some valid g with t_g == h_c has io >= thr
+ *   5 background none of the above; every cell of an image without ground truth
+ *   255          h_c outside [0, n_hoi)
+ * gt_status[g]:
+ *   0 hit        g is the match of a cell with labels == 1; the match is the association's own: the first maximum of
+ *                min(ih, io) over the valid pairs of the cell's class, strict >
+ *   1 shadowed   not hit, but some cell of class t_g has ih >= thr and io >= thr with g (its match went to another pair)
+ *   2 unscored   neither, but some output PAIR p of the image has ih(g, p) >= thr and io(g, p) >= thr: the head paired the
+ *                boxes and never scored this class on them (another object label, a zero prior)
+ *   3 unpaired   no output pair covers g
+ * Per class the tp cells are as many as the hit pairs; categories 0 .. 5 partition the cells with a class, statuses 0 .. 3 the
+ * valid pairs.  An image with more than 2048 ground-truth pairs (the association's cap, reported through its status) gets 255
+ * in every category and status of the image.
+ * Errors, before any device call: SKG_E_ARG for n_images < 0 or n_hoi <= 0; n_images == 0 returns 0 and launches nothing;
+ * SKG_E_ARG for a null pointer; SKG_E_ALIGN for boxes_h / boxes_o / gt_h / gt_o not 16-byte aligned.                      */
+int skg_eval_hoi_errors_u8(const float* boxes_h, const float* boxes_o, const int32_t* pair_off, const int64_t* index,
+                           const int32_t* hoi, const float* labels, const int32_t* cell_off, int n_images,
+                           const int32_t* hoi_object, int n_hoi, const float* gt_h, const float* gt_o, const int64_t* gt_hoi,
+                           const int32_t* gt_off, float min_iou, uint8_t* category, uint8_t* gt_status, void* stream);
 
 /* V-COCO role detection, scenarios 1 and 2 at once (the matching rule of the published V-COCO toolkit's role evaluation,
  * `_do_role_eval` of vsrl_eval.VCOCOeval, which vcoco_evaluation.py:3-10 imports from outside the reference; restated,

@@ -260,6 +260,8 @@ PROTOTYPES = {
                                          _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
     "skg_eval_ap11_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "skg_eval_known_object_u8": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "skg_eval_hoi_errors_u8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _f32,
+                                         _vp, _vp, _vp]),
     "skg_eval_vcoco_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
                                            _f32, _vp, _vp, _vp, _vp]),
     "skg_eval_ap_voc_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),

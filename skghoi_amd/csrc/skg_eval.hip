@@ -17,6 +17,9 @@
 //                            the precision, float64 like pocket.
 //   skg_eval_known_object_u8 : HICO-DET's Known Object setting, launched behind the association: one workgroup per image,
 //                            the object categories of its ground truth as an LDS bit mask, one keep flag per cell.
+//   skg_eval_hoi_errors_u8 : the error breakdown of the Default setting (this project's own definition), launched behind the
+//                            association: one workgroup per image, one flag word per ground-truth pair in LDS, one category
+//                            per cell and one status per ground-truth pair.
 //
 // V-COCO (role AP, scenarios 1 and 2; the published toolkit's `_do_role_eval`, restated in include/skghoi.h -- the toolkit is
 // outside the reference tree, parity unpinned at that boundary):
@@ -176,6 +179,113 @@ extern "C" int skg_eval_known_object_u8(const int32_t* hoi, const int32_t* cell_
     if (!hoi || !cell_off || !hoi_object || !gt_hoi || !gt_off || !keep) return SKG_E_ARG;
     hipLaunchKernelGGL(skg_eval_known_object_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, hoi, cell_off,
                        hoi_object, n_hoi, n_obj, gt_hoi, gt_off, keep);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ error breakdown
+// Where the Default mAP is lost inside the head: one category per cell (tp, duplicate, verb, object, human, background) and
+// one status per ground-truth pair (hit, shadowed, unscored, unpaired).  Not part of the reference: this project's own
+// definition in the spirit of TIDE-style detection diagnostics, the rule is stated in include/skghoi.h -- parity unpinned,
+// there is nothing to be on a par with.  Launched behind the association on its hoi_out and final labels.  One workgroup
+// per image: one flag word per ground-truth pair in LDS (EV_MAX_GT x 4 bytes = 8 KB; bit 0 = the match of a true positive,
+// bit 1 = covered by a cell of its class).  Lanes stride over the cells, one pass over the ground truth each collecting the
+// five predicates (a true positive repeats the association's arg-max and flags its match); after a barrier lanes stride
+// over the ground-truth pairs and, for the ones no cell of their class covered, walk the image's output pairs.  Every
+// barrier is reached by all lanes (the early return of an image above the cap is uniform), every output byte is written once.
+#define EV_ERR_HIT 1u
+#define EV_ERR_SCORED 2u
+
+__global__ __launch_bounds__(256) void skg_eval_hoi_errors_kernel(
+    const float* __restrict__ boxes_h, const float* __restrict__ boxes_o, const int32_t* __restrict__ pair_off,
+    const int64_t* __restrict__ index, const int32_t* __restrict__ hoi, const float* __restrict__ labels,
+    const int32_t* __restrict__ cell_off, const int32_t* __restrict__ hoi_object, int n_hoi, const float* __restrict__ gt_h,
+    const float* __restrict__ gt_o, const int64_t* __restrict__ gt_hoi, const int32_t* __restrict__ gt_off, float min_iou,
+    uint8_t* __restrict__ category, uint8_t* __restrict__ gt_status) {
+    __shared__ unsigned sflag[EV_MAX_GT];
+    const int a = blockIdx.x, tid = threadIdx.x;
+    const int c0 = cell_off[a], c1 = cell_off[a + 1];
+    const int g0 = gt_off[a], ng = gt_off[a + 1] - g0;
+    if (ng > EV_MAX_GT) {                                    // uniform: the association refused the image, summary() raises
+        for (int c = c0 + tid; c < c1; c += 256) category[c] = (uint8_t)255;
+        for (int g = tid; g < ng; g += 256) gt_status[g0 + g] = (uint8_t)255;
+        return;
+    }
+    for (int g = tid; g < ng; g += 256) sflag[g] = 0u;
+    __syncthreads();
+    const int p0 = pair_off[a], p1 = pair_off[a + 1];
+    for (int c = c0 + tid; c < c1; c += 256) {
+        const int h = hoi[c];
+        if (h < 0 || h >= n_hoi) { category[c] = (uint8_t)255; continue; }
+        const int oc = hoi_object[h];
+        const int64_t p = (int64_t)p0 + index[c];
+        const float4 dh = *reinterpret_cast<const float4*>(boxes_h + 4 * p);
+        const float4 dob = *reinterpret_cast<const float4*>(boxes_o + 4 * p);
+        bool dup = false, verb = false, obj = false, hum = false;
+        float best = -1.f;
+        int match = -1;
+        for (int g = 0; g < ng; ++g) {
+            const int64_t t = gt_hoi[g0 + g];
+            if (t < 0 || t >= n_hoi) continue;               // invalid pairs take no part
+            const bool same = t == (int64_t)h;
+            if (!same) {
+                const int ot = hoi_object[t];
+                if (ot < 0 || ot != oc) continue;            // another object category: no predicate reads this pair
+            }
+            const float ih = ev_iou(*reinterpret_cast<const float4*>(gt_h + 4 * (int64_t)(g0 + g)), dh);
+            const float io = ev_iou(*reinterpret_cast<const float4*>(gt_o + 4 * (int64_t)(g0 + g)), dob);
+            const bool ch = ih >= min_iou, co = io >= min_iou;       // NaN: false
+            if (same) {
+                if (ch && co) { dup = true; atomicOr(&sflag[g], EV_ERR_SCORED); }
+                obj |= ch; hum |= co;
+                const float v = fminf(ih, io);
+                if (v > best) { best = v; match = g; }       // the association's arg-max: first maximum, NaN never wins
+            } else if (ch && co) {
+                verb = true;
+            }
+        }
+        if (labels[c] == 1.f) {
+            if (match >= 0) atomicOr(&sflag[match], EV_ERR_HIT);
+            category[c] = (uint8_t)0;
+        } else {
+            category[c] = (uint8_t)(dup ? 1 : verb ? 2 : obj ? 3 : hum ? 4 : 5);
+        }
+    }
+    __syncthreads();
+    for (int g = tid; g < ng; g += 256) {
+        const int64_t t = gt_hoi[g0 + g];
+        if (t < 0 || t >= n_hoi) { gt_status[g0 + g] = (uint8_t)255; continue; }
+        const unsigned f = sflag[g];
+        int st = (f & EV_ERR_HIT) ? 0 : (f & EV_ERR_SCORED) ? 1 : 3;
+        if (st == 3) {
+            const float4 gh = *reinterpret_cast<const float4*>(gt_h + 4 * (int64_t)(g0 + g));
+            const float4 go = *reinterpret_cast<const float4*>(gt_o + 4 * (int64_t)(g0 + g));
+            for (int p = p0; p < p1; ++p) {
+                if (ev_iou(gh, *reinterpret_cast<const float4*>(boxes_h + 4 * (int64_t)p)) >= min_iou &&
+                    ev_iou(go, *reinterpret_cast<const float4*>(boxes_o + 4 * (int64_t)p)) >= min_iou) {
+                    st = 2;
+                    break;
+                }
+            }
+        }
+        gt_status[g0 + g] = (uint8_t)st;
+    }
+}
+
+extern "C" int skg_eval_hoi_errors_u8(const float* boxes_h, const float* boxes_o, const int32_t* pair_off, const int64_t* index,
+                                      const int32_t* hoi, const float* labels, const int32_t* cell_off, int n_images,
+                                      const int32_t* hoi_object, int n_hoi, const float* gt_h, const float* gt_o,
+                                      const int64_t* gt_hoi, const int32_t* gt_off, float min_iou, uint8_t* category,
+                                      uint8_t* gt_status, void* stream) {
+    if (n_images < 0 || n_hoi <= 0) return SKG_E_ARG;
+    if (n_images == 0) return 0;
+    if (!boxes_h || !boxes_o || !pair_off || !index || !hoi || !labels || !cell_off || !hoi_object || !gt_h || !gt_o ||
+        !gt_hoi || !gt_off || !category || !gt_status)
+        return SKG_E_ARG;
+    if (!skg_aligned16(boxes_h) || !skg_aligned16(boxes_o) || !skg_aligned16(gt_h) || !skg_aligned16(gt_o))
+        return SKG_E_ALIGN;
+    hipLaunchKernelGGL(skg_eval_hoi_errors_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, boxes_h, boxes_o,
+                       pair_off, index, hoi, labels, cell_off, hoi_object, n_hoi, gt_h, gt_o, gt_hoi, gt_off, min_iou,
+                       category, gt_status);
     return skg_launch_status();
 }
 

@@ -9,6 +9,8 @@ DetectionAPMeter) is a third-party package absent from the image and unpinned by
 semantics are restated here -- parity is unpinned at that boundary (oracle: oracle/eval_oracle.py, plain loops).
 HICO-DET's Known Object setting (the second half of the published table; Chao et al., WACV 2018) is computed in-process by
 the same two evaluators (`known_object=True`), the rule of the official evaluation restated under the same terms.
+The same two evaluators break the Default setting's errors down (`errors=True`: a category per cell, a status per ground-truth
+pair, AP without each category) -- this project's own definition in the spirit of TIDE, not the reference's.
 V-COCO's AP_role (scenario 1 and 2) is computed in-process by VCOCOEvaluator / DeviceVCOCOEvaluator, the rule of the
 external toolkit restated under the same terms.
 The detections behind the head (hicodet/detections/eval_detections.py: object-detection mAP and mean maximum recall over the
@@ -252,7 +254,57 @@ class DeviceAPMeter:
 # every interaction class over all test images, what utils.test computes -- and Known Object -- a class only over the images
 # that contain its object category.  The official evaluation code (MATLAB, fed by the .mat exporter below) is outside the
 # reference tree: the published rule is restated (include/skghoi.h, skg_eval_known_object_u8), parity unpinned at that boundary.
-_SUMMARY_KEYS = ("ap", "full", "rare", "non_rare", "known_object")
+_SUMMARY_KEYS = ("ap", "full", "rare", "non_rare", "known_object", "errors")
+
+# Error breakdown of the Default setting (`errors=True`): where the mAP is lost inside the head.  Not part of the reference and
+# of no published protocol -- this project's own definition in the spirit of TIDE-style detection diagnostics (parity unpinned:
+# there is nothing to be on a par with); the rule is stated in include/skghoi.h (skg_eval_hoi_errors_u8).  Per image, with
+# ih / io the IoU of a ground-truth pair's human / object box with an output pair's, thr = min_iou, a comparison with NaN
+# false, and a ground-truth pair valid iff its class is in [0, num_cls) (an invalid one takes no part: status 255):
+#   cell category, the first rule that applies -- 0 tp: the Default label is 1; 1 duplicate: a valid pair of the cell's class
+#   has ih >= thr and io >= thr (matched, lost the bid); 2 verb: a valid pair of ANOTHER class of the same object category
+#   (hoi_object equal and >= 0) has both; 3 object: a valid pair of the cell's class has ih >= thr; 4 human: ... io >= thr;
+#   5 background: none (every cell of an image without ground truth); 255: a cell without a class.
+#   ground-truth status -- 0 hit: the match (first maximum of min(ih, io) over the valid pairs of the class, strict >) of a
+#   cell with label 1; 1 shadowed: not hit, a cell of its class covers it (ih and io >= thr); 2 unscored: neither, but an output
+#   PAIR of the image covers it (paired, never scored for this class); 3 unpaired: no output pair covers it.
+# Per class the tp cells are as many as the hit pairs; 0 .. 5 partition the cells, 0 .. 3 the valid pairs.
+ERROR_CATEGORIES = ("tp", "duplicate", "verb", "object", "human", "background")
+ERROR_GT_STATUSES = ("hit", "shadowed", "unscored", "unpaired")
+_AP_WITHOUT = ERROR_CATEGORIES[1:] + ("all_fp",)
+
+
+def _without_mask(name, category):
+    """The cells that stay when the false positives of one category (`all_fp`: of every category) are taken out."""
+    return category == 0 if name == "all_fp" else category != ERROR_CATEGORIES.index(name)
+
+
+def _errors_summary(cells, gt, ap_without, full):
+    """summary()["errors"] of both HOI evaluators from host tensors: cells [num_cls, 6] / gt [num_cls, 4] int64 counts and
+    {name: float64 [num_cls]} APs over the cells that are not of that category."""
+    map_without = {k: float(v.mean()) for k, v in ap_without.items()}
+    return dict(categories=ERROR_CATEGORIES, gt_statuses=ERROR_GT_STATUSES, cells=cells, cells_total=cells.sum(0), gt=gt,
+                gt_total=gt.sum(0), ap_without=ap_without, map_without=map_without,
+                delta_map={k: v - full for k, v in map_without.items()})
+
+
+def format_error_table(summary):
+    """The `errors` entry of an HOI evaluator's summary() as text: cells per category with the mAP gained by taking the
+    category's false positives out (delta mAP), and ground-truth pairs per status."""
+    e = summary["errors"]
+    n_cells = max(int(e["cells_total"].sum()), 1); n_gt = max(int(e["gt_total"].sum()), 1)
+    lines = ["cells by category (Default setting, mAP %.4f)" % summary["full"],
+             "  %-12s %10s %8s %10s" % ("category", "cells", "share", "delta mAP")]
+    for i, name in enumerate(e["categories"]):
+        n = int(e["cells_total"][i])
+        delta = "%+10.4f" % e["delta_map"][name] if name in e["delta_map"] else "%10s" % "-"
+        lines.append("  %-12s %10d %7.1f%% %s" % (name, n, 100.0 * n / n_cells, delta))
+    lines.append("  %-12s %10s %8s %+10.4f" % ("all_fp", "", "", e["delta_map"]["all_fp"]))
+    lines += ["ground-truth pairs by status", "  %-12s %10s %8s" % ("status", "pairs", "share")]
+    for i, name in enumerate(e["gt_statuses"]):
+        n = int(e["gt_total"][i])
+        lines.append("  %-12s %10d %7.1f%%" % (name, n, 100.0 * n / n_gt))
+    return "\n".join(lines)
 
 
 def hoi_object_of(object_n_verb_to_interaction):
@@ -302,10 +354,18 @@ class HOIEvaluator:
     splits={name: class indices}: `summary()` also holds the mean AP over each named list.  known_object=True: `add` also
     flags the cells the Known Object setting keeps (`last_keep`: [bool tensor] of the most recent call, in the shape of its
     labels) and `summary()["known_object"]` holds that setting's `ap`, `full`, `rare` / `non_rare` and named splits -- the
-    same AP, num_gt, labels and order over the kept cells only."""
+    same AP, num_gt, labels and order over the kept cells only.
+
+    errors=True: the error breakdown of the Default setting (this project's own definition, not the reference's; the rule is
+    stated above ERROR_CATEGORIES and in include/skghoi.h).  `add` also gives every cell a category and every ground-truth pair
+    a status (`last_category` / `last_gt_status`: [uint8 tensor] of the most recent call) and `summary()["errors"]` holds
+    `categories` / `gt_statuses` (the names), `cells` [num_cls, 6] / `cells_total`, `gt` [num_cls, 4] / `gt_total` (int64
+    counts), `ap_without` {duplicate, verb, object, human, background, all_fp: float64 [num_cls]} -- the same AP, num_gt,
+    labels and order over the cells that are not of that category -- `map_without` (their means) and `delta_map` =
+    map_without - full.  It composes with known_object / splits and leaves their output as it is."""
 
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, algorithm="11P",
-                 known_object=False, splits=None):
+                 known_object=False, splits=None, errors=False):
         self.lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
             else hico_object_n_verb_to_interaction()
         num_cls = int(self.lut.max()) + 1
@@ -314,10 +374,48 @@ class HOIEvaluator:
         self.num_anno_train = None if num_anno_train is None else torch.as_tensor(num_anno_train)
         self.splits = _check_splits(splits, num_cls)
         self.known_object = bool(known_object)
-        if self.known_object:
+        self.errors = bool(errors)
+        if self.known_object or self.errors:
             self.hoi_object = hoi_object_of(self.lut)
+        if self.known_object:
             self.ko_meter = DetectionAPMeter(num_cls, num_gt=num_gt_test, algorithm=algorithm)
             self.last_keep = []
+        if self.errors:
+            self._err_cells, self._err_gt = [], []               # (scores, classes, labels, category), (classes, status)
+            self.last_category, self.last_gt_status = [], []
+
+    def _errors_of(self, output, target, inter, labels):
+        """Category of every cell and status of every ground-truth pair of one image (the rule above ERROR_CATEGORIES)."""
+        dev = labels.device
+        idx = output["index"]
+        pair_h = output["boxes_h"].to(dev).float().reshape(-1, 4); pair_o = output["boxes_o"].to(dev).float().reshape(-1, 4)
+        gt_h = target["boxes_h"].to(dev).float().reshape(-1, 4); gt_o = target["boxes_o"].to(dev).float().reshape(-1, 4)
+        t = target["hoi"].to(dev).reshape(-1).long()
+        G, n = t.shape[0], inter.shape[0]
+        ho = self.hoi_object.to(dev)
+        valid = (t >= 0) & (t < ho.shape[0])
+        status = torch.full((G,), 255, dtype=torch.uint8, device=dev)
+        if G == 0:
+            return torch.where(labels == 1, 0, 5).to(torch.uint8), status
+        thr = torch.tensor(self.min_iou, dtype=torch.float32, device=dev)
+        ih = box_iou(gt_h, pair_h[idx].reshape(-1, 4)); io = box_iou(gt_o, pair_o[idx].reshape(-1, 4))      # [G, n]
+        ch, co = ih >= thr, io >= thr
+        same = valid[:, None] & (t[:, None] == inter[None])
+        obj_g = torch.where(valid, ho[t.clamp(0, ho.shape[0] - 1)], torch.full_like(t, -1))
+        other = valid[:, None] & (t[:, None] != inter[None]) & (obj_g[:, None] >= 0) & (obj_g[:, None] == ho[inter][None])
+        cover = same & ch & co
+        cat = torch.full((n,), 5, dtype=torch.uint8, device=dev)
+        for k, m in ((4, same & co), (3, same & ch), (2, other & ch & co), (1, cover)):      # later = higher priority
+            cat[m.any(0)] = k
+        cat[labels == 1] = 0
+        hit = torch.zeros(G, dtype=torch.bool, device=dev)
+        v = torch.min(ih, io)
+        for c in torch.nonzero(labels == 1).squeeze(1).tolist():
+            gs = torch.nonzero(same[:, c]).squeeze(1)
+            hit[gs[torch.nonzero(v[gs, c] == v[gs, c].max())[0, 0]]] = True      # first maximum
+        paired = ((box_iou(gt_h, pair_h) >= thr) & (box_iou(gt_o, pair_o) >= thr)).any(1)
+        st = torch.where(hit, 0, torch.where(cover.any(1), 1, torch.where(paired, 2, 3))).to(torch.uint8)
+        return cat, torch.where(valid, st, status)
 
     def _keep_of(self, inter, t_hoi):
         """The Known Object flags of one image's cells: the image's ground truth holds the object category of the cell's class."""
@@ -355,12 +453,36 @@ class HOIEvaluator:
             keep = self._keep_of(inter, t_hoi)
             self.ko_meter.append(scores[keep], inter[keep], labels[keep])
             self.last_keep = [keep]
+        if self.errors:
+            cat, status = self._errors_of(output, target, inter, labels)
+            self._err_cells.append((scores.reshape(-1), inter.reshape(-1), labels.reshape(-1), cat))
+            self._err_gt.append((t_hoi.reshape(-1).long(), status))
+            self.last_category, self.last_gt_status = [cat], [status]
         return labels
+
+    def _errors_block(self, full):
+        num_cls = self.meter.num_cls
+        cat_of = lambda parts, k, dtype: torch.cat([p[k].cpu() for p in parts]) if parts else torch.zeros(0, dtype=dtype)
+        scores = cat_of(self._err_cells, 0, torch.float32); inter = cat_of(self._err_cells, 1, torch.int64)
+        labels = cat_of(self._err_cells, 2, torch.float32); cat = cat_of(self._err_cells, 3, torch.uint8).long()
+        t = cat_of(self._err_gt, 0, torch.int64); status = cat_of(self._err_gt, 1, torch.uint8).long()
+        cells = torch.bincount(inter * 6 + cat, minlength=num_cls * 6).reshape(num_cls, 6)
+        ok = status != 255
+        gt = torch.bincount(t[ok] * 4 + status[ok], minlength=num_cls * 4).reshape(num_cls, 4)
+        ap_without = {}
+        for name in _AP_WITHOUT:
+            m = _without_mask(name, cat)
+            meter = DetectionAPMeter(num_cls, num_gt=self.meter.num_gt, algorithm=self.meter.algorithm)
+            meter.append(scores[m], inter[m], labels[m])
+            ap_without[name] = meter.eval()
+        return _errors_summary(cells, gt, ap_without, full)
 
     def summary(self):
         out = _hoi_summary(self.meter.eval(), self.num_anno_train, self.splits)
         if self.known_object:
             out["known_object"] = _hoi_summary(self.ko_meter.eval(), self.num_anno_train, self.splits)
+        if self.errors:
+            out["errors"] = self._errors_block(out["full"])
         return out
 
 
@@ -372,11 +494,14 @@ class DeviceHOIEvaluator:
     algorithm="AUC": the VOC all-point area instead (skg_eval_ap_voc_f64; the host meter's 'AUC' branch).
     splits / known_object: as for HOIEvaluator.  known_object=True adds one skg_eval_known_object_u8 launch per `add`, behind
     the association and without a host synchronisation (`last_keep`: per-image uint8 views of one device tensor), and at the
-    end the same ranking a second time, over the kept cells."""
+    end the same ranking a second time, over the kept cells.  errors=True (as for HOIEvaluator) adds one
+    skg_eval_hoi_errors_u8 launch per `add`, behind the association on its hoi_out and final labels and without a host
+    synchronisation (`last_category` / `last_gt_status`: per-image uint8 views of two device tensors), and at the end the same
+    ranking six more times, each over the cells that are not of one category."""
     batched = True                                               # trainer.test feeds lists
 
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, device="cuda",
-                 algorithm="11P", known_object=False, splits=None):
+                 algorithm="11P", known_object=False, splits=None, errors=False):
         from . import _capi
         self.algorithm = _check_algorithm(algorithm)             # "AUC": the 600 APs by skg_eval_ap_voc_f64
         self.device = torch.device(device)
@@ -392,12 +517,17 @@ class DeviceHOIEvaluator:
         self._scores, self._hoi, self._labels = [], [], []
         self.splits = _check_splits(splits, self.num_cls)
         self.known_object = bool(known_object)
-        if self.known_object:
-            if self.n_obj > _capi.EVAL_MAX_OBJECTS:
-                raise ValueError("%d object categories; skg_eval_known_object_u8 takes at most %d"
-                                 % (self.n_obj, _capi.EVAL_MAX_OBJECTS))
+        self.errors = bool(errors)
+        if self.known_object and self.n_obj > _capi.EVAL_MAX_OBJECTS:
+            raise ValueError("%d object categories; skg_eval_known_object_u8 takes at most %d"
+                             % (self.n_obj, _capi.EVAL_MAX_OBJECTS))
+        if self.known_object or self.errors:
             self.hoi_object = hoi_object_of(lut).to(self.device, torch.int32).contiguous()
+        if self.known_object:
             self._keep, self.last_keep = [], []
+        if self.errors:
+            self._cat, self._gt_hoi, self._gt_status = [], [], []
+            self.last_category, self.last_gt_status = [], []
 
     def add(self, outputs, targets):
         """outputs: the head's result dicts of a batch (HEAD:317-322); targets: per image {boxes_h, boxes_o, hoi}.
@@ -409,6 +539,8 @@ class DeviceHOIEvaluator:
         if n == 0:
             if self.known_object:
                 self.last_keep = []
+            if self.errors:
+                self.last_category, self.last_gt_status = [], []
             return []
         ppi = [int(o["boxes_h"].shape[0]) for o in outputs]; cpi = [int(o["scores"].shape[0]) for o in outputs]
         cat = lambda k: _cat_results(outputs, k, dev)
@@ -437,6 +569,16 @@ class DeviceHOIEvaluator:
                 hoi.data_ptr(), cell_off, n, self.hoi_object.data_ptr(), self.num_cls, self.n_obj, gt_hoi.data_ptr(), gt_off,
                 keep.data_ptr(), _stream()), "skg_eval_known_object_u8")
             self._keep.append(keep[:L]); self.last_keep = list(keep[:L].split(cpi))
+        if self.errors:                                              # behind the association, on its hoi_out and final labels
+            G = int(sum(gts))                                        # (without ground truth: the padding row, owned by no image)
+            cat = torch.empty(max(L, 1), dtype=torch.uint8, device=dev)
+            status = torch.empty(max(G, 1), dtype=torch.uint8, device=dev)
+            _capi.check(_capi.lib().skg_eval_hoi_errors_u8(
+                boxes_h.data_ptr(), boxes_o.data_ptr(), pair_off, index.data_ptr(), hoi.data_ptr(), labels.data_ptr(), cell_off,
+                n, self.hoi_object.data_ptr(), self.num_cls, gt_h.data_ptr(), gt_o.data_ptr(), gt_hoi.data_ptr(), gt_off,
+                self.min_iou, cat.data_ptr(), status.data_ptr(), _stream()), "skg_eval_hoi_errors_u8")
+            self._cat.append(cat[:L]); self._gt_hoi.append(gt_hoi[:G]); self._gt_status.append(status[:G])
+            self.last_category, self.last_gt_status = list(cat[:L].split(cpi)), list(status[:G].split(gts))
         return list(labels[:L].split(cpi))
 
     def summary(self):
@@ -457,6 +599,20 @@ class DeviceHOIEvaluator:
         out = _hoi_summary(ap.cpu(), self.num_anno_train, self.splits)
         if self.known_object:
             out["known_object"] = _hoi_summary(ap_ko.cpu(), self.num_anno_train, self.splits)
+        if self.errors:
+            nc = self.num_cls
+            cells = torch.zeros(nc, 6, dtype=torch.int64); gt = torch.zeros(nc, 4, dtype=torch.int64)
+            ap_without = {name: torch.zeros(nc, dtype=torch.float64) for name in _AP_WITHOUT}
+            if self._scores:
+                cat = torch.cat(self._cat).long()
+                cells = torch.bincount(hoi * 6 + cat, minlength=nc * 6).reshape(nc, 6).cpu()
+                t = torch.cat(self._gt_hoi); status = torch.cat(self._gt_status).long()
+                ok = status != 255
+                gt = torch.bincount(t[ok] * 4 + status[ok], minlength=nc * 4).reshape(nc, 4).cpu()
+                for name in _AP_WITHOUT:                             # the same rule over a mask, like Known Object
+                    m = _without_mask(name, cat)
+                    ap_without[name] = _class_aps_device(self.algorithm, scores[m], hoi[m], labels[m], nc, self.num_gt).cpu()
+            out["errors"] = _errors_summary(cells, gt, ap_without, out["full"])
         return out
 
 

@@ -1507,7 +1507,7 @@ def test(net, test_loader, evaluator, device=None, lookahead=True):
     with the image's ground-truth pairs and logged into the 600-class 11-point meter; returns `evaluator.summary()`
     (`ap` per class, `full`, and `rare` / `non_rare` when the evaluator knows the training counts; one mean per named class
     list of the evaluator's `splits`; with `known_object=True` a `known_object` dict of the same keys, HICO-DET's second
-    setting).
+    setting; with `errors=True` an `errors` dict, the error breakdown of the Default setting).
 
     test_loader yields batches whose LAST element is the list of targets ({boxes_h, boxes_o, hoi}) and whose other
     elements are the network's arguments -- for the bare interaction head (inference from cached features / detections):

@@ -4,7 +4,8 @@
   FPN-like feature maps + detections -> producer (device NMS/top-k, MultiScaleRoIAlign, global pool) -> feature shard
   + per-image detection JSON on disk -> batched inference from the cache -> 600-way HOI scores -> 11-point mAP
   against synthetic ground truth, in HICO-DET's Default and Known Object settings (full / rare / non-rare; --errors: the
-  error breakdown of the Default setting, cells by category and ground-truth pairs by status)
+  error breakdown of the Default setting, cells by category and ground-truth pairs by status; --pair-nms THRESH: the same
+  numbers again behind the pair NMS over the scored triplets, evaluate.pair_nms -- opt-in, not the reference's)
   -> the producer's kept detections judged against the same ground truth (object-detection mAP, maximum recall, pair
   coverage) -> HICO-DET .mat cells / V-COCO-style pickle.
 
@@ -29,7 +30,7 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False):
+def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_cache_")
     o2v = synth.hico_object_to_verb()
@@ -86,6 +87,18 @@ def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False):
         print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
     if errors:                                                   # where the Default mAP is lost: cells by category, pairs by status
         print(evaluate.format_error_table(summ))
+    if pair_nms is not None:                                     # the remedy for the `duplicate` row: the same evaluation, filtered
+        filtered = evaluate.pair_nms(outputs, pair_nms)
+        ev_f = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True, errors=errors)
+        for out, t in zip(filtered, targets):
+            ev_f.add(out, t)
+        summ_f = ev_f.summary()
+        print("behind pair_nms(thresh=%g): %d of %d cells" % (pair_nms, sum(len(o["scores"]) for o in filtered),
+                                                             sum(len(o["scores"]) for o in outputs)))
+        for name, s in (("Default", summ_f), ("Known Object", summ_f["known_object"])):
+            print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
+        if errors:
+            print(evaluate.format_error_table(summ_f))
     # ---- the boxes behind those numbers: what the producer kept, judged against the same ground truth
     det_ev = evaluate.DeviceDetectionEvaluator(num_classes=80, human_idx=49, num_hoi=600, device=dev)
     det_ev.add(kept_all, targets)
@@ -108,5 +121,7 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--out", default=None)
     ap.add_argument("--errors", action="store_true", help="print the error breakdown of the Default setting")
+    ap.add_argument("--pair-nms", type=float, default=None, metavar="THRESH",
+                    help="evaluate a second time behind evaluate.pair_nms(outputs, THRESH); with --errors both tables are printed")
     a = ap.parse_args()
-    main(a.images, a.batch, a.out, errors=a.errors)
+    main(a.images, a.batch, a.out, errors=a.errors, pair_nms=a.pair_nms)

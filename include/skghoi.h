@@ -853,6 +853,47 @@ int skg_eval_pair_cover_u8(const float* det_boxes, const int64_t* det_labels, co
                            int n_images, const float* gt_h, const float* gt_o, const int64_t* gt_object,
                            const int32_t* gt_off, int human_idx, float min_iou, uint8_t* covered, void* stream);
 
+/* Pair NMS: suppression of duplicate (human, object, class) triplets among the scored cells of an image -- what the error
+ * breakdown's `duplicate` category asks for.  NOT part of the reference, which ranks every cell: opt-in post-processing,
+ * restated from the published idea (PPDM's PNMS; the triplet_nms_filter of QPIC and CDN) -- parity unpinned.  CDN's fractional
+ * exponents (ih^alpha * io^beta) are left out: powf is not bit-reproducible between host and device.  Top-k per image, merging
+ * over ranks and a mask input of the association are not part of it either.
+ *
+ * For a batch in the layout of skg_eval_associate_f32 (boxes_h / boxes_o [sumP, 4], object [sumP], index / pred / scores [L],
+ * index local to the image, cell_off [n_images + 1]; pair_off with n_images + 1 entries).  No lut: V-COCO results alike.
+ * Per image:
+ *   group     the group of cell c is the pair (object[index[c]], pred[c]); cells of different groups or images never interact.
+ *   order     inside a group: score descending, compared as floats (-0 equals +0); equal scores in arrival order (the lower
+ *             cell index first).
+ *   overlap   of two cells a, b on pairs p = index[a], q = index[b]: ih = IoU(boxes_h[p], boxes_h[q]), io = IoU(boxes_o[p],
+ *             boxes_o[q]), the association's plain fp32 arithmetic (areas, clamped width x height, one division).
+ *             SKG_PAIR_NMS_MIN: min(ih, io); SKG_PAIR_NMS_PRODUCT: ih * io, one fp32 multiply.  A comparison with NaN is false
+ *             (min: over thresh iff ih > thresh and io > thresh): a NaN box neither suppresses nor is suppressed.
+ *   greedy    walk the group in order; a cell is suppressed iff an earlier cell THAT WAS KEPT has overlap > thresh, strictly.
+ *             A suppressed cell suppresses nothing.  A cell with a NaN score is dropped (keep 0) and suppresses nothing, the
+ *             convention of the V-COCO and detection matchers.  Two cells on one pair index have overlap 1 wherever the boxes
+ *             are finite and not empty; no special case.
+ * keep [L] uint8: 1 kept, 0 suppressed or dropped; every byte of an image with cells is written exactly once.
+ *
+ * order [L] int64: the permutation of 0 .. L - 1 that puts the batch's cells in (image, group, score descending, arrival)
+ * order -- three stable sorts, the last one on top: by scores + 0.f descending (-0 like +0), by the group key (object and
+ * pred are class indices in [0, 2^31): object * 2^31 + pred), by image.  The kernel finds the group boundaries itself, from
+ * object and pred.  An image with more than SKG_PAIR_NMS_MAX_GROUPS groups or with a group of more than
+ * SKG_PAIR_NMS_MAX_GROUP_CELLS cells is not filtered: keep = 1 in the whole image, and status[0] / status[1] receive the
+ * largest such group count / group size (atomicMax).  An order entry outside its image's cells or an index outside its
+ * image's pairs is found before anything is read through it: keep = 1 in the whole image and status[2] = 1.  status: three
+ * device int32, zero them before the first call.  The head's limits fit the caps: 20 x 39 = 780 pairs in one group, 30 object
+ * labels x 117 verbs in groups.
+ * Errors, before any device call: SKG_E_ARG for n_images < 0 or an unknown measure; n_images == 0 returns 0 and launches
+ * nothing; SKG_E_ARG for a null pointer; SKG_E_ALIGN for boxes_h / boxes_o not 16-byte aligned.                         */
+#define SKG_PAIR_NMS_MIN 0
+#define SKG_PAIR_NMS_PRODUCT 1
+#define SKG_PAIR_NMS_MAX_GROUPS 4096
+#define SKG_PAIR_NMS_MAX_GROUP_CELLS 1024
+int skg_hoi_pair_nms_u8(const float* boxes_h, const float* boxes_o, const int64_t* object, const int32_t* pair_off,
+                        const int64_t* index, const int64_t* pred, const float* scores, const int32_t* cell_off, int n_images,
+                        const int64_t* order, int measure, float thresh, uint8_t* keep, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Order-independent 64-bit checksum of the live parameters (bit patterns weighted by position) over a table of
  * chunks: chunk c covers `count` fp32 words at `ptr` (16-byte aligned) whose first word has global index `first`.

@@ -14,6 +14,8 @@ MAX_DET_PER_IMAGE = 1024
 VCOCO_ACTIONS, VCOCO_MAX_CLASSES, VCOCO_MAX_PERSONS = 26, 52, 256      # SKG_VCOCO_*
 EVAL_MAX_OBJECTS = 1024                              # SKG_EVAL_MAX_OBJECTS: skg_eval_known_object_u8's LDS bit mask
 EVAL_DET_MAX_GT = 1024                               # SKG_EVAL_DET_MAX_GT: ground-truth boxes (2 per pair) per image in LDS
+PAIR_NMS_MIN, PAIR_NMS_PRODUCT = 0, 1                 # SKG_PAIR_NMS_*: skg_hoi_pair_nms_u8's measure
+PAIR_NMS_MAX_GROUPS, PAIR_NMS_MAX_GROUP_CELLS = 4096, 1024       # SKG_PAIR_NMS_MAX_*: groups per image, cells per group
 MAX_NODES = 160
 SPATIAL_LD = 48
 TRANSH_DIM = 50
@@ -268,6 +270,7 @@ PROTOTYPES = {
     "skg_eval_det_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f32, _f32, _vp,
                                          _vp, _vp, _vp, _vp, _vp]),
     "skg_eval_pair_cover_u8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _f32, _vp, _vp]),
+    "skg_hoi_pair_nms_u8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _f32, _vp, _vp, _vp]),
     "skg_transh_sample_ws_ints": (C.c_int64, [C.c_int, C.c_int]),
     "skg_transh_sample_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),

@@ -40,6 +40,13 @@
 //                              with the same 64-bit key.
 //   skg_eval_pair_cover_u8   : one workgroup per image, one lane per ground-truth pair, the detections through LDS in chunks:
 //                              is the human box and the object box of the pair covered by two different detections.
+//
+// Pair NMS over the head's scored cells (opt-in post-processing, not the reference's; the published PNMS idea restated in
+// include/skghoi.h -- parity unpinned):
+//
+//   skg_hoi_pair_nms_u8      : one workgroup per image over the cells sorted by (group, score): the group starts compacted
+//                              into an LDS list, then one wave per group walks the candidates in sequence while its lanes
+//                              clear the alive bits of the later cells they own, in registers.
 #include "skg_common.h"
 
 #define EV_MAX_GT 2048            // ground-truth pairs per image the association keeps in LDS
@@ -714,5 +721,146 @@ extern "C" int skg_eval_pair_cover_u8(const float* det_boxes, const int64_t* det
     if (n_images == 0) return 0;
     hipLaunchKernelGGL(skg_eval_pair_cover_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, det_boxes, det_labels,
                        labels_in, det_off, gt_h, gt_o, gt_object, gt_off, human_idx, min_iou, covered);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ pair NMS
+// Suppression of duplicate (human, object, class) triplets among the head's scored cells, per image -- the remedy the error
+// breakdown's `duplicate` category points at.  Not part of the reference: restated from the published idea (PPDM's PNMS; the
+// triplet_nms_filter of QPIC / CDN without the fractional exponents) -- parity unpinned; the rule is stated in
+// include/skghoi.h (skg_hoi_pair_nms_u8).  `order` puts the batch's cells in (image, group, score descending, arrival) order.
+// One workgroup per image.  Phase 1: lanes stride over the image's sorted positions in tiles of 256 and compact the positions
+// where the group changes into an LDS list (wave ballots + four wave counts; two barriers per tile, every loop bound uniform);
+// every order entry and every pair index is range-checked here, ahead of any write.  An image above a cap, or a malformed one,
+// leaves through a uniform early path (keep = 1 everywhere, reported through status).  Phase 2 has no barrier: the four waves
+// take the groups round-robin; lane l owns the group's cells l, l + 64, ... with one alive bit and one pair index each in
+// registers (PN_SLOTS of them), the wave walks the candidates in sequence, reads the candidate's alive bit from its owner by
+// a shuffle (wave-uniform: all 64 lanes reach every shuffle) and the owners clear the bits of their later cells.  Nothing
+// passes between lanes through memory, so no wave-synchronous assumption is made.  LDS: 16 KB + a few words.
+#define PN_SLOTS (SKG_PAIR_NMS_MAX_GROUP_CELLS / 64)
+
+// sorted position s of image [c0, c1) with pairs [p0, p0 + np) -> its cell, global pair index and group key; false = malformed
+__device__ __forceinline__ bool pn_cell(const int64_t* __restrict__ order, const int64_t* __restrict__ index,
+                                        const int64_t* __restrict__ object, const int64_t* __restrict__ pred, int s, int c0,
+                                        int c1, int p0, int np, int64_t& ob, int64_t& pr) {
+    const int64_t c = order[s];
+    if (c < c0 || c >= c1) return false;
+    const int64_t li = index[c];
+    if ((uint64_t)li >= (uint64_t)np) return false;
+    ob = object[(int64_t)p0 + li]; pr = pred[c];
+    return true;
+}
+
+__global__ __launch_bounds__(256) void skg_hoi_pair_nms_kernel(
+    const float* __restrict__ boxes_h, const float* __restrict__ boxes_o, const int64_t* __restrict__ object,
+    const int32_t* __restrict__ pair_off, const int64_t* __restrict__ index, const int64_t* __restrict__ pred,
+    const float* __restrict__ scores, const int32_t* __restrict__ cell_off, const int64_t* __restrict__ order, int measure,
+    float thresh, uint8_t* __restrict__ keep, int32_t* __restrict__ status) {
+    __shared__ int sstart[SKG_PAIR_NMS_MAX_GROUPS + 1];      // sorted positions where a group starts, then the image's end
+    __shared__ int swave[4];
+    __shared__ int sbad, slong;
+    const int a = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int c0 = cell_off[a], c1 = cell_off[a + 1];
+    const int p0 = pair_off[a], np = pair_off[a + 1] - p0;
+    if (c1 <= c0) return;                                    // uniform: an image without cells
+    if (tid == 0) { sbad = 0; slong = 0; }
+    __syncthreads();
+
+    // ---- phase 1: the group starts, in order
+    int ng = 0;                                              // the same in every lane
+    for (int s0 = c0; s0 < c1; s0 += 256) {                  // uniform
+        const int s = s0 + tid;
+        bool start = false;
+        if (s < c1) {
+            int64_t ob = 0, pr = 0, ob1 = 0, pr1 = 0;
+            bool ok = pn_cell(order, index, object, pred, s, c0, c1, p0, np, ob, pr);
+            start = s == c0;
+            if (ok && !start) {
+                ok = pn_cell(order, index, object, pred, s - 1, c0, c1, p0, np, ob1, pr1);
+                start = ob != ob1 || pr != pr1;
+            }
+            if (!ok) sbad = 1;                               // (every writer stores the same value)
+        }
+        const unsigned long long b = __ballot(start);
+        if (lane == 0) swave[wv] = __popcll(b);
+        __syncthreads();
+        int pos = ng + __popcll(b & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wv; ++w) pos += swave[w];
+        if (start && pos < SKG_PAIR_NMS_MAX_GROUPS) sstart[pos] = s;
+        ng += (swave[0] + swave[1]) + (swave[2] + swave[3]);
+        __syncthreads();                                     // swave is read, sstart and sbad are written
+    }
+    const bool bad = sbad != 0;
+    if (!bad && ng <= SKG_PAIR_NMS_MAX_GROUPS) {             // uniform
+        if (tid == 0) sstart[ng] = c1;
+        __syncthreads();
+        int longest = 0;
+        for (int g = tid; g < ng; g += 256) longest = max(longest, sstart[g + 1] - sstart[g]);
+        if (longest > SKG_PAIR_NMS_MAX_GROUP_CELLS) atomicMax(&slong, longest);
+        __syncthreads();
+    }
+    const int too_long = slong;                              // 0 unless the branch above ran and found one
+    if (bad || ng > SKG_PAIR_NMS_MAX_GROUPS || too_long) {   // uniform: reported, every byte of the image written once
+        if (tid == 0) {
+            if (bad) atomicMax(status + 2, 1);
+            else if (ng > SKG_PAIR_NMS_MAX_GROUPS) atomicMax(status, ng);
+            else atomicMax(status + 1, too_long);
+        }
+        for (int c = c0 + tid; c < c1; c += 256) keep[c] = (uint8_t)1;
+        return;
+    }
+
+    // ---- phase 2: greedy suppression, one wave per group
+    for (int g = wv; g < ng; g += 4) {                       // uniform over the wave
+        const int gs = sstart[g], n = sstart[g + 1] - gs;
+        unsigned alive = 0u;                                 // bit k: this lane's cell k * 64 + lane is neither dropped nor suppressed
+        int64_t pj[PN_SLOTS];
+#pragma unroll
+        for (int k = 0; k < PN_SLOTS; ++k) {
+            const int j = k * 64 + lane;
+            pj[k] = 0;
+            if (j < n) {
+                const int64_t c = order[gs + j];
+                pj[k] = (int64_t)p0 + index[c];
+                const float s = scores[c];
+                if (s == s) alive |= 1u << k;                // a NaN score: dropped, suppresses nothing
+            }
+        }
+        for (int i = 0; i + 1 < n; ++i) {                    // uniform over the wave
+            const unsigned owner = __shfl(alive, i & 63, 64);
+            if (!((owner >> (i >> 6)) & 1u)) continue;       // uniform: dropped or suppressed, suppresses nothing
+            const int64_t pi = (int64_t)p0 + index[order[gs + i]];
+            const float4 hi = *reinterpret_cast<const float4*>(boxes_h + 4 * pi);
+            const float4 oi = *reinterpret_cast<const float4*>(boxes_o + 4 * pi);
+#pragma unroll
+            for (int k = 0; k < PN_SLOTS; ++k) {
+                const int j = k * 64 + lane;
+                if (j <= i || j >= n || !((alive >> k) & 1u)) continue;
+                const float ih = ev_iou(hi, *reinterpret_cast<const float4*>(boxes_h + 4 * pj[k]));
+                const float io = ev_iou(oi, *reinterpret_cast<const float4*>(boxes_o + 4 * pj[k]));
+                // min: fminf(ih, io) > thresh where both are numbers; a NaN on either side makes it false
+                const bool over = measure == SKG_PAIR_NMS_PRODUCT ? ih * io > thresh : (ih > thresh && io > thresh);
+                if (over) alive &= ~(1u << k);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < PN_SLOTS; ++k) {
+            const int j = k * 64 + lane;
+            if (j < n) keep[order[gs + j]] = (uint8_t)((alive >> k) & 1u);
+        }
+    }
+}
+
+extern "C" int skg_hoi_pair_nms_u8(const float* boxes_h, const float* boxes_o, const int64_t* object, const int32_t* pair_off,
+                                   const int64_t* index, const int64_t* pred, const float* scores, const int32_t* cell_off,
+                                   int n_images, const int64_t* order, int measure, float thresh, uint8_t* keep,
+                                   int32_t* status, void* stream) {
+    if (n_images < 0 || (measure != SKG_PAIR_NMS_MIN && measure != SKG_PAIR_NMS_PRODUCT)) return SKG_E_ARG;
+    if (n_images == 0) return 0;
+    if (!boxes_h || !boxes_o || !object || !pair_off || !index || !pred || !scores || !cell_off || !order || !keep || !status)
+        return SKG_E_ARG;
+    if (!skg_aligned16(boxes_h) || !skg_aligned16(boxes_o)) return SKG_E_ALIGN;
+    hipLaunchKernelGGL(skg_hoi_pair_nms_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, boxes_h, boxes_o, object,
+                       pair_off, index, pred, scores, cell_off, order, measure, thresh, keep, status);
     return skg_launch_status();
 }

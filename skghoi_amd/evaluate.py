@@ -15,6 +15,8 @@ V-COCO's AP_role (scenario 1 and 2) is computed in-process by VCOCOEvaluator / D
 external toolkit restated under the same terms.
 The detections behind the head (hicodet/detections/eval_detections.py: object-detection mAP and mean maximum recall over the
 kept boxes, generate_gt_detections.py) are judged by DetectionEvaluator / DeviceDetectionEvaluator, which add pair coverage.
+pair_nms / pair_nms_keep suppress duplicate (human, object, class) triplets among the scored cells of an image before they reach
+an evaluator or an exporter (skg_hoi_pair_nms_u8) -- opt-in, the published PNMS idea restated, not the reference's.
 
 Everything works on whatever device the result tensors live on (the association is a handful of small IoU matrices);
 nothing here is on the timed hot path.
@@ -1127,6 +1129,166 @@ class DeviceDetectionEvaluator:
                 hoi_pairs = torch.bincount(hoi[inside], minlength=self.num_hoi).cpu()
                 hoi_covered = torch.bincount(hoi[inside & cov.bool()], minlength=self.num_hoi).cpu()
         return _det_summary(ap.cpu(), self.num_gt.cpu(), tp.cpu(), pairs, covered, hoi_pairs, hoi_covered)
+
+
+# ----------------------------------------------------------------------------------------------- pair NMS
+# Suppression of duplicate (human, object, class) triplets among the scored cells of an image: the remedy for the `duplicate`
+# category of the error breakdown (two detections of one person at IoU 0.45 both survive the box NMS of `preprocess`, both are
+# paired with the same object and scored for the same verb).  NOT the reference's, which ranks every cell: opt-in
+# post-processing of the head's result dicts, restated from the published idea (PPDM's PNMS; the triplet_nms_filter of QPIC
+# and CDN, without CDN's fractional exponents -- powf is not bit-reproducible between host and device) -- parity unpinned.
+# The rule is stated in include/skghoi.h (skg_hoi_pair_nms_u8).  Per image: the group of cell c is (object[index[c]],
+# prediction[c]) -- no LUT, V-COCO results alike; inside a group the cells go score descending (-0 equals +0), equal scores in
+# arrival order; the overlap of two cells is min(ih, io) ("min") or ih * io ("product", one fp32 multiply) of the IoUs of their
+# human and their object boxes in the association's fp32 arithmetic, a comparison with NaN false; a cell is suppressed iff an
+# earlier cell of its group THAT WAS KEPT has overlap > thresh, strictly; a cell with a NaN score is dropped and suppresses
+# nothing.  `thresh` has no default: there is no dataset in the tree to tune one on.  Top-k per image, merging over ranks and a
+# mask input of the association are not part of it.
+PAIR_NMS_MEASURES = ("min", "product")                           # SKG_PAIR_NMS_MIN, SKG_PAIR_NMS_PRODUCT
+_PER_CELL_KEYS = {"index": 0, "prediction": 0, "scores": 0, "labels": 0, "prior": 1}      # key -> the dimension of the cells
+
+
+def _pair_nms_args(thresh, measure):
+    if measure not in PAIR_NMS_MEASURES:
+        raise ValueError("unknown measure %r: one of %s" % (measure, ", ".join(PAIR_NMS_MEASURES)))
+    thresh = float(thresh)
+    if thresh != thresh:
+        raise ValueError("thresh is NaN")
+    return thresh, PAIR_NMS_MEASURES.index(measure)
+
+
+def _pair_nms_keep_host(output, thresh, code):
+    """The rule on one image's result dict in plain torch on the host -> uint8 keep [n_cells]: the restatement the kernel is
+    checked against."""
+    idx = output["index"].reshape(-1).cpu().long()
+    sc = output["scores"].reshape(-1).cpu().float()
+    keep = ~torch.isnan(sc)                                      # a NaN score: dropped, and never a candidate below
+    n = idx.shape[0]
+    if n < 2:
+        return keep.to(torch.uint8)
+    bh = output["boxes_h"].cpu().float().reshape(-1, 4)[idx]; bo = output["boxes_o"].cpu().float().reshape(-1, 4)[idx]
+    ob = output["object"].reshape(-1).cpu().long()[idx]; pr = output["prediction"].reshape(-1).cpu().long()
+    o = torch.sort(sc + 0., descending=True, stable=True).indices              # -0 like +0; arrival order on ties
+    o = o[torch.sort(pr[o], stable=True).indices]
+    o = o[torch.sort(ob[o], stable=True).indices]                              # (object, prediction, score descending, arrival)
+    first = torch.ones(n, dtype=torch.bool)
+    first[1:] = (ob[o][1:] != ob[o][:-1]) | (pr[o][1:] != pr[o][:-1])
+    bounds = torch.nonzero(first).squeeze(1).tolist() + [n]
+    thr = torch.tensor(thresh, dtype=torch.float32)
+    for s, e in zip(bounds[:-1], bounds[1:]):
+        if e - s < 2:
+            continue
+        g = o[s:e]
+        ih = box_iou(bh[g], bh[g]); io = box_iou(bo[g], bo[g])
+        over = (ih * io > thr) if code else ((ih > thr) & (io > thr))         # NaN: false
+        alive = keep[g].clone()
+        for i in range(e - s - 1):                               # greedy: only a kept cell suppresses
+            if alive[i]:
+                alive[i + 1:] &= ~over[i, i + 1:]
+        keep[g] = alive
+    return keep.to(torch.uint8)
+
+
+def _pair_nms_device(outputs, thresh, code, dev):
+    """Three stable sorts and one skg_hoi_pair_nms_u8 launch on the current stream, no host synchronisation.  Returns keep
+    (uint8 device tensor, its first sum(cells) entries), status (three device int32: the kernel's), the cells per image and the
+    image of every cell (int64 device tensor)."""
+    from . import _capi
+    from .engine import _stream
+    n = len(outputs)
+    ppi = [int(o["boxes_h"].shape[0]) for o in outputs]; cpi = [int(o["scores"].shape[0]) for o in outputs]
+    L = int(sum(cpi))
+    keep = torch.zeros(max(L, 1), dtype=torch.uint8, device=dev)
+    status = torch.zeros(3, dtype=torch.int32, device=dev)
+    cat = lambda k: _cat_results(outputs, k, dev)
+    # per cell: its image and the first pair of its image, from the shapes alone
+    per_cell = np.stack([np.repeat(np.arange(n, dtype=np.int64), cpi),
+                         np.repeat(np.concatenate([[0], np.cumsum(ppi)[:-1]]).astype(np.int64), cpi)])
+    per_cell = torch.from_numpy(per_cell).to(dev)
+    image = per_cell[0]
+    if L == 0:
+        return keep, status, cpi, image
+    boxes_h = cat("boxes_h").float().reshape(-1, 4).contiguous(); boxes_o = cat("boxes_o").float().reshape(-1, 4).contiguous()
+    obj = cat("object").long().reshape(-1); index = cat("index").long().reshape(-1)
+    pred = cat("prediction").long().reshape(-1); scores = cat("scores").float().reshape(-1).contiguous()
+    offs_d, (pair_off, cell_off) = _offset_table(dev, ppi, cpi)
+    boxes_h, boxes_o, obj = map(_pad_row, (boxes_h, boxes_o, obj))
+    # class indices in [0, 2^31): one key per (object, prediction).  (The clamp keeps this gather inside `object` whatever
+    # `index` holds; the kernel checks every index against its image's pairs and reports through status.)
+    group = obj[(index + per_cell[1]).clamp(0, obj.shape[0] - 1)] * (1 << 31) + pred
+    order = torch.sort(scores + 0., descending=True, stable=True).indices      # -0 like +0; arrival order on ties
+    order = order[torch.sort(group[order], stable=True).indices]
+    order = order[torch.sort(image[order], stable=True).indices].contiguous()
+    _capi.check(_capi.lib().skg_hoi_pair_nms_u8(
+        boxes_h.data_ptr(), boxes_o.data_ptr(), obj.data_ptr(), pair_off, index.data_ptr(), pred.data_ptr(), scores.data_ptr(),
+        cell_off, n, order.data_ptr(), code, thresh, keep.data_ptr(), status.data_ptr(), _stream()), "skg_hoi_pair_nms_u8")
+    return keep, status, cpi, image
+
+
+def _pair_nms_raise(status):
+    """status: the kernel's three words on the host."""
+    from . import _capi
+    groups, cells, malformed = (int(v) for v in status)
+    if malformed:
+        raise IndexError("a result dict's `index` is outside its image's pairs")
+    if groups:
+        raise _capi.SkgError("an image has %d (object, prediction) groups; skg_hoi_pair_nms_u8 takes at most %d per image "
+                             "(SKG_PAIR_NMS_MAX_GROUPS)" % (groups, _capi.PAIR_NMS_MAX_GROUPS))
+    if cells:
+        raise _capi.SkgError("a group has %d cells; skg_hoi_pair_nms_u8 takes at most %d per group "
+                             "(SKG_PAIR_NMS_MAX_GROUP_CELLS)" % (cells, _capi.PAIR_NMS_MAX_GROUP_CELLS))
+
+
+def pair_nms_keep(outputs, thresh, measure="min"):
+    """The pair NMS flags of the head's result dicts of a batch (the rule above PAIR_NMS_MEASURES): per image a uint8 tensor
+    [n_cells], 1 = kept.  On the device: views of one device tensor, written by three stable sorts and one
+    skg_hoi_pair_nms_u8 launch on the current stream, WITHOUT a host synchronisation -- so an image above one of the kernel's
+    caps (_capi.PAIR_NMS_MAX_GROUPS groups, _capi.PAIR_NMS_MAX_GROUP_CELLS cells in one group; the head's own limits fit) comes
+    back all ones here, as the C rule says; `pair_nms`, which has to synchronise anyway, raises.  On CPU tensors: the host
+    restatement (no caps).  An empty list gives []."""
+    thresh, code = _pair_nms_args(thresh, measure)
+    if len(outputs) == 0:
+        return []
+    dev = outputs[0]["scores"].device
+    if dev.type != "cuda":
+        return [_pair_nms_keep_host(o, thresh, code) for o in outputs]
+    keep, _, cpi, _ = _pair_nms_device(outputs, thresh, code, dev)
+    return list(keep[:int(sum(cpi))].split(cpi))
+
+
+def _pair_nms_filtered(output, sel):
+    """A new result dict with the per-cell entries at the cells `sel` (int64, ascending); the per-pair entries (boxes_h,
+    boxes_o, object, weights, unary_labels) are passed through as they are, so `index` stays valid."""
+    return {k: (v.index_select(_PER_CELL_KEYS[k], sel) if k in _PER_CELL_KEYS and torch.is_tensor(v) else v)
+            for k, v in output.items()}
+
+
+def pair_nms(outputs, thresh, measure="min"):
+    """The head's result dicts of a batch without the cells the pair NMS suppresses or drops (the rule above
+    PAIR_NMS_MEASURES): new dicts, the inputs are not touched; `index`, `prediction`, `scores`, `labels` (when present) and
+    `prior` (along dim 1) hold the kept cells in their order, everything per pair is passed through.  What comes out goes into
+    the evaluators, hicodet_mat_cells and vcoco_results like any result list: `functools.partial(pair_nms, thresh=0.7)` is a
+    `postprocess` of trainer.test.
+
+    On the device the new shapes have to reach the host: ONE synchronisation per call -- one read of the per-image kept counts
+    and the kernel's status, not one per image.  An image above a cap of the kernel raises SkgError naming the cap."""
+    thresh, code = _pair_nms_args(thresh, measure)
+    if len(outputs) == 0:
+        return []
+    dev = outputs[0]["scores"].device
+    if dev.type != "cuda":
+        return [_pair_nms_filtered(o, torch.nonzero(_pair_nms_keep_host(o, thresh, code)).squeeze(1).to(dev)) for o in outputs]
+    n = len(outputs)
+    keep, status, cpi, image = _pair_nms_device(outputs, thresh, code, dev)
+    L = int(sum(cpi))
+    counts = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, image, keep[:L].long())
+    host = torch.cat([counts, status.long()]).cpu()              # the one synchronisation
+    _pair_nms_raise(host[n:].tolist())
+    kept = host[:n].tolist()
+    # the kept cells in arrival order, their number known: nothing below waits for the device
+    sel = torch.sort(keep[:L], descending=True, stable=True).indices[:int(sum(kept))].split(kept)
+    first = np.concatenate([[0], np.cumsum(cpi)]).tolist()
+    return [_pair_nms_filtered(o, s - first[a]) for a, (o, s) in enumerate(zip(outputs, sel))]
 
 
 # ----------------------------------------------------------------------------------------------- exporters

@@ -1502,7 +1502,7 @@ def _with_lookahead(loader, enabled=True, depth=1):
 
 
 @torch.no_grad()
-def test(net, test_loader, evaluator, device=None, lookahead=True):
+def test(net, test_loader, evaluator, device=None, lookahead=True, postprocess=None):
     """utils.py:148-198 (`test`): eval mode, ONE image per forward (`assert len(output) == 1`), every result associated
     with the image's ground-truth pairs and logged into the 600-class 11-point meter; returns `evaluator.summary()`
     (`ap` per class, `full`, and `rare` / `non_rare` when the evaluator knows the training counts; one mean per named class
@@ -1518,7 +1518,11 @@ def test(net, test_loader, evaluator, device=None, lookahead=True):
 
     lookahead: the loop runs one image ahead of the network -- image i + 1 is uploaded BEFORE forward i is enqueued and its
     detection selection, count read-back and TransH table draw run beside forward i on the head's side stream
-    (InteractionHead.prefetch_eval), so forward i + 1 begins at its launch plan.  Same results, same RNG stream."""
+    (InteractionHead.prefetch_eval), so forward i + 1 begins at its launch plan.  Same results, same RNG stream.
+
+    postprocess: a callable applied to the forward's result list before `evaluator.add` -- for example
+    `functools.partial(evaluate.pair_nms, thresh=0.7)`, the pair NMS over the scored triplets (not the reference's: opt-in;
+    on the device it costs one host synchronisation per image, behind the look-ahead's launches).  None: the loop as it is."""
     mod = net.module if isinstance(net, nn.parallel.DistributedDataParallel) else net
     if device is None:
         p = next(mod.parameters(), None)
@@ -1546,6 +1550,8 @@ def test(net, test_loader, evaluator, device=None, lookahead=True):
             ahead(nxt_inputs[1], after=uploaded)
         if output is not None:
             assert len(output) == 1, "Batch size is not 1"           # utils.py:166-167
+            if postprocess is not None:
+                output = postprocess(output)
             target = cur[-1][0]
             if batched:
                 evaluator.add(output, [target])

@@ -5,7 +5,9 @@
   + per-image detection JSON on disk -> batched inference from the cache -> 600-way HOI scores -> 11-point mAP
   against synthetic ground truth, in HICO-DET's Default and Known Object settings (full / rare / non-rare; --errors: the
   error breakdown of the Default setting, cells by category and ground-truth pairs by status; --pair-nms THRESH: the same
-  numbers again behind the pair NMS over the scored triplets, evaluate.pair_nms -- opt-in, not the reference's)
+  numbers again behind the pair NMS over the scored triplets, evaluate.pair_nms -- opt-in, not the reference's;
+  --bootstrap N: confidence intervals of every mean from N image-level bootstrap replicates, and with --pair-nms the paired
+  comparison of the filtered run against the plain run)
   -> the producer's kept detections judged against the same ground truth (object-detection mAP, maximum recall, pair
   coverage) -> HICO-DET .mat cells / V-COCO-style pickle.
 
@@ -30,7 +32,7 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None):
+def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None, bootstrap=None):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_cache_")
     o2v = synth.hico_object_to_verb()
@@ -79,17 +81,20 @@ def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None
         targets.append(dict(boxes_h=out["boxes_h"][p:p + 1].cpu(), boxes_o=out["boxes_o"][p:p + 1].cpu(),
                             object=out["object"][p:p + 1].cpu(), hoi=torch.tensor([hoi])))
     num_anno_train = [5 if h % 4 == 0 else 50 for h in range(600)]      # synthetic training counts: every fourth class is rare
-    ev = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True, errors=errors)
+    ev = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True, errors=errors, bootstrap=bootstrap)
     for out, t in zip(outputs, targets):
         ev.add(out, t)
     summ = ev.summary()
     for name, s in (("Default", summ), ("Known Object", summ["known_object"])):
         print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
+    if bootstrap:                                                # how far those means move when the images are resampled
+        print(evaluate.format_bootstrap(summ))
     if errors:                                                   # where the Default mAP is lost: cells by category, pairs by status
         print(evaluate.format_error_table(summ))
     if pair_nms is not None:                                     # the remedy for the `duplicate` row: the same evaluation, filtered
         filtered = evaluate.pair_nms(outputs, pair_nms)
-        ev_f = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True, errors=errors)
+        ev_f = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True, errors=errors,
+                                     bootstrap=bootstrap)
         for out, t in zip(filtered, targets):
             ev_f.add(out, t)
         summ_f = ev_f.summary()
@@ -97,6 +102,11 @@ def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None
                                                              sum(len(o["scores"]) for o in outputs)))
         for name, s in (("Default", summ_f), ("Known Object", summ_f["known_object"])):
             print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
+        if bootstrap:                                            # the same images in the same order: the replicates are paired
+            for key in ("full", "rare", "non_rare"):
+                c = evaluate.bootstrap_compare(summ_f, summ, key)
+                print("pair_nms - plain, %-8s delta %+.4f  replicates %+.4f [%+.4f, %+.4f]  P(filtered better) %.3f" % (
+                    key, c["delta"], c["mean"], c["lo"], c["hi"], c["p_a_better"]))
         if errors:
             print(evaluate.format_error_table(summ_f))
     # ---- the boxes behind those numbers: what the producer kept, judged against the same ground truth
@@ -123,5 +133,7 @@ if __name__ == "__main__":
     ap.add_argument("--errors", action="store_true", help="print the error breakdown of the Default setting")
     ap.add_argument("--pair-nms", type=float, default=None, metavar="THRESH",
                     help="evaluate a second time behind evaluate.pair_nms(outputs, THRESH); with --errors both tables are printed")
+    ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
+                    help="N image-level bootstrap replicates: intervals of every mean; with --pair-nms the paired comparison")
     a = ap.parse_args()
-    main(a.images, a.batch, a.out, errors=a.errors, pair_nms=a.pair_nms)
+    main(a.images, a.batch, a.out, errors=a.errors, pair_nms=a.pair_nms, bootstrap=a.bootstrap)

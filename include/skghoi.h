@@ -807,6 +807,48 @@ int skg_eval_vcoco_match_f32(const float* boxes_h, const float* boxes_o, const i
  * -- the area under the precision-recall curve made monotone from the right.  0 without ground truth or detections.   */
 int skg_eval_ap_voc_f64(const float* labels_sorted, const int64_t* class_off, const int64_t* num_gt, int n_classes,
                         double* ap, void* stream);
+/* Bootstrap AP: the AP of every class in every replicate of a paired image-level bootstrap, for confidence intervals of the
+ * mAP.  NOT part of the reference, which reports point estimates only: opt-in, this project's own definition (the percentile
+ * bootstrap over images) -- parity unpinned, there is nothing to be on a par with.  The rule, stated once:
+ *
+ *   image ids   an evaluator built with `bootstrap=` numbers the images it is given 0, 1, 2, ... in `add` order; every cell
+ *               and every ground-truth pair carries the id of its image.
+ *   weights     W [n_images, n_boot] uint8, replicate index fastest: with g = torch.Generator().manual_seed(seed) on the CPU
+ *               (the function's own generator: the global one, which the head's TransH draws use, does not move), for
+ *               b = 0 .. n_boot - 1 in order, column b = bincount(torch.randint(n_images, (n_images,), generator=g),
+ *               minlength=n_images) -- n_images draws with replacement.  A count above 255 is an OverflowError.
+ *   replicate   the AP of class c in replicate b is the evaluator's AP over the SAME ranking (the class's cells score
+ *               descending, equal scores in arrival order: labels_sorted / class_off of skg_eval_ap11_f64) with cell i counted
+ *               w_i = W[img_i, b] times.  tp_i = sum_{j <= i} w_j * label_j and n_i = sum_{j <= i} w_j are int64; positions
+ *               with w_i == 0 do not exist; prec_i = (double)tp_i / (double)n_i, rec_i = (double)tp_i / (double)num_gt_b[c],
+ *               num_gt_b[c] = sum_img W[img, b] * (ground-truth pairs of class c in img; ids outside the classes are ignored).
+ *               SKG_AP_11P: sum_k max{prec_i : rec_i >= thresholds11[k]} / 11, each term divided by 11 and added in
+ *               threshold order (the host meter's sequence).  SKG_AP_AUC: (1 / num_gt_b[c]) sum_i w_i * label_i *
+ *               max_{j >= i} prec_j, each product rounded on its own and added from the last position to the first.
+ *               0 when num_gt_b[c] == 0 or the class has no cell of positive weight.  This is the AP of the explicitly
+ *               duplicated detection list ('11P' bit for bit, 'AUC' up to the order of a float64 sum); unit weights give the
+ *               point estimate, which is why an evaluator refuses a num_gt_test that disagrees with the targets it was given.
+ *   means       class c is DEFINED in replicate b iff num_gt_b[c] > 0 or num_gt[c] == 0 (the latter contributes 0, as it does
+ *               to the point estimate).  A replicate's full / rare / non_rare / named split is the mean of its APs over the
+ *               defined classes of that list, NaN if none is defined.  (A class whose ground truth sits in one image is absent
+ *               from (1 - 1/n)^n = 0.34 .. 0.37 of the replicates; scored as 0 there it would drag every `rare` replicate
+ *               down.)  Intervals are percentiles of the replicate means (torch.nanquantile, linear interpolation).
+ *
+ * labels_sorted (a non-zero label is a true positive) / img_sorted [n_cells], class_off [n_classes + 1] (clamped to
+ * [0, n_cells] before anything is read through it); weights row stride ldw >= n_boot; num_gt_boot [n_classes, n_boot];
+ * ap [n_boot, n_classes], every element written exactly once by a launch (no zero fill is needed).  An img_sorted value
+ * outside [0, n_images) is found before anything is read through it: the cell counts as weight 0 and status (one device int32,
+ * zero it first) receives 1.
+ * Errors, before any device call: SKG_E_ARG for n_classes < 0, n_cells < 0, n_boot < 1, n_images < 0, ldw < n_boot, an unknown
+ * algorithm, thresholds11 == NULL with SKG_AP_11P, a null class_off / num_gt_boot / ap / status, or, with n_cells > 0, a null
+ * labels_sorted / img_sorted / weights; SKG_E_LIMIT for n_boot above 64 * 65535.  Then n_classes == 0 or n_cells == 0 returns 0
+ * and launches nothing (ap is left as it is: the caller's zeros).                                                          */
+#define SKG_AP_11P 0
+#define SKG_AP_AUC 1
+int skg_eval_ap_boot_f64(const float* labels_sorted, const int32_t* img_sorted, const int64_t* class_off, int64_t n_cells,
+                         int n_classes, const uint8_t* weights, int n_images, int n_boot, int64_t ldw,
+                         const int64_t* num_gt_boot, int algorithm, const double* thresholds11, double* ap, int32_t* status,
+                         void* stream);
 
 /* Object-detection quality of the boxes that go into the cache (hicodet/detections/eval_detections.py:91-127: class-wise
  * NMS of the ground-truth boxes, pocket BoxAssociation per object class), for a batch of images: detections det_boxes

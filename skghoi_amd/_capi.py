@@ -15,6 +15,7 @@ VCOCO_ACTIONS, VCOCO_MAX_CLASSES, VCOCO_MAX_PERSONS = 26, 52, 256      # SKG_VCO
 EVAL_MAX_OBJECTS = 1024                              # SKG_EVAL_MAX_OBJECTS: skg_eval_known_object_u8's LDS bit mask
 EVAL_DET_MAX_GT = 1024                               # SKG_EVAL_DET_MAX_GT: ground-truth boxes (2 per pair) per image in LDS
 PAIR_NMS_MIN, PAIR_NMS_PRODUCT = 0, 1                 # SKG_PAIR_NMS_*: skg_hoi_pair_nms_u8's measure
+AP_11P, AP_AUC = 0, 1                                # SKG_AP_*: skg_eval_ap_boot_f64's algorithm
 PAIR_NMS_MAX_GROUPS, PAIR_NMS_MAX_GROUP_CELLS = 4096, 1024       # SKG_PAIR_NMS_MAX_*: groups per image, cells per group
 MAX_NODES = 160
 SPATIAL_LD = 48
@@ -267,6 +268,8 @@ PROTOTYPES = {
     "skg_eval_vcoco_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
                                            _f32, _vp, _vp, _vp, _vp]),
     "skg_eval_ap_voc_f64": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "skg_eval_ap_boot_f64": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, _i64, _vp, C.c_int, _vp, _vp, _vp,
+                                       _vp]),
     "skg_eval_det_match_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f32, _f32, _vp,
                                          _vp, _vp, _vp, _vp, _vp]),
     "skg_eval_pair_cover_u8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _f32, _vp, _vp]),

@@ -47,6 +47,12 @@
 //   skg_hoi_pair_nms_u8      : one workgroup per image over the cells sorted by (group, score): the group starts compacted
 //                              into an LDS list, then one wave per group walks the candidates in sequence while its lanes
 //                              clear the alive bits of the later cells they own, in registers.
+//
+// Bootstrap confidence intervals of the mAP (opt-in, this project's own definition; the rule is stated in include/skghoi.h):
+//
+//   skg_eval_ap_boot_f64     : one wave per (class, 64 replicates) over the same sorted labels and the image id of every cell:
+//                              lane = replicate, every lane walks the class in sequence with its weighted running sums in
+//                              registers; '11P' or the VOC all-point area.
 #include "skg_common.h"
 
 #define EV_MAX_GT 2048            // ground-truth pairs per image the association keeps in LDS
@@ -862,5 +868,133 @@ extern "C" int skg_hoi_pair_nms_u8(const float* boxes_h, const float* boxes_o, c
     if (!skg_aligned16(boxes_h) || !skg_aligned16(boxes_o)) return SKG_E_ALIGN;
     hipLaunchKernelGGL(skg_hoi_pair_nms_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, boxes_h, boxes_o, object,
                        pair_off, index, pred, scores, cell_off, order, measure, thresh, keep, status);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ bootstrap AP
+// AP of every class in every replicate of a paired image-level bootstrap.  Not part of the reference: this project's own
+// definition, the rule is stated in include/skghoi.h (skg_eval_ap_boot_f64) -- parity unpinned, there is nothing to be on a par
+// with.  The ranking (labels_sorted / class_off of the two AP kernels above, img_sorted beside it) is shared by all replicates;
+// a replicate counts cell i w = weights[img_sorted[i], b] times.  One wave per (class, 64 replicates), lane = replicate: the
+// position in the class is the same in every lane, so the label and the image id are wave-uniform loads and the weight load
+// is 64 consecutive bytes of one row.  Every lane walks the class in sequence with its running sums (int64) in registers;
+// EVB_CHUNK cells are fetched ahead of the arithmetic.  A division is needed only where w * label > 0: behind a true positive
+// the precision only falls until the next one, so every maximum of the precision sits on a true positive.  '11P' is one
+// forward walk with eleven running maxima; 'AUC' is a forward walk for the class totals and a backward walk that carries the
+// suffix maximum.  No LDS, no barrier, no atomics but atomicMax into status; every lane with a replicate stores its ap once.
+#define EVB_CHUNK 8
+
+// cell `i` of the class in replicate `b`: its weight (0 for an image id outside [0, n_images), reported through `bad`) and
+// whether it is a true positive.  i, and so the image id and the branch on it, are wave-uniform.
+__device__ __forceinline__ int evb_cell(const float* __restrict__ labels_sorted, const int32_t* __restrict__ img_sorted,
+                                        const uint8_t* __restrict__ weights, int64_t i, int n_images, int64_t ldw, int b,
+                                        bool& pos, bool& bad) {
+    const int32_t img = img_sorted[i];
+    pos = labels_sorted[i] != 0.f;
+    if ((uint32_t)img >= (uint32_t)n_images) { bad = true; return 0; }       // checked before anything is read through it
+    return (int)weights[(int64_t)img * ldw + b];
+}
+
+template <int kAlgorithm>
+__global__ __launch_bounds__(64) void skg_eval_ap_boot_kernel(
+    const float* __restrict__ labels_sorted, const int32_t* __restrict__ img_sorted, const int64_t* __restrict__ class_off,
+    int64_t n_cells, int n_classes, const uint8_t* __restrict__ weights, int n_images, int n_boot, int64_t ldw,
+    const int64_t* __restrict__ num_gt_boot, const double* __restrict__ thr, double* __restrict__ ap,
+    int32_t* __restrict__ status) {
+    const int c = blockIdx.x;
+    const int b = blockIdx.y * 64 + (int)threadIdx.x;
+    const bool live = b < n_boot;
+    const int br = live ? b : n_boot - 1;                    // lanes past the last replicate read the last one, store nothing
+    int64_t s0 = class_off[c], s1 = class_off[c + 1];
+    if (s0 < 0) s0 = 0;
+    if (s1 > n_cells) s1 = n_cells;                          // a malformed table reads nothing outside the cells
+    const int64_t ngi = num_gt_boot[(int64_t)c * n_boot + br];
+    const double ng = (double)ngi;
+    bool bad = false;
+    double result = 0.0;
+    if (kAlgorithm == 0) {
+        double t[11], best[11];
+#pragma unroll
+        for (int k = 0; k < 11; ++k) { t[k] = thr[k]; best[k] = 0.0; }
+        int64_t tp = 0, n = 0;
+        for (int64_t i0 = s0; i0 < s1; i0 += EVB_CHUNK) {    // uniform
+            int w[EVB_CHUNK];
+            bool pos[EVB_CHUNK];
+#pragma unroll
+            for (int u = 0; u < EVB_CHUNK; ++u) {
+                w[u] = 0; pos[u] = false;
+                if (i0 + u < s1) w[u] = evb_cell(labels_sorted, img_sorted, weights, i0 + u, n_images, ldw, br, pos[u], bad);
+            }
+#pragma unroll
+            for (int u = 0; u < EVB_CHUNK; ++u) {
+                n += w[u];
+                if (pos[u] && w[u] > 0 && ngi > 0) {         // pos is uniform, w is the lane's
+                    tp += w[u];
+                    const double prec = (double)tp / (double)n, rec = (double)tp / ng;
+#pragma unroll
+                    for (int k = 0; k < 11; ++k)
+                        if (rec >= t[k] && prec > best[k]) best[k] = prec;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 11; ++k) result += best[k] / 11.0;       // the host meter's sequence
+    } else {
+        int64_t tp = 0, n = 0;                               // the class's totals in this replicate
+        for (int64_t i0 = s0; i0 < s1; i0 += EVB_CHUNK) {
+            int w[EVB_CHUNK];
+            bool pos[EVB_CHUNK];
+#pragma unroll
+            for (int u = 0; u < EVB_CHUNK; ++u) {
+                w[u] = 0; pos[u] = false;
+                if (i0 + u < s1) w[u] = evb_cell(labels_sorted, img_sorted, weights, i0 + u, n_images, ldw, br, pos[u], bad);
+            }
+#pragma unroll
+            for (int u = 0; u < EVB_CHUNK; ++u) { n += w[u]; if (pos[u]) tp += w[u]; }
+        }
+        double mx = 0.0, acc = 0.0;                          // suffix maximum of the precision; sum of w * label * maximum
+        for (int64_t e = s1; e > s0; e -= EVB_CHUNK) {       // from the end: position e - 1 - u
+            int w[EVB_CHUNK];
+            bool pos[EVB_CHUNK];
+#pragma unroll
+            for (int u = 0; u < EVB_CHUNK; ++u) {
+                w[u] = 0; pos[u] = false;
+                if (e - 1 - u >= s0) w[u] = evb_cell(labels_sorted, img_sorted, weights, e - 1 - u, n_images, ldw, br, pos[u], bad);
+            }
+#pragma unroll
+            for (int u = 0; u < EVB_CHUNK; ++u) {
+                if (pos[u] && w[u] > 0) {
+                    mx = fmax(mx, (double)tp / (double)n);
+                    const double term = (double)w[u] * mx;   // rounded on its own (-ffp-contract=off), then added
+                    acc += term;
+                    tp -= w[u];
+                }
+                n -= w[u];
+            }
+        }
+        result = ngi > 0 ? acc / ng : 0.0;
+    }
+    if (bad && threadIdx.x == 0) atomicMax(status, 1);
+    if (live) ap[(int64_t)b * n_classes + c] = result;       // also 0 for a class without cells or without ground truth
+}
+
+extern "C" int skg_eval_ap_boot_f64(const float* labels_sorted, const int32_t* img_sorted, const int64_t* class_off,
+                                    int64_t n_cells, int n_classes, const uint8_t* weights, int n_images, int n_boot,
+                                    int64_t ldw, const int64_t* num_gt_boot, int algorithm, const double* thresholds11,
+                                    double* ap, int32_t* status, void* stream) {
+    if (n_classes < 0 || n_cells < 0 || n_boot < 1 || n_images < 0 || ldw < n_boot) return SKG_E_ARG;
+    if (algorithm != SKG_AP_11P && algorithm != SKG_AP_AUC) return SKG_E_ARG;
+    if (algorithm == SKG_AP_11P && !thresholds11) return SKG_E_ARG;
+    if (!class_off || !num_gt_boot || !ap || !status) return SKG_E_ARG;
+    if (n_cells > 0 && (!labels_sorted || !img_sorted || !weights)) return SKG_E_ARG;
+    if ((n_boot + 63) / 64 > 65535) return SKG_E_LIMIT;
+    if (n_classes == 0 || n_cells == 0) return 0;            // nothing to rank: nothing launched, ap stays the caller's
+    const dim3 grid(n_classes, (n_boot + 63) / 64);
+    if (algorithm == SKG_AP_11P)
+        hipLaunchKernelGGL(skg_eval_ap_boot_kernel<0>, grid, dim3(64), 0, (hipStream_t)stream, labels_sorted, img_sorted,
+                           class_off, n_cells, n_classes, weights, n_images, n_boot, ldw, num_gt_boot, thresholds11, ap, status);
+    else
+        hipLaunchKernelGGL(skg_eval_ap_boot_kernel<1>, grid, dim3(64), 0, (hipStream_t)stream, labels_sorted, img_sorted,
+                           class_off, n_cells, n_classes, weights, n_images, n_boot, ldw, num_gt_boot, thresholds11, ap, status);
     return skg_launch_status();
 }

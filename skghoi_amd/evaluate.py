@@ -17,6 +17,8 @@ The detections behind the head (hicodet/detections/eval_detections.py: object-de
 kept boxes, generate_gt_detections.py) are judged by DetectionEvaluator / DeviceDetectionEvaluator, which add pair coverage.
 pair_nms / pair_nms_keep suppress duplicate (human, object, class) triplets among the scored cells of an image before they reach
 an evaluator or an exporter (skg_hoi_pair_nms_u8) -- opt-in, the published PNMS idea restated, not the reference's.
+The two HOI evaluators give confidence intervals of their means by a paired image-level bootstrap (`bootstrap=`;
+skg_eval_ap_boot_f64, bootstrap_weights / bootstrap_compare / format_bootstrap) -- opt-in, this project's own definition.
 
 Everything works on whatever device the result tensors live on (the association is a handful of small IoU matrices);
 nothing here is on the timed hot path.
@@ -137,6 +139,23 @@ class DetectionAPMeter:
 _THR11 = {}                                                      # device -> the eleven recall thresholds of '11P' (float64)
 
 
+def _thr11(dev):
+    if dev not in _THR11:
+        _THR11[dev] = torch.linspace(0, 1, 11, dtype=torch.float64).to(dev)
+    return _THR11[dev]
+
+
+def _rank_by_class(scores, classes, num_cls):
+    """The one ranking of the evaluators: two stable sorts -- score descending, then class ascending on top of it, so equal
+    scores of a class stay in arrival order.  Returns (order [L] int64: the cells in ranked order, class_off [num_cls + 1]
+    int64: the range of every class in it), on the tensors' device."""
+    o1 = torch.sort(scores, descending=True, stable=True).indices          # score descending, arrival order on ties
+    o2 = torch.sort(classes[o1], stable=True).indices                      # ... then class ascending, order kept
+    class_off = torch.zeros(num_cls + 1, dtype=torch.int64, device=scores.device)
+    class_off[1:] = torch.cumsum(torch.bincount(classes, minlength=num_cls), 0)
+    return o1[o2], class_off
+
+
 def _class_aps_device(algorithm, scores, classes, labels, num_cls, num_gt):
     """The ranking of every device evaluator: (scores, classes int64 in [0, num_cls), 0/1 labels) of the detections in
     arrival order and num_gt [num_cls] int64, all on one device -> the per-class APs, float64 [num_cls] on that device.
@@ -149,21 +168,243 @@ def _class_aps_device(algorithm, scores, classes, labels, num_cls, num_gt):
     ap = torch.zeros(num_cls, dtype=torch.float64, device=dev)
     if scores.numel() == 0 or num_cls == 0:
         return ap
-    o1 = torch.sort(scores, descending=True, stable=True).indices          # score descending, arrival order on ties
-    o2 = torch.sort(classes[o1], stable=True).indices                      # ... then class ascending, order kept
-    lab_sorted = labels[o1[o2]].float().contiguous()
-    class_off = torch.zeros(num_cls + 1, dtype=torch.int64, device=dev)
-    class_off[1:] = torch.cumsum(torch.bincount(classes, minlength=num_cls), 0)
+    order, class_off = _rank_by_class(scores, classes, num_cls)
+    lab_sorted = labels[order].float().contiguous()
     if algorithm == "AUC":
         _capi.check(_capi.lib().skg_eval_ap_voc_f64(lab_sorted.data_ptr(), class_off.data_ptr(), num_gt.data_ptr(),
                                                     num_cls, ap.data_ptr(), _stream()), "skg_eval_ap_voc_f64")
     else:
-        if dev not in _THR11:
-            _THR11[dev] = torch.linspace(0, 1, 11, dtype=torch.float64).to(dev)
         _capi.check(_capi.lib().skg_eval_ap11_f64(lab_sorted.data_ptr(), class_off.data_ptr(), num_gt.data_ptr(),
-                                                  num_cls, _THR11[dev].data_ptr(), ap.data_ptr(), _stream()),
+                                                  num_cls, _thr11(dev).data_ptr(), ap.data_ptr(), _stream()),
                     "skg_eval_ap11_f64")
     return ap
+
+
+# ----------------------------------------------------------------------------------------------- bootstrap intervals
+# Confidence intervals of the mAP by a paired image-level bootstrap (`bootstrap=` of the two HOI evaluators).  Not part of the
+# reference, which prints point estimates only -- this project's own definition (the percentile bootstrap over images); the
+# rule is stated in include/skghoi.h (skg_eval_ap_boot_f64) and the code below follows it.  The ranking is shared by all
+# replicates: the cells are sorted once, a replicate is a weighted walk over the same order.
+_BOOT_KEYS = ("n_boot", "seed", "n_images", "level", "replicates", "ap_std", "undefined_share", "known_object", "bootstrap")
+_BOOT_GT_ROWS = 4096             # ground-truth pairs per index_add_ of num_gt_boot (bounds the [rows, n_boot] int64 temporary)
+
+
+def bootstrap_weights(n_images, n_boot, seed=0):
+    """uint8 [n_images, n_boot], replicate index fastest: column b holds how often each image is drawn in replicate b --
+    bincount(torch.randint(n_images, (n_images,), generator=g), minlength=n_images) for b = 0 .. n_boot - 1 in order from
+    g = torch.Generator().manual_seed(seed), the function's own CPU generator (the global one, which the head's TransH draws
+    use, does not move).  Columns sum to n_images.  A count above 255 raises OverflowError."""
+    n_images, n_boot = int(n_images), int(n_boot)
+    if n_images < 0 or n_boot < 1:
+        raise ValueError("bootstrap_weights needs n_images >= 0 and n_boot >= 1")
+    w = torch.zeros(n_images, n_boot, dtype=torch.uint8)
+    if n_images == 0:
+        return w
+    g = torch.Generator().manual_seed(int(seed))
+    for b in range(n_boot):
+        col = torch.bincount(torch.randint(n_images, (n_images,), generator=g), minlength=n_images)
+        if int(col.max()) > 255:
+            raise OverflowError("image drawn %d times in replicate %d; the weights are uint8" % (int(col.max()), b))
+        w[:, b] = col.to(torch.uint8)
+    return w
+
+
+def _check_bootstrap(bootstrap, splits):
+    """`bootstrap=` of the HOI evaluators -> None or dict(n_boot, seed, level)."""
+    if bootstrap is None:
+        return None
+    cfg = dict(bootstrap) if isinstance(bootstrap, dict) else dict(n_boot=bootstrap)
+    unknown = set(cfg) - {"n_boot", "seed", "level"}
+    if unknown or "n_boot" not in cfg:
+        raise ValueError("bootstrap is None, an int n_boot or dict(n_boot=, seed=0, level=0.95)")
+    if isinstance(cfg["n_boot"], bool) or int(cfg["n_boot"]) != cfg["n_boot"] or int(cfg["n_boot"]) < 1:
+        raise ValueError("bootstrap: n_boot must be a positive integer")
+    out = dict(n_boot=int(cfg["n_boot"]), seed=int(cfg.get("seed", 0)), level=float(cfg.get("level", 0.95)))
+    if not 0.0 < out["level"] < 1.0:
+        raise ValueError("bootstrap: level must lie in (0, 1)")
+    for name in splits:
+        if name in _BOOT_KEYS:
+            raise ValueError("the split name %r collides with a key of summary()['bootstrap']" % (name,))
+    return out
+
+
+def _class_aps_boot_host(algorithm, lab_sorted, img_sorted, class_off, num_gt_boot, weights):
+    """The rule of skg_eval_ap_boot_f64 restated on host tensors, one class at a time over [L_c, n_boot] running sums."""
+    n_boot = weights.shape[1]
+    num_cls = class_off.numel() - 1
+    ap = torch.zeros(n_boot, num_cls, dtype=torch.float64)
+    thr = torch.linspace(0, 1, 11, dtype=torch.float64)
+    off = class_off.tolist()
+    for c in range(num_cls):
+        s0, s1 = off[c], off[c + 1]
+        if s1 <= s0:
+            continue
+        w = weights[img_sorted[s0:s1].long()].long()                               # [L_c, n_boot]
+        wl = w * (lab_sorted[s0:s1] != 0).long()[:, None]
+        tp = torch.cumsum(wl, 0); n = torch.cumsum(w, 0)
+        there = w > 0                                                              # positions with w == 0 do not exist
+        prec = torch.where(there, tp.double() / n.clamp(min=1).double(), torch.zeros((), dtype=torch.float64))
+        ng = num_gt_boot[c]                                                        # [n_boot]
+        has_gt = ng > 0
+        ngd = ng.clamp(min=1).double()
+        if algorithm == "AUC":
+            sufmax = torch.flip(torch.cummax(torch.flip(prec, [0]), 0).values, [0])
+            val = (wl.double() * sufmax).sum(0) / ngd
+        else:
+            rec = tp.double() / ngd
+            val = torch.zeros(n_boot, dtype=torch.float64)
+            for k in range(11):
+                m = there & (rec >= thr[k])
+                val = val + torch.where(m, prec, torch.zeros((), dtype=torch.float64)).max(0).values / 11
+        ap[:, c] = torch.where(has_gt, val, torch.zeros((), dtype=torch.float64))
+    return ap
+
+
+def _class_aps_boot_device(algorithm, scores, classes, labels, img, num_cls, gt_cls, gt_img, weights):
+    """The per-class APs of every bootstrap replicate over the ranking of _class_aps_device: (scores, classes int64 in
+    [0, num_cls), 0/1 labels, img = the image id of every cell) in arrival order, (gt_cls, gt_img) = class and image id of
+    every ground-truth pair (classes outside [0, num_cls) are ignored), weights uint8 [n_images, n_boot] (bootstrap_weights),
+    all on one device.  Returns (ap_boot float64 [n_boot, num_cls], num_gt_boot int64 [num_cls, n_boot]) on that device.
+    num_gt_boot is an integer index_add_ of weight rows (deterministic); then the same two stable sorts and ONE launch,
+    skg_eval_ap_boot_f64.  On CPU tensors the vectorised host restatement runs instead (_class_aps_boot_host).  An image id
+    outside the weights raises IndexError."""
+    dev = scores.device
+    n_images, n_boot = weights.shape
+    gt_cls = gt_cls.long(); gt_img = gt_img.long()
+    ok = (gt_cls >= 0) & (gt_cls < num_cls)
+    gt_cls, gt_img = gt_cls[ok], gt_img[ok]
+    if gt_img.numel() and (int(gt_img.min()) < 0 or int(gt_img.max()) >= n_images):
+        raise IndexError("a ground-truth pair's image id is outside the %d images of the weights" % n_images)
+    num_gt_boot = torch.zeros(num_cls, n_boot, dtype=torch.int64, device=dev)
+    for r in range(0, gt_cls.numel(), _BOOT_GT_ROWS):
+        num_gt_boot.index_add_(0, gt_cls[r:r + _BOOT_GT_ROWS], weights[gt_img[r:r + _BOOT_GT_ROWS]].long())
+    ap = torch.zeros(n_boot, num_cls, dtype=torch.float64, device=dev)
+    if scores.numel() == 0 or num_cls == 0:
+        return ap, num_gt_boot
+    order, class_off = _rank_by_class(scores, classes, num_cls)
+    lab_sorted = labels[order].float().contiguous()
+    img_sorted = img[order].to(torch.int32).contiguous()
+    if dev.type != "cuda":
+        if int(img_sorted.min()) < 0 or int(img_sorted.max()) >= n_images:
+            raise IndexError("a cell's image id is outside the %d images of the weights" % n_images)
+        return _class_aps_boot_host(algorithm, lab_sorted, img_sorted, class_off, num_gt_boot, weights), num_gt_boot
+    from . import _capi
+    from .engine import _stream
+    weights = weights.contiguous()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    thr = _thr11(dev)
+    _capi.check(_capi.lib().skg_eval_ap_boot_f64(
+        lab_sorted.data_ptr(), img_sorted.data_ptr(), class_off.data_ptr(), lab_sorted.numel(), num_cls, weights.data_ptr(),
+        n_images, n_boot, n_boot, num_gt_boot.data_ptr(), _capi.AP_AUC if algorithm == "AUC" else _capi.AP_11P, thr.data_ptr(),
+        ap.data_ptr(), status.data_ptr(), _stream()), "skg_eval_ap_boot_f64")
+    if int(status.item()):
+        raise IndexError("a cell's image id is outside the %d images of the weights" % n_images)
+    return ap, num_gt_boot
+
+
+def _nan_std(x):
+    """Sample standard deviation over dim 0 of a float64 tensor, NaN entries left out; NaN where fewer than two remain."""
+    there = ~torch.isnan(x)
+    cnt = there.sum(0).double()
+    zero = torch.zeros((), dtype=torch.float64)
+    mean = torch.where(there, x, zero).sum(0) / cnt
+    dev2 = torch.where(there, (x - mean) ** 2, zero).sum(0)
+    return torch.where(cnt > 1, (dev2 / (cnt - 1).clamp(min=1)).sqrt(), torch.full((), float("nan"), dtype=torch.float64))
+
+
+def _bootstrap_stats(ap_boot, num_gt_boot, num_gt, num_anno_train, splits, level):
+    """The part of summary()["bootstrap"] that depends on the cells (also its `known_object` block), from host tensors:
+    ap_boot [n_boot, num_cls] float64, num_gt_boot [num_cls, n_boot] and num_gt [num_cls] int64.  Class c is defined in
+    replicate b iff num_gt_boot[c, b] > 0 or num_gt[c] == 0; a replicate's mean runs over the defined classes of a list."""
+    n_boot, num_cls = ap_boot.shape
+    defined = (num_gt_boot.t() > 0) | (num_gt == 0)[None]
+    lists = {"full": torch.arange(num_cls)}
+    if num_anno_train is not None:
+        lists["rare"] = torch.nonzero(num_anno_train < 10).squeeze(1)
+        lists["non_rare"] = torch.nonzero(num_anno_train >= 10).squeeze(1)
+    lists.update(splits)
+    q = torch.tensor([(1 - level) / 2, 1 - (1 - level) / 2], dtype=torch.float64)
+    out, replicates, undefined = {}, {}, {}
+    for key, idx in lists.items():
+        d = defined[:, idx]
+        rep = torch.full((n_boot,), float("nan"), dtype=torch.float64)
+        for b in range(n_boot):                                  # the point estimate's own operation, per replicate
+            if bool(d[b].any()):
+                rep[b] = ap_boot[b, idx[d[b]]].mean()
+        replicates[key] = rep
+        undefined[key] = float(1.0 - d.double().mean()) if d.numel() else float("nan")
+        if bool(torch.isnan(rep).all()):
+            lo = hi = mean = float("nan")
+        else:
+            lo, hi = (float(v) for v in torch.nanquantile(rep, q))
+            mean = float(torch.nanmean(rep))
+        out[key] = dict(mean=mean, std=float(_nan_std(rep)), lo=lo, hi=hi)
+    out["replicates"] = replicates
+    out["ap_std"] = _nan_std(torch.where(defined, ap_boot, torch.full((), float("nan"), dtype=torch.float64)))
+    out["undefined_share"] = undefined
+    return out
+
+
+def _check_gt_counts(gt_cls, num_gt, num_cls):
+    """The unit-weight replicate is the point estimate only if num_gt_test is what the targets hold: ValueError otherwise."""
+    gt_cls = gt_cls.long().cpu()
+    counts = torch.bincount(gt_cls[(gt_cls >= 0) & (gt_cls < num_cls)], minlength=num_cls)
+    diff = torch.nonzero(counts != num_gt).reshape(-1)
+    if diff.numel():
+        c = int(diff[0])
+        raise ValueError("bootstrap: class %d has %d ground-truth pairs in the targets passed to add() and %d in num_gt_test; "
+                         "add every test image (also those without detections) or pass the counts of the images added"
+                         % (c, int(counts[c]), int(num_gt[c])))
+
+
+def bootstrap_compare(summary_a, summary_b, key="full", known_object=False):
+    """Paired comparison of two runs from their summaries with `bootstrap`: the replicate-wise differences a - b of `key`
+    (full / rare / non_rare / a named split; known_object=True: of the Known Object blocks).  The two runs must have added
+    the SAME images in the SAME order with the same n_boot and seed -- then replicate b resamples the same images in both, and
+    the resampling noise the runs share cancels in the difference.  Only n_boot, seed and n_images can be checked here
+    (ValueError); the order of the images is the caller's.
+    Returns dict(delta = point a - point b, mean, lo, hi = percentiles of the differences at summary_a's level,
+    p_a_better = the share of replicates with a difference > 0 plus half the ties); replicates where either side is undefined
+    (NaN) are left out."""
+    ba, bb = summary_a.get("bootstrap"), summary_b.get("bootstrap")
+    if ba is None or bb is None:
+        raise ValueError("bootstrap_compare needs two summaries of evaluators built with bootstrap=")
+    for k in ("n_boot", "seed", "n_images"):
+        if ba[k] != bb[k]:
+            raise ValueError("bootstrap_compare: %s differs (%r against %r): the replicates are not paired" % (k, ba[k], bb[k]))
+    pa, pb, ra, rb = summary_a, summary_b, ba, bb
+    if known_object:
+        if "known_object" not in ba or "known_object" not in bb:
+            raise ValueError("bootstrap_compare: a summary has no known_object block")
+        pa, pb, ra, rb = summary_a["known_object"], summary_b["known_object"], ba["known_object"], bb["known_object"]
+    if key not in ra["replicates"] or key not in rb["replicates"]:
+        raise ValueError("bootstrap_compare: no replicates of %r in both summaries" % (key,))
+    d = ra["replicates"][key] - rb["replicates"][key]
+    d = d[~torch.isnan(d)]
+    level = ba["level"]
+    if d.numel() == 0:
+        return dict(delta=pa[key] - pb[key], mean=float("nan"), lo=float("nan"), hi=float("nan"), p_a_better=float("nan"))
+    lo, hi = (float(v) for v in torch.quantile(d, torch.tensor([(1 - level) / 2, 1 - (1 - level) / 2], dtype=torch.float64)))
+    better = (float((d > 0).sum()) + 0.5 * float((d == 0).sum())) / d.numel()
+    return dict(delta=pa[key] - pb[key], mean=float(d.mean()), lo=lo, hi=hi, p_a_better=better)
+
+
+def format_bootstrap(summary):
+    """The `bootstrap` entry of an HOI evaluator's summary() as text: per key the point estimate, the mean, standard deviation
+    and percentile interval of the replicates, and the mean share of classes undefined in a replicate."""
+    bs = summary["bootstrap"]
+    lines = ["bootstrap over %d images, %d replicates, seed %d, %g%% percentile intervals"
+             % (bs["n_images"], bs["n_boot"], bs["seed"], 100.0 * bs["level"])]
+    for title, point, block in (("Default", summary, bs), ("Known Object", summary.get("known_object"), bs.get("known_object"))):
+        if block is None:
+            continue
+        lines.append("%s setting" % title)
+        lines.append("  %-20s %8s %8s %8s %8s %8s %10s" % ("key", "point", "mean", "std", "lo", "hi", "undefined"))
+        for key in block["replicates"]:
+            s = block[key]
+            lines.append("  %-20s %8.4f %8.4f %8.4f %8.4f %8.4f %9.1f%%" % (key, point[key], s["mean"], s["std"], s["lo"], s["hi"],
+                                                                            100.0 * block["undefined_share"][key]))
+    return "\n".join(lines)
 
 
 def _offset_table(device, *counts):
@@ -364,10 +605,20 @@ class HOIEvaluator:
     `categories` / `gt_statuses` (the names), `cells` [num_cls, 6] / `cells_total`, `gt` [num_cls, 4] / `gt_total` (int64
     counts), `ap_without` {duplicate, verb, object, human, background, all_fp: float64 [num_cls]} -- the same AP, num_gt,
     labels and order over the cells that are not of that category -- `map_without` (their means) and `delta_map` =
-    map_without - full.  It composes with known_object / splits and leaves their output as it is."""
+    map_without - full.  It composes with known_object / splits and leaves their output as it is.
+
+    bootstrap=None | n_boot | dict(n_boot=, seed=0, level=0.95): confidence intervals of the means by a paired image-level
+    percentile bootstrap (this project's own definition, not the reference's; the rule is stated in include/skghoi.h,
+    skg_eval_ap_boot_f64).  Every call of `add` is one image, numbered in `add` order; `add` also keeps the image id of every
+    cell and the (class, image) of every ground-truth pair, and `summary()["bootstrap"]` holds n_boot, seed, n_images, level,
+    per key (full, rare, non_rare, every named split) {mean, std, lo, hi} of the replicate means, `replicates` {key: float64
+    [n_boot]}, `ap_std` [num_cls], `undefined_share` {key: the mean share of classes without ground truth in a replicate, which
+    its mean leaves out}, and with known_object=True a `known_object` block of the same shape.  num_gt_test must be what the
+    added targets hold (add every test image, also those without detections): ValueError from summary() otherwise.  The error
+    breakdown is not bootstrapped.  None: the summary, the stored state and the work are what they were."""
 
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, algorithm="11P",
-                 known_object=False, splits=None, errors=False):
+                 known_object=False, splits=None, errors=False, bootstrap=None):
         self.lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
             else hico_object_n_verb_to_interaction()
         num_cls = int(self.lut.max()) + 1
@@ -377,6 +628,9 @@ class HOIEvaluator:
         self.splits = _check_splits(splits, num_cls)
         self.known_object = bool(known_object)
         self.errors = bool(errors)
+        self.bootstrap = _check_bootstrap(bootstrap, self.splits)
+        if self.bootstrap is not None:
+            self._boot_cells, self._boot_gt, self._boot_images = [], [], 0      # (scores, classes, labels, keep), classes
         if self.known_object or self.errors:
             self.hoi_object = hoi_object_of(self.lut)
         if self.known_object:
@@ -460,6 +714,11 @@ class HOIEvaluator:
             self._err_cells.append((scores.reshape(-1), inter.reshape(-1), labels.reshape(-1), cat))
             self._err_gt.append((t_hoi.reshape(-1).long(), status))
             self.last_category, self.last_gt_status = [cat], [status]
+        if self.bootstrap is not None:                               # this image is number self._boot_images
+            self._boot_cells.append((scores.reshape(-1), inter.reshape(-1), labels.reshape(-1),
+                                     keep.reshape(-1) if self.known_object else None))
+            self._boot_gt.append(t_hoi.reshape(-1).long())
+            self._boot_images += 1
         return labels
 
     def _errors_block(self, full):
@@ -479,12 +738,36 @@ class HOIEvaluator:
             ap_without[name] = meter.eval()
         return _errors_summary(cells, gt, ap_without, full)
 
+    def _bootstrap_block(self):
+        """summary()["bootstrap"]: the rule of include/skghoi.h through the host restatement, over this evaluator's log."""
+        cfg, num_cls, n = self.bootstrap, self.meter.num_cls, self._boot_images
+        num_gt = torch.as_tensor(self.meter.num_gt, dtype=torch.int64)
+        cat_of = lambda k, dtype: torch.cat([p[k].cpu() for p in self._boot_cells]) if n else torch.zeros(0, dtype=dtype)
+        scores = cat_of(0, torch.float32).float(); inter = cat_of(1, torch.int64); labels = cat_of(2, torch.float32)
+        img = torch.repeat_interleave(torch.arange(n), torch.tensor([p[0].numel() for p in self._boot_cells], dtype=torch.int64))
+        gt_cls = torch.cat([g.cpu() for g in self._boot_gt]) if n else torch.zeros(0, dtype=torch.int64)
+        gt_img = torch.repeat_interleave(torch.arange(n), torch.tensor([g.numel() for g in self._boot_gt], dtype=torch.int64))
+        _check_gt_counts(gt_cls, num_gt, num_cls)
+        weights = bootstrap_weights(n, cfg["n_boot"], cfg["seed"])
+        algorithm = self.meter.algorithm
+        ap_boot, ngb = _class_aps_boot_device(algorithm, scores, inter, labels, img, num_cls, gt_cls, gt_img, weights)
+        out = dict(n_boot=cfg["n_boot"], seed=cfg["seed"], n_images=n, level=cfg["level"])
+        out.update(_bootstrap_stats(ap_boot, ngb, num_gt, self.num_anno_train, self.splits, cfg["level"]))
+        if self.known_object:                                        # the same weights and num_gt_boot over the kept cells
+            keep = cat_of(3, torch.bool).bool()
+            ap_ko, _ = _class_aps_boot_device(algorithm, scores[keep], inter[keep], labels[keep], img[keep], num_cls, gt_cls,
+                                              gt_img, weights)
+            out["known_object"] = _bootstrap_stats(ap_ko, ngb, num_gt, self.num_anno_train, self.splits, cfg["level"])
+        return out
+
     def summary(self):
         out = _hoi_summary(self.meter.eval(), self.num_anno_train, self.splits)
         if self.known_object:
             out["known_object"] = _hoi_summary(self.ko_meter.eval(), self.num_anno_train, self.splits)
         if self.errors:
             out["errors"] = self._errors_block(out["full"])
+        if self.bootstrap is not None:
+            out["bootstrap"] = self._bootstrap_block()
         return out
 
 
@@ -499,11 +782,14 @@ class DeviceHOIEvaluator:
     end the same ranking a second time, over the kept cells.  errors=True (as for HOIEvaluator) adds one
     skg_eval_hoi_errors_u8 launch per `add`, behind the association on its hoi_out and final labels and without a host
     synchronisation (`last_category` / `last_gt_status`: per-image uint8 views of two device tensors), and at the end the same
-    ranking six more times, each over the cells that are not of one category."""
+    ranking six more times, each over the cells that are not of one category.  bootstrap= (as for HOIEvaluator; the images of
+    every `add` are numbered in order) adds no launch and no synchronisation to `add` -- the ids come from counts the host
+    holds -- and at the end one skg_eval_ap_boot_f64 launch over the same ranking (two with known_object): every replicate is a
+    weighted walk over the cells sorted once."""
     batched = True                                               # trainer.test feeds lists
 
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, device="cuda",
-                 algorithm="11P", known_object=False, splits=None, errors=False):
+                 algorithm="11P", known_object=False, splits=None, errors=False, bootstrap=None):
         from . import _capi
         self.algorithm = _check_algorithm(algorithm)             # "AUC": the 600 APs by skg_eval_ap_voc_f64
         self.device = torch.device(device)
@@ -530,6 +816,9 @@ class DeviceHOIEvaluator:
         if self.errors:
             self._cat, self._gt_hoi, self._gt_status = [], [], []
             self.last_category, self.last_gt_status = [], []
+        self.bootstrap = _check_bootstrap(bootstrap, self.splits)
+        if self.bootstrap is not None:
+            self._boot_img, self._boot_gt, self._boot_images = [], [], 0      # image id per cell; (class, image id) per pair
 
     def add(self, outputs, targets):
         """outputs: the head's result dicts of a batch (HEAD:317-322); targets: per image {boxes_h, boxes_o, hoi}.
@@ -581,6 +870,12 @@ class DeviceHOIEvaluator:
                 self.min_iou, cat.data_ptr(), status.data_ptr(), _stream()), "skg_eval_hoi_errors_u8")
             self._cat.append(cat[:L]); self._gt_hoi.append(gt_hoi[:G]); self._gt_status.append(status[:G])
             self.last_category, self.last_gt_status = list(cat[:L].split(cpi)), list(status[:G].split(gts))
+        if self.bootstrap is not None:                               # ids from the counts the host holds: no launch of ours, no sync
+            ids = np.arange(self._boot_images, self._boot_images + n, dtype=np.int32)
+            G = int(sum(gts))                                        # (without ground truth gt_hoi is the padding row: none kept)
+            self._boot_img.append(torch.from_numpy(np.repeat(ids, cpi)).to(dev))
+            self._boot_gt.append((gt_hoi[:G], torch.from_numpy(np.repeat(ids, gts)).to(dev)))
+            self._boot_images += n
         return list(labels[:L].split(cpi))
 
     def summary(self):
@@ -615,6 +910,28 @@ class DeviceHOIEvaluator:
                     m = _without_mask(name, cat)
                     ap_without[name] = _class_aps_device(self.algorithm, scores[m], hoi[m], labels[m], nc, self.num_gt).cpu()
             out["errors"] = _errors_summary(cells, gt, ap_without, out["full"])
+        if self.bootstrap is not None:
+            cfg, nc, n = self.bootstrap, self.num_cls, self._boot_images
+            empty = lambda dtype: torch.zeros(0, dtype=dtype, device=dev)
+            gt_cls = torch.cat([g for g, _ in self._boot_gt]) if self._boot_gt else empty(torch.int64)
+            gt_img = torch.cat([i for _, i in self._boot_gt]) if self._boot_gt else empty(torch.int32)
+            num_gt = self.num_gt.cpu()
+            _check_gt_counts(gt_cls, num_gt, nc)
+            weights = bootstrap_weights(n, cfg["n_boot"], cfg["seed"]).to(dev)
+            if self._scores:
+                img = torch.cat(self._boot_img)
+            else:
+                scores, hoi, labels, img = empty(torch.float32), empty(torch.int64), empty(torch.float32), empty(torch.int32)
+            ap_boot, ngb = _class_aps_boot_device(self.algorithm, scores, hoi, labels, img, nc, gt_cls, gt_img, weights)
+            ngb = ngb.cpu()
+            bs = dict(n_boot=cfg["n_boot"], seed=cfg["seed"], n_images=n, level=cfg["level"])
+            bs.update(_bootstrap_stats(ap_boot.cpu(), ngb, num_gt, self.num_anno_train, self.splits, cfg["level"]))
+            if self.known_object:                                    # the same weights and num_gt_boot over the kept cells
+                if self._scores:
+                    scores, hoi, labels, img = scores[keep], hoi[keep], labels[keep], img[keep]
+                ap_ko, _ = _class_aps_boot_device(self.algorithm, scores, hoi, labels, img, nc, gt_cls, gt_img, weights)
+                bs["known_object"] = _bootstrap_stats(ap_ko.cpu(), ngb, num_gt, self.num_anno_train, self.splits, cfg["level"])
+            out["bootstrap"] = bs
         return out
 
 

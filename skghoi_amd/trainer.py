@@ -1507,7 +1507,9 @@ def test(net, test_loader, evaluator, device=None, lookahead=True, postprocess=N
     with the image's ground-truth pairs and logged into the 600-class 11-point meter; returns `evaluator.summary()`
     (`ap` per class, `full`, and `rare` / `non_rare` when the evaluator knows the training counts; one mean per named class
     list of the evaluator's `splits`; with `known_object=True` a `known_object` dict of the same keys, HICO-DET's second
-    setting; with `errors=True` an `errors` dict, the error breakdown of the Default setting).
+    setting; with `errors=True` an `errors` dict, the error breakdown of the Default setting; with `bootstrap=` a `bootstrap`
+    dict, confidence intervals of the means over resampled images -- the loop needs nothing for it, but every image of the
+    loader has to reach `evaluator.add`, and the global generator moves exactly as without it).
 
     test_loader yields batches whose LAST element is the list of targets ({boxes_h, boxes_o, hoi}) and whose other
     elements are the network's arguments -- for the bare interaction head (inference from cached features / detections):

@@ -81,7 +81,7 @@ def _check_algorithm(algorithm):
 class DetectionAPMeter:
     """pocket.utils.DetectionAPMeter(num_cls, num_gt=..., algorithm='11P'): per-class lists of (score, label),
     AP = mean over t in {0, 0.1, ..., 1} of max precision at recall >= t (float64); algorithm='AUC': the VOC all-point area.
-    The one AP implementation of the host: every host evaluator ranks through it (a class's detections score descending,
+    The one AP implementation of the host: _class_aps ranks CPU tensors through it (a class's detections score descending,
     equal scores in arrival order)."""
 
     def __init__(self, num_cls, num_gt=None, algorithm="11P"):
@@ -98,9 +98,11 @@ class DetectionAPMeter:
 
     def append(self, scores, classes, labels):
         scores = scores.detach().cpu().double(); classes = classes.detach().cpu().long(); labels = labels.detach().cpu().double()
-        for c in classes.unique().tolist():
-            m = classes == c
-            self._scores[c].append(scores[m]); self._labels[c].append(labels[m])
+        order = torch.sort(classes, stable=True).indices        # grouped by class, arrival order kept inside a class
+        cls, counts = torch.unique_consecutive(classes[order], return_counts=True)
+        counts = counts.tolist()
+        for c, s, l in zip(cls.tolist(), scores[order].split(counts), labels[order].split(counts)):
+            self._scores[c].append(s); self._labels[c].append(l)
 
     @staticmethod
     def _ap(scores, labels, num_gt, algorithm):
@@ -135,7 +137,7 @@ class DetectionAPMeter:
         return out
 
 
-# ----------------------------------------------------------------------------------------------- shared by the device evaluators
+# ----------------------------------------------------------------------------------------------- shared by the evaluators
 _THR11 = {}                                                      # device -> the eleven recall thresholds of '11P' (float64)
 
 
@@ -178,6 +180,40 @@ def _class_aps_device(algorithm, scores, classes, labels, num_cls, num_gt):
                                                   num_cls, _thr11(dev).data_ptr(), ap.data_ptr(), _stream()),
                     "skg_eval_ap11_f64")
     return ap
+
+
+def _class_aps(algorithm, scores, classes, labels, num_cls, num_gt):
+    """The one AP entry of the evaluators, with the contract of _class_aps_device, on whichever device the tensors live:
+    CUDA tensors go through _class_aps_device, CPU tensors through DetectionAPMeter (float64 [num_cls] on the host)."""
+    if scores.device.type == "cuda":
+        return _class_aps_device(algorithm, scores, classes, labels, num_cls, num_gt)
+    meter = DetectionAPMeter(num_cls, num_gt=num_gt, algorithm=algorithm)
+    meter.append(scores, classes, labels)
+    return meter.eval()
+
+
+class _Log:
+    """What an evaluator keeps between `add` and `summary()`: named columns, each a list of per-`add` tensors on one device
+    (a host evaluator's log lives on the CPU, a device evaluator's keeps the device views it is given: no copy, no
+    synchronisation).  A column exists only if the option that needs it is on; per-cell and per-pair columns grow
+    independently.  `column(name)` is the whole column as one contiguous tensor, empty of the column's dtype if nothing was
+    appended."""
+
+    def __init__(self, device, **dtypes):
+        self.device = torch.device(device)
+        self.dtypes = dtypes
+        self.parts = {name: [] for name in dtypes}
+
+    def __contains__(self, name):
+        return name in self.parts
+
+    def append(self, **tensors):
+        for name, t in tensors.items():
+            self.parts[name].append(t.detach().to(self.device))
+
+    def column(self, name):
+        parts = self.parts[name]
+        return torch.cat(parts) if parts else torch.zeros(0, dtype=self.dtypes[name], device=self.device)
 
 
 # ----------------------------------------------------------------------------------------------- bootstrap intervals
@@ -478,10 +514,6 @@ class DeviceAPMeter:
             mine = torch.cat(_all_gather_ragged(mine.contiguous(), self.group))
         if mine.shape[0] == 0:
             return torch.zeros(self.num_cls, dtype=torch.float64)
-        if dev.type != "cuda":                                  # (CPU tensors: rehearsals over gloo) the host meter
-            m = DetectionAPMeter(self.num_cls, self.num_gt, self.algorithm)
-            m.append(mine[:, 0], mine[:, 1].long(), mine[:, 2])
-            return m.eval()
         scores, cls, labels = mine[:, 0].contiguous(), mine[:, 1].long(), mine[:, 2].contiguous()
         if ((cls < 0) | (cls >= self.num_cls)).any():
             raise IndexError("a logged prediction is outside [0, %d)" % self.num_cls)
@@ -489,7 +521,7 @@ class DeviceAPMeter:
             num_gt = torch.zeros(self.num_cls, device=dev, dtype=torch.float64).index_add_(0, cls, labels.double()).long()
         else:
             num_gt = torch.as_tensor(self.num_gt, dtype=torch.int64, device=dev)
-        return _class_aps_device(self.algorithm, scores, cls, labels, self.num_cls, num_gt).cpu()
+        return _class_aps(self.algorithm, scores, cls, labels, self.num_cls, num_gt).cpu()     # (CPU tensors: rehearsals over gloo)
 
 
 # ----------------------------------------------------------------------------------------------- HICO-DET settings
@@ -590,7 +622,94 @@ def _hoi_summary(ap, num_anno_train, splits):
     return out
 
 
-class HOIEvaluator:
+class _HOIEvaluatorBase:
+    """What HOIEvaluator and DeviceHOIEvaluator share: the constructor's checks, the log and `summary()`, written once over
+    the log on whichever device it lives.  The two differ in `add` only -- the torch restatement of the rule against the kernel
+    launches -- and in `_check_log`.  Log columns: scores, hoi, labels per cell; keep (known_object), category (errors), img
+    (bootstrap) per cell; gt_hoi (errors or bootstrap), gt_status (errors), gt_img (bootstrap) per ground-truth pair."""
+
+    def __init__(self, num_gt_test, object_n_verb_to_interaction, min_iou, num_anno_train, device, algorithm, known_object,
+                 splits, errors, bootstrap):
+        self.algorithm = _check_algorithm(algorithm)             # "AUC": the VOC all-point area (DetectionAPMeter's branch)
+        self.device = torch.device(device)
+        self.lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
+            else hico_object_n_verb_to_interaction()
+        self.num_cls = int(self.lut.max()) + 1
+        self.num_gt = torch.as_tensor([int(v) for v in num_gt_test], dtype=torch.int64, device=self.device)
+        self.min_iou = float(min_iou)
+        self.num_anno_train = None if num_anno_train is None else torch.as_tensor(num_anno_train)
+        self.splits = _check_splits(splits, self.num_cls)
+        self.known_object = bool(known_object)
+        self.errors = bool(errors)
+        self.bootstrap = _check_bootstrap(bootstrap, self.splits)
+        columns = dict(scores=torch.float32, hoi=torch.int64, labels=torch.float32)
+        if self.known_object or self.errors:
+            self.hoi_object = hoi_object_of(self.lut)
+        if self.known_object:
+            columns["keep"] = torch.bool
+            self.last_keep = []
+        if self.errors:
+            columns.update(category=torch.uint8, gt_status=torch.uint8)
+            self.last_category, self.last_gt_status = [], []
+        if self.bootstrap is not None:                               # images are numbered in `add` order
+            columns.update(img=torch.int64, gt_img=torch.int64)
+            self._boot_images = 0
+        if self.errors or self.bootstrap is not None:                # one ground-truth class column for both
+            columns["gt_hoi"] = torch.int64
+        self.log = _Log(self.device, **columns)
+
+    def _check_log(self, hoi):
+        """What a device evaluator can only report at summary() time; the host evaluator raises in `add`."""
+
+    def summary(self):
+        log, nc = self.log, self.num_cls
+        scores, hoi, labels = log.column("scores"), log.column("hoi").long(), log.column("labels")
+        self._check_log(hoi)
+
+        def aps(mask=None):                                          # the same rule over a mask: the cells' order kept
+            cells = (scores, hoi, labels) if mask is None else (scores[mask], hoi[mask], labels[mask])
+            return _class_aps(self.algorithm, *cells, nc, self.num_gt).cpu()
+        out = _hoi_summary(aps(), self.num_anno_train, self.splits)
+        if self.known_object:
+            keep = log.column("keep").bool()
+            out["known_object"] = _hoi_summary(aps(keep), self.num_anno_train, self.splits)
+        if self.errors:
+            out["errors"] = self._errors_block(aps, hoi, out["full"])
+        if self.bootstrap is not None:
+            out["bootstrap"] = self._bootstrap_block(scores, hoi, labels, keep if self.known_object else None)
+        return out
+
+    def _errors_block(self, aps, hoi, full):
+        """summary()["errors"]: the counts by bincount, ap_without by `aps` over the cells that are not of a category."""
+        log, nc = self.log, self.num_cls
+        cat = log.column("category").long()
+        cells = torch.bincount(hoi * 6 + cat, minlength=nc * 6).reshape(nc, 6).cpu()
+        t, status = log.column("gt_hoi"), log.column("gt_status").long()
+        ok = status != 255
+        gt = torch.bincount(t[ok] * 4 + status[ok], minlength=nc * 4).reshape(nc, 4).cpu()
+        return _errors_summary(cells, gt, {name: aps(_without_mask(name, cat)) for name in _AP_WITHOUT}, full)
+
+    def _bootstrap_block(self, scores, hoi, labels, keep):
+        """summary()["bootstrap"]: the rule of include/skghoi.h over the log -- on the device one skg_eval_ap_boot_f64 launch
+        over the point estimate's ranking (two with known_object), on the host its restatement."""
+        log, cfg, nc, n = self.log, self.bootstrap, self.num_cls, self._boot_images
+        img, gt_cls, gt_img = log.column("img"), log.column("gt_hoi"), log.column("gt_img")
+        num_gt = self.num_gt.cpu()
+        _check_gt_counts(gt_cls, num_gt, nc)
+        weights = bootstrap_weights(n, cfg["n_boot"], cfg["seed"]).to(self.device)
+        stats = lambda ap: _bootstrap_stats(ap.cpu(), ngb, num_gt, self.num_anno_train, self.splits, cfg["level"])
+        ap_boot, ngb = _class_aps_boot_device(self.algorithm, scores, hoi, labels, img, nc, gt_cls, gt_img, weights)
+        ngb = ngb.cpu()
+        out = dict(n_boot=cfg["n_boot"], seed=cfg["seed"], n_images=n, level=cfg["level"])
+        out.update(stats(ap_boot))
+        if keep is not None:                                         # the same weights and num_gt_boot over the kept cells
+            ap_ko, _ = _class_aps_boot_device(self.algorithm, scores[keep], hoi[keep], labels[keep], img[keep], nc, gt_cls,
+                                              gt_img, weights)
+            out["known_object"] = stats(ap_ko)
+        return out
+
+
+class HOIEvaluator(_HOIEvaluatorBase):
     """The loop body of utils.test (utils.py:170-196) for any batch size: feed the head's result dict and the image's
     target (`boxes_h`, `boxes_o`, `hoi`), read full / rare / non-rare mAP at the end.
 
@@ -619,26 +738,8 @@ class HOIEvaluator:
 
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, algorithm="11P",
                  known_object=False, splits=None, errors=False, bootstrap=None):
-        self.lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
-            else hico_object_n_verb_to_interaction()
-        num_cls = int(self.lut.max()) + 1
-        self.meter = DetectionAPMeter(num_cls, num_gt=num_gt_test, algorithm=algorithm)
-        self.min_iou = min_iou
-        self.num_anno_train = None if num_anno_train is None else torch.as_tensor(num_anno_train)
-        self.splits = _check_splits(splits, num_cls)
-        self.known_object = bool(known_object)
-        self.errors = bool(errors)
-        self.bootstrap = _check_bootstrap(bootstrap, self.splits)
-        if self.bootstrap is not None:
-            self._boot_cells, self._boot_gt, self._boot_images = [], [], 0      # (scores, classes, labels, keep), classes
-        if self.known_object or self.errors:
-            self.hoi_object = hoi_object_of(self.lut)
-        if self.known_object:
-            self.ko_meter = DetectionAPMeter(num_cls, num_gt=num_gt_test, algorithm=algorithm)
-            self.last_keep = []
-        if self.errors:
-            self._err_cells, self._err_gt = [], []               # (scores, classes, labels, category), (classes, status)
-            self.last_category, self.last_gt_status = [], []
+        super().__init__(num_gt_test, object_n_verb_to_interaction, min_iou, num_anno_train, "cpu", algorithm, known_object,
+                         splits, errors, bootstrap)
 
     def _errors_of(self, output, target, inter, labels):
         """Category of every cell and status of every ground-truth pair of one image (the rule above ERROR_CATEGORIES)."""
@@ -704,74 +805,25 @@ class HOIEvaluator:
                                               target["boxes_o"].to(scores.device)[gt].view(-1, 4),
                                               boxes_h[det].view(-1, 4), boxes_o[det].view(-1, 4),
                                               scores[det].view(-1), self.min_iou)
-        self.meter.append(scores, inter, labels)
+        t_hoi = t_hoi.reshape(-1).long()
+        log = dict(scores=scores.reshape(-1), hoi=inter.reshape(-1), labels=labels.reshape(-1))
         if self.known_object:
-            keep = self._keep_of(inter, t_hoi)
-            self.ko_meter.append(scores[keep], inter[keep], labels[keep])
-            self.last_keep = [keep]
+            log["keep"] = self._keep_of(inter, t_hoi).reshape(-1)
+            self.last_keep = [log["keep"]]
         if self.errors:
-            cat, status = self._errors_of(output, target, inter, labels)
-            self._err_cells.append((scores.reshape(-1), inter.reshape(-1), labels.reshape(-1), cat))
-            self._err_gt.append((t_hoi.reshape(-1).long(), status))
-            self.last_category, self.last_gt_status = [cat], [status]
+            log["category"], log["gt_status"] = self._errors_of(output, target, inter, labels)
+            self.last_category, self.last_gt_status = [log["category"]], [log["gt_status"]]
+        if "gt_hoi" in self.log:
+            log["gt_hoi"] = t_hoi
         if self.bootstrap is not None:                               # this image is number self._boot_images
-            self._boot_cells.append((scores.reshape(-1), inter.reshape(-1), labels.reshape(-1),
-                                     keep.reshape(-1) if self.known_object else None))
-            self._boot_gt.append(t_hoi.reshape(-1).long())
+            log["img"] = torch.full_like(log["hoi"], self._boot_images, dtype=torch.int64)
+            log["gt_img"] = torch.full_like(t_hoi, self._boot_images)
             self._boot_images += 1
+        self.log.append(**log)
         return labels
 
-    def _errors_block(self, full):
-        num_cls = self.meter.num_cls
-        cat_of = lambda parts, k, dtype: torch.cat([p[k].cpu() for p in parts]) if parts else torch.zeros(0, dtype=dtype)
-        scores = cat_of(self._err_cells, 0, torch.float32); inter = cat_of(self._err_cells, 1, torch.int64)
-        labels = cat_of(self._err_cells, 2, torch.float32); cat = cat_of(self._err_cells, 3, torch.uint8).long()
-        t = cat_of(self._err_gt, 0, torch.int64); status = cat_of(self._err_gt, 1, torch.uint8).long()
-        cells = torch.bincount(inter * 6 + cat, minlength=num_cls * 6).reshape(num_cls, 6)
-        ok = status != 255
-        gt = torch.bincount(t[ok] * 4 + status[ok], minlength=num_cls * 4).reshape(num_cls, 4)
-        ap_without = {}
-        for name in _AP_WITHOUT:
-            m = _without_mask(name, cat)
-            meter = DetectionAPMeter(num_cls, num_gt=self.meter.num_gt, algorithm=self.meter.algorithm)
-            meter.append(scores[m], inter[m], labels[m])
-            ap_without[name] = meter.eval()
-        return _errors_summary(cells, gt, ap_without, full)
 
-    def _bootstrap_block(self):
-        """summary()["bootstrap"]: the rule of include/skghoi.h through the host restatement, over this evaluator's log."""
-        cfg, num_cls, n = self.bootstrap, self.meter.num_cls, self._boot_images
-        num_gt = torch.as_tensor(self.meter.num_gt, dtype=torch.int64)
-        cat_of = lambda k, dtype: torch.cat([p[k].cpu() for p in self._boot_cells]) if n else torch.zeros(0, dtype=dtype)
-        scores = cat_of(0, torch.float32).float(); inter = cat_of(1, torch.int64); labels = cat_of(2, torch.float32)
-        img = torch.repeat_interleave(torch.arange(n), torch.tensor([p[0].numel() for p in self._boot_cells], dtype=torch.int64))
-        gt_cls = torch.cat([g.cpu() for g in self._boot_gt]) if n else torch.zeros(0, dtype=torch.int64)
-        gt_img = torch.repeat_interleave(torch.arange(n), torch.tensor([g.numel() for g in self._boot_gt], dtype=torch.int64))
-        _check_gt_counts(gt_cls, num_gt, num_cls)
-        weights = bootstrap_weights(n, cfg["n_boot"], cfg["seed"])
-        algorithm = self.meter.algorithm
-        ap_boot, ngb = _class_aps_boot_device(algorithm, scores, inter, labels, img, num_cls, gt_cls, gt_img, weights)
-        out = dict(n_boot=cfg["n_boot"], seed=cfg["seed"], n_images=n, level=cfg["level"])
-        out.update(_bootstrap_stats(ap_boot, ngb, num_gt, self.num_anno_train, self.splits, cfg["level"]))
-        if self.known_object:                                        # the same weights and num_gt_boot over the kept cells
-            keep = cat_of(3, torch.bool).bool()
-            ap_ko, _ = _class_aps_boot_device(algorithm, scores[keep], inter[keep], labels[keep], img[keep], num_cls, gt_cls,
-                                              gt_img, weights)
-            out["known_object"] = _bootstrap_stats(ap_ko, ngb, num_gt, self.num_anno_train, self.splits, cfg["level"])
-        return out
-
-    def summary(self):
-        out = _hoi_summary(self.meter.eval(), self.num_anno_train, self.splits)
-        if self.known_object:
-            out["known_object"] = _hoi_summary(self.ko_meter.eval(), self.num_anno_train, self.splits)
-        if self.errors:
-            out["errors"] = self._errors_block(out["full"])
-        if self.bootstrap is not None:
-            out["bootstrap"] = self._bootstrap_block()
-        return out
-
-
-class DeviceHOIEvaluator:
+class DeviceHOIEvaluator(_HOIEvaluatorBase):
     """utils.test (utils.py:148-198) on the device, for batches of any size: interaction lookup + box-pair association in
     one launch per batch (skg_eval_associate_f32), detections kept on the device, and at the end the shared device ranking
     (_class_aps_device) for the 600 eleven-point APs, float64.  Same numbers as HOIEvaluator (the host
@@ -791,34 +843,16 @@ class DeviceHOIEvaluator:
     def __init__(self, num_gt_test, object_n_verb_to_interaction=None, min_iou=0.5, num_anno_train=None, device="cuda",
                  algorithm="11P", known_object=False, splits=None, errors=False, bootstrap=None):
         from . import _capi
-        self.algorithm = _check_algorithm(algorithm)             # "AUC": the 600 APs by skg_eval_ap_voc_f64
-        self.device = torch.device(device)
-        lut = object_n_verb_to_interaction if object_n_verb_to_interaction is not None \
-            else hico_object_n_verb_to_interaction()
-        self.n_obj, self.n_verb = lut.shape
-        self.num_cls = int(lut.max()) + 1
-        self.lut = lut.to(self.device, torch.int32).contiguous()
-        self.num_gt = torch.as_tensor([int(v) for v in num_gt_test], dtype=torch.int64, device=self.device)
-        self.min_iou = float(min_iou)
-        self.num_anno_train = None if num_anno_train is None else torch.as_tensor(num_anno_train)
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._scores, self._hoi, self._labels = [], [], []
-        self.splits = _check_splits(splits, self.num_cls)
-        self.known_object = bool(known_object)
-        self.errors = bool(errors)
+        super().__init__(num_gt_test, object_n_verb_to_interaction, min_iou, num_anno_train, device, algorithm, known_object,
+                         splits, errors, bootstrap)
+        self.n_obj, self.n_verb = self.lut.shape
         if self.known_object and self.n_obj > _capi.EVAL_MAX_OBJECTS:
             raise ValueError("%d object categories; skg_eval_known_object_u8 takes at most %d"
                              % (self.n_obj, _capi.EVAL_MAX_OBJECTS))
+        self.lut = self.lut.to(self.device, torch.int32).contiguous()      # the tables as the kernels read them
         if self.known_object or self.errors:
-            self.hoi_object = hoi_object_of(lut).to(self.device, torch.int32).contiguous()
-        if self.known_object:
-            self._keep, self.last_keep = [], []
-        if self.errors:
-            self._cat, self._gt_hoi, self._gt_status = [], [], []
-            self.last_category, self.last_gt_status = [], []
-        self.bootstrap = _check_bootstrap(bootstrap, self.splits)
-        if self.bootstrap is not None:
-            self._boot_img, self._boot_gt, self._boot_images = [], [], 0      # image id per cell; (class, image id) per pair
+            self.hoi_object = self.hoi_object.to(self.device, torch.int32).contiguous()
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def add(self, outputs, targets):
         """outputs: the head's result dicts of a batch (HEAD:317-322); targets: per image {boxes_h, boxes_o, hoi}.
@@ -853,86 +887,40 @@ class DeviceHOIEvaluator:
             scores.data_ptr(), cell_off, n, self.lut.data_ptr(), self.n_obj, self.n_verb, gt_h.data_ptr(), gt_o.data_ptr(),
             gt_hoi.data_ptr(), gt_off, self.min_iou, hoi.data_ptr(), labels.data_ptr(), self.status.data_ptr(), _stream()),
             "skg_eval_associate_f32")
-        self._scores.append(scores[:L]); self._hoi.append(hoi[:L]); self._labels.append(labels[:L])
+        G = int(sum(gts))                                            # (without ground truth gt_hoi is the padding row: none kept)
+        log = dict(scores=scores[:L], hoi=hoi[:L], labels=labels[:L])
+        if "gt_hoi" in self.log:
+            log["gt_hoi"] = gt_hoi[:G]
         if self.known_object:                                        # behind the association, on its hoi_out
             keep = torch.zeros(max(L, 1), dtype=torch.uint8, device=dev)
             _capi.check(_capi.lib().skg_eval_known_object_u8(
                 hoi.data_ptr(), cell_off, n, self.hoi_object.data_ptr(), self.num_cls, self.n_obj, gt_hoi.data_ptr(), gt_off,
                 keep.data_ptr(), _stream()), "skg_eval_known_object_u8")
-            self._keep.append(keep[:L]); self.last_keep = list(keep[:L].split(cpi))
+            log["keep"] = keep[:L]; self.last_keep = list(keep[:L].split(cpi))
         if self.errors:                                              # behind the association, on its hoi_out and final labels
-            G = int(sum(gts))                                        # (without ground truth: the padding row, owned by no image)
             cat = torch.empty(max(L, 1), dtype=torch.uint8, device=dev)
             status = torch.empty(max(G, 1), dtype=torch.uint8, device=dev)
             _capi.check(_capi.lib().skg_eval_hoi_errors_u8(
                 boxes_h.data_ptr(), boxes_o.data_ptr(), pair_off, index.data_ptr(), hoi.data_ptr(), labels.data_ptr(), cell_off,
                 n, self.hoi_object.data_ptr(), self.num_cls, gt_h.data_ptr(), gt_o.data_ptr(), gt_hoi.data_ptr(), gt_off,
                 self.min_iou, cat.data_ptr(), status.data_ptr(), _stream()), "skg_eval_hoi_errors_u8")
-            self._cat.append(cat[:L]); self._gt_hoi.append(gt_hoi[:G]); self._gt_status.append(status[:G])
+            log["category"], log["gt_status"] = cat[:L], status[:G]
             self.last_category, self.last_gt_status = list(cat[:L].split(cpi)), list(status[:G].split(gts))
         if self.bootstrap is not None:                               # ids from the counts the host holds: no launch of ours, no sync
             ids = np.arange(self._boot_images, self._boot_images + n, dtype=np.int32)
-            G = int(sum(gts))                                        # (without ground truth gt_hoi is the padding row: none kept)
-            self._boot_img.append(torch.from_numpy(np.repeat(ids, cpi)).to(dev))
-            self._boot_gt.append((gt_hoi[:G], torch.from_numpy(np.repeat(ids, gts)).to(dev)))
+            log["img"] = torch.from_numpy(np.repeat(ids, cpi)).to(dev)
+            log["gt_img"] = torch.from_numpy(np.repeat(ids, gts)).to(dev)
             self._boot_images += n
+        self.log.append(**log)
         return list(labels[:L].split(cpi))
 
-    def summary(self):
+    def _check_log(self, hoi):
         from . import _capi
-        dev = self.device
         if int(self.status.item()):
             raise _capi.SkgError("an image has %d ground-truth pairs; skg_eval_associate_f32 keeps at most 2048 per image"
                                  % int(self.status.item()))
-        ap = ap_ko = torch.zeros(self.num_cls, dtype=torch.float64, device=dev)
-        if self._scores:
-            scores = torch.cat(self._scores); hoi = torch.cat(self._hoi).long(); labels = torch.cat(self._labels)
-            if (hoi < 0).any():
-                raise IndexError("a predicted (object, verb) pair is not a valid interaction")
-            ap = _class_aps_device(self.algorithm, scores, hoi, labels, self.num_cls, self.num_gt)
-            if self.known_object:                                    # the same rule over the kept cells (their order kept)
-                keep = torch.cat(self._keep).bool()
-                ap_ko = _class_aps_device(self.algorithm, scores[keep], hoi[keep], labels[keep], self.num_cls, self.num_gt)
-        out = _hoi_summary(ap.cpu(), self.num_anno_train, self.splits)
-        if self.known_object:
-            out["known_object"] = _hoi_summary(ap_ko.cpu(), self.num_anno_train, self.splits)
-        if self.errors:
-            nc = self.num_cls
-            cells = torch.zeros(nc, 6, dtype=torch.int64); gt = torch.zeros(nc, 4, dtype=torch.int64)
-            ap_without = {name: torch.zeros(nc, dtype=torch.float64) for name in _AP_WITHOUT}
-            if self._scores:
-                cat = torch.cat(self._cat).long()
-                cells = torch.bincount(hoi * 6 + cat, minlength=nc * 6).reshape(nc, 6).cpu()
-                t = torch.cat(self._gt_hoi); status = torch.cat(self._gt_status).long()
-                ok = status != 255
-                gt = torch.bincount(t[ok] * 4 + status[ok], minlength=nc * 4).reshape(nc, 4).cpu()
-                for name in _AP_WITHOUT:                             # the same rule over a mask, like Known Object
-                    m = _without_mask(name, cat)
-                    ap_without[name] = _class_aps_device(self.algorithm, scores[m], hoi[m], labels[m], nc, self.num_gt).cpu()
-            out["errors"] = _errors_summary(cells, gt, ap_without, out["full"])
-        if self.bootstrap is not None:
-            cfg, nc, n = self.bootstrap, self.num_cls, self._boot_images
-            empty = lambda dtype: torch.zeros(0, dtype=dtype, device=dev)
-            gt_cls = torch.cat([g for g, _ in self._boot_gt]) if self._boot_gt else empty(torch.int64)
-            gt_img = torch.cat([i for _, i in self._boot_gt]) if self._boot_gt else empty(torch.int32)
-            num_gt = self.num_gt.cpu()
-            _check_gt_counts(gt_cls, num_gt, nc)
-            weights = bootstrap_weights(n, cfg["n_boot"], cfg["seed"]).to(dev)
-            if self._scores:
-                img = torch.cat(self._boot_img)
-            else:
-                scores, hoi, labels, img = empty(torch.float32), empty(torch.int64), empty(torch.float32), empty(torch.int32)
-            ap_boot, ngb = _class_aps_boot_device(self.algorithm, scores, hoi, labels, img, nc, gt_cls, gt_img, weights)
-            ngb = ngb.cpu()
-            bs = dict(n_boot=cfg["n_boot"], seed=cfg["seed"], n_images=n, level=cfg["level"])
-            bs.update(_bootstrap_stats(ap_boot.cpu(), ngb, num_gt, self.num_anno_train, self.splits, cfg["level"]))
-            if self.known_object:                                    # the same weights and num_gt_boot over the kept cells
-                if self._scores:
-                    scores, hoi, labels, img = scores[keep], hoi[keep], labels[keep], img[keep]
-                ap_ko, _ = _class_aps_boot_device(self.algorithm, scores, hoi, labels, img, nc, gt_cls, gt_img, weights)
-                bs["known_object"] = _bootstrap_stats(ap_ko.cpu(), ngb, num_gt, self.num_anno_train, self.splits, cfg["level"])
-            out["bootstrap"] = bs
-        return out
+        if (hoi < 0).any():
+            raise IndexError("a predicted (object, verb) pair is not a valid interaction")
 
 
 # ----------------------------------------------------------------------------------------------- V-COCO role AP
@@ -1018,7 +1006,38 @@ def _vcoco_summary(table, ap_s1, ap_s2, npos):
     return out
 
 
-class VCOCOEvaluator:
+class _VCOCOEvaluatorBase:
+    """What VCOCOEvaluator and DeviceVCOCOEvaluator share: the class table, npos, the log (scores, pred and one label column
+    per scenario, per cell) and `summary()`.  They differ in `add` and `_check_log`."""
+    batched = True                                               # trainer.test feeds lists
+
+    def __init__(self, actions, thr, device):
+        self.table = _vcoco_class_table(actions)
+        self.thr = float(thr)
+        self.device = torch.device(device)
+        self.npos = torch.zeros(_N_VSRL, dtype=torch.int64, device=self.device)
+        self.log = _Log(self.device, scores=torch.float32, pred=torch.int64, labels_s1=torch.int8, labels_s2=torch.int8)
+
+    def _check_log(self, pred):
+        """What a device evaluator can only report at summary() time; the host evaluator raises in `add`."""
+
+    def summary(self):
+        """role_ap_s1 / role_ap_s2 [K] float64 (NaN where no person does the action), mean_s1 / mean_s2 over the K classes,
+        npos [26], toolkit_mean_s1 / _s2 over the toolkit's 25 role slots (a slot the head does not predict counts 0); every
+        tensor on the host."""
+        K, log = len(self.table), self.log
+        scores, pred = log.column("scores"), log.column("pred")
+        self._check_log(pred)
+        num_gt = self.npos[torch.tensor([aid for aid, _ in self.table], dtype=torch.int64, device=self.device)].contiguous()
+        aps = []
+        for s in (1, 2):
+            labels = log.column("labels_s%d" % s)
+            keep = labels >= 0                                       # dropped cells never reach the ranking
+            aps.append(_class_aps("AUC", scores[keep], pred[keep], labels[keep], K, num_gt).cpu())
+        return _vcoco_summary(self.table, aps[0], aps[1], self.npos.to("cpu", copy=True))
+
+
+class VCOCOEvaluator(_VCOCOEvaluatorBase):
     """AP_role of V-COCO in scenario 1 and scenario 2 (`_do_role_eval` of the published toolkit's vsrl_eval.VCOCOeval, which
     vcoco_evaluation.py:3-10 imports from outside the reference; restated, parity unpinned at that boundary) from the head's
     result dicts, on the host -- the restatement DeviceVCOCOEvaluator is checked against.
@@ -1039,13 +1058,9 @@ class VCOCOEvaluator:
     The head's own detections are scored: the score-0 template rows that vcoco_results' records carry for every other class
     do not change scenario 1 (given positive scores and no degenerate role box at the origin) and are left out of
     scenario 2, where the toolkit can count them for role-less persons."""
-    batched = True                                               # trainer.test feeds lists
 
     def __init__(self, actions, thr=0.5):
-        self.table = _vcoco_class_table(actions)
-        self.thr = float(thr)
-        self.npos = torch.zeros(_N_VSRL, dtype=torch.int64)
-        self._scores, self._pred, self._labels = [], [], []
+        super().__init__(actions, thr, "cpu")
 
     def _labels_of(self, output, target):
         idx = output["index"].cpu().long()
@@ -1080,7 +1095,7 @@ class VCOCOEvaluator:
                         best[key] = c
                 if best:
                     labels[list(best.values()), s] = 1
-        self._scores.append(sc); self._pred.append(pr); self._labels.append(labels)
+        self.log.append(scores=sc, pred=pr, labels_s1=labels[:, 0], labels_s2=labels[:, 1])
         return labels
 
     def add(self, outputs, targets):
@@ -1090,41 +1105,21 @@ class VCOCOEvaluator:
             raise ValueError("%d outputs for %d targets" % (len(outputs), len(targets)))
         return [self._labels_of(o, t) for o, t in zip(outputs, targets)]
 
-    def summary(self):
-        """role_ap_s1 / role_ap_s2 [K] float64 (NaN where no person does the action), mean_s1 / mean_s2 over the K classes,
-        npos [26], toolkit_mean_s1 / _s2 over the toolkit's 25 role slots (a slot the head does not predict counts 0)."""
-        K = len(self.table)
-        scores = torch.cat(self._scores) if self._scores else torch.zeros(0)
-        pred = torch.cat(self._pred) if self._pred else torch.zeros(0, dtype=torch.int64)
-        labels = torch.cat(self._labels) if self._labels else torch.zeros(0, 2, dtype=torch.int8)
-        aps = []
-        for s in range(2):
-            meter = DetectionAPMeter(K, num_gt=[int(self.npos[aid]) for aid, _ in self.table], algorithm="AUC")
-            keep = labels[:, s] >= 0                                 # dropped cells never reach the ranking
-            meter.append(scores[keep], pred[keep], labels[keep, s])
-            aps.append(meter.eval())
-        return _vcoco_summary(self.table, aps[0], aps[1], self.npos.clone())
 
-
-class DeviceVCOCOEvaluator:
+class DeviceVCOCOEvaluator(_VCOCOEvaluatorBase):
     """VCOCOEvaluator on the device, for batches of any size: one skg_eval_vcoco_match_f32 launch per `add` (both scenarios),
     detections, labels and npos kept on the device, and at the end, per scenario, the shared device ranking
     (_class_aps_device, 'AUC').  Same labels and APs as the host evaluator; same rule, same interface -- callers
     must add every test image, also those without detections.  An image with more than 256 persons is reported by
     `summary()`, like the 2048 ground-truth pairs of DeviceHOIEvaluator."""
-    batched = True
 
     def __init__(self, actions, thr=0.5, device="cuda"):
         from . import _capi
-        self.table = _vcoco_class_table(actions)
+        super().__init__(actions, thr, device)
         if len(self.table) > _capi.VCOCO_MAX_CLASSES:
             raise ValueError("%d classes; skg_eval_vcoco_match_f32 takes at most %d" % (len(self.table), _capi.VCOCO_MAX_CLASSES))
-        self.thr = float(thr)
-        self.device = torch.device(device)
         self.class_ar = torch.tensor(self.table, dtype=torch.int32).reshape(-1, 2).to(self.device).contiguous()
-        self.npos = torch.zeros(_N_VSRL, dtype=torch.int64, device=self.device)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._scores, self._pred, self._labels = [], [], []
 
     def add(self, outputs, targets):
         """As VCOCOEvaluator.add; the returned tensors are views of one device tensor."""
@@ -1155,27 +1150,16 @@ class DeviceVCOCOEvaluator:
             boxes_h.data_ptr(), boxes_o.data_ptr(), pair_off, index.data_ptr(), pred.data_ptr(), scores.data_ptr(), cell_off, n,
             self.class_ar.data_ptr(), len(self.table), persons.data_ptr(), actions.data_ptr(), role_boxes.data_ptr(), gt_off,
             self.thr, labels[0].data_ptr(), labels[1].data_ptr(), self.status.data_ptr(), _stream()), "skg_eval_vcoco_match_f32")
-        self._scores.append(scores[:L]); self._pred.append(pred[:L]); self._labels.append(labels[:, :L])
+        self.log.append(scores=scores[:L], pred=pred[:L], labels_s1=labels[0, :L], labels_s2=labels[1, :L])
         return list(labels[:, :L].t().split(cpi))
 
-    def summary(self):
-        """As VCOCOEvaluator.summary (tensors on the host)."""
+    def _check_log(self, pred):
         from . import _capi
-        dev = self.device
         if int(self.status.item()):
             raise _capi.SkgError("an image has %d persons; skg_eval_vcoco_match_f32 keeps at most %d per image"
                                  % (int(self.status.item()), _capi.VCOCO_MAX_PERSONS))
-        K = len(self.table)
-        num_gt = self.npos[torch.tensor([a for a, _ in self.table], dtype=torch.int64, device=dev)].contiguous()
-        aps = [torch.zeros(K, dtype=torch.float64), torch.zeros(K, dtype=torch.float64)]
-        if self._scores:
-            scores = torch.cat(self._scores); pred = torch.cat(self._pred); labels = torch.cat(self._labels, dim=1)
-            if ((pred < 0) | (pred >= K)).any():
-                raise IndexError("a prediction is outside the %d classes" % K)
-            for s in range(2):
-                keep = labels[s] >= 0                                # dropped cells never reach the ranking
-                aps[s] = _class_aps_device("AUC", scores[keep], pred[keep], labels[s][keep], K, num_gt).cpu()
-        return _vcoco_summary(self.table, aps[0], aps[1], self.npos.cpu())
+        if ((pred < 0) | (pred >= len(self.table))).any():
+            raise IndexError("a prediction is outside the %d classes" % len(self.table))
 
 
 # ----------------------------------------------------------------------------------------------- object detections
@@ -1255,7 +1239,50 @@ def _det_target(target, device):
     return bh, bo, ob, hoi
 
 
-class DetectionEvaluator:
+class _DetectionEvaluatorBase:
+    """What DetectionEvaluator and DeviceDetectionEvaluator share: the constructor's checks, num_gt, the log (scores, cls,
+    labels per detection; covered and, with num_hoi, hoi per ground-truth pair, -1 for a pair of a target without `hoi`) and
+    `summary()`.  They differ in `add` and `_check_log`."""
+    batched = True                                               # trainer.test-style loops feed lists
+
+    def __init__(self, num_classes, human_idx, min_iou, nms_thresh, algorithm, num_hoi, device):
+        self.algorithm = _check_algorithm(algorithm)
+        if not 0 <= int(human_idx) < int(num_classes):
+            raise ValueError("human_idx %d is outside the %d classes" % (human_idx, num_classes))
+        self.num_classes, self.human_idx = int(num_classes), int(human_idx)
+        self.min_iou, self.nms_thresh = float(min_iou), float(nms_thresh)
+        self.num_hoi = None if num_hoi is None else int(num_hoi)
+        self.device = torch.device(device)
+        self.num_gt = torch.zeros(self.num_classes, dtype=torch.int64, device=self.device)
+        columns = dict(scores=torch.float32, cls=torch.int64, labels=torch.int8, covered=torch.uint8)
+        if self.num_hoi is not None:
+            columns["hoi"] = torch.int64
+        self.log = _Log(self.device, **columns)
+        self.last_gt_keep, self.last_matched, self.last_covered = [], [], []
+
+    def _check_log(self, cls):
+        """What a device evaluator can only report at summary() time; the host evaluator raises in `add`."""
+
+    def summary(self):
+        C, log = self.num_classes, self.log
+        scores, cls, labels = log.column("scores"), log.column("cls"), log.column("labels")
+        self._check_log(cls)
+        live = labels >= 0                                           # dropped detections never reach the ranking
+        cl, lab = cls[live], labels[live].double()
+        ap = _class_aps(self.algorithm, scores[live], cl, lab, C, self.num_gt)
+        tp = torch.zeros(C, dtype=torch.float64, device=self.device).index_add_(0, cl, lab)
+        cov = log.column("covered")
+        hoi_pairs = hoi_covered = None
+        if self.num_hoi is not None:
+            hoi = log.column("hoi")
+            inside = (hoi >= 0) & (hoi < self.num_hoi)
+            hoi_pairs = torch.bincount(hoi[inside], minlength=self.num_hoi).cpu()
+            hoi_covered = torch.bincount(hoi[inside & cov.bool()], minlength=self.num_hoi).cpu()
+        return _det_summary(ap.cpu(), self.num_gt.to("cpu", copy=True), tp.cpu(), int(cov.numel()), int(cov.sum()), hoi_pairs,
+                            hoi_covered)
+
+
+class DetectionEvaluator(_DetectionEvaluatorBase):
     """Object-detection AP, maximum recall and pair coverage of the detections behind the head (the rule above), on the host
     in plain torch and loops -- the restatement DeviceDetectionEvaluator is checked against.
 
@@ -1270,21 +1297,9 @@ class DetectionEvaluator:
     map_present / mean_max_rec_present over the classes with ground truth, pair_recall = covered pairs / pairs, and, with
     num_hoi, pair_recall_hoi [num_hoi] over the targets that carry `hoi` (NaN for a class without pairs; ids outside
     [0, num_hoi) are ignored)."""
-    batched = True                                               # trainer.test-style loops feed lists
 
     def __init__(self, num_classes=80, human_idx=49, min_iou=0.5, nms_thresh=0.5, algorithm="AUC", num_hoi=None):
-        self.algorithm = _check_algorithm(algorithm)
-        if not 0 <= int(human_idx) < int(num_classes):
-            raise ValueError("human_idx %d is outside the %d classes" % (human_idx, num_classes))
-        self.num_classes, self.human_idx = int(num_classes), int(human_idx)
-        self.min_iou, self.nms_thresh = float(min_iou), float(nms_thresh)
-        self.num_hoi = None if num_hoi is None else int(num_hoi)
-        self.num_gt = torch.zeros(self.num_classes, dtype=torch.int64)
-        self._scores, self._cls, self._labels = [], [], []
-        self._pairs = self._covered = 0
-        self._hoi_pairs = None if num_hoi is None else torch.zeros(self.num_hoi, dtype=torch.int64)
-        self._hoi_covered = None if num_hoi is None else torch.zeros(self.num_hoi, dtype=torch.int64)
-        self.last_gt_keep, self.last_matched, self.last_covered = [], [], []
+        super().__init__(num_classes, human_idx, min_iou, nms_thresh, algorithm, num_hoi, "cpu")
 
     def _one(self, det, target):
         C = self.num_classes
@@ -1322,12 +1337,9 @@ class DetectionEvaluator:
             co = (box_iou(bo, boxes) >= thr) & live[None] & (cls[None] == ob[:, None])
             same = (ch.sum(1) == 1) & (co.sum(1) == 1) & (ch & co).any(1)                   # one detection on both sides
             covered = (ch.any(1) & co.any(1) & ~same).to(torch.uint8)
-        self._scores.append(sc); self._cls.append(cls); self._labels.append(labels)
-        self._pairs += G; self._covered += int(covered.sum())
-        if self.num_hoi is not None and hoi is not None:
-            inside = (hoi >= 0) & (hoi < self.num_hoi)
-            self._hoi_pairs += torch.bincount(hoi[inside], minlength=self.num_hoi)
-            self._hoi_covered += torch.bincount(hoi[inside & covered.bool()], minlength=self.num_hoi)
+        self.log.append(scores=sc, cls=cls, labels=labels, covered=covered)
+        if self.num_hoi is not None:                                 # -1: a pair of a target without `hoi`
+            self.log.append(hoi=hoi if hoi is not None else torch.full_like(ob, -1))
         return labels, keep, matched, covered
 
     def add(self, detections, targets):
@@ -1337,41 +1349,18 @@ class DetectionEvaluator:
         self.last_gt_keep = [r[1] for r in res]; self.last_matched = [r[2] for r in res]; self.last_covered = [r[3] for r in res]
         return [r[0] for r in res]
 
-    def summary(self):
-        C = self.num_classes
-        sc = torch.cat(self._scores) if self._scores else torch.zeros(0)
-        cls = torch.cat(self._cls) if self._cls else torch.zeros(0, dtype=torch.int64)
-        lab = torch.cat(self._labels) if self._labels else torch.zeros(0, dtype=torch.int8)
-        live = lab >= 0                                          # dropped detections never reach the ranking
-        sc, cls, lab = sc[live], cls[live], lab[live].double()
-        meter = DetectionAPMeter(C, num_gt=self.num_gt, algorithm=self.algorithm)
-        meter.append(sc, cls, lab)
-        tp = torch.zeros(C, dtype=torch.float64).index_add_(0, cls, lab)
-        return _det_summary(meter.eval(), self.num_gt.clone(), tp, self._pairs, self._covered, self._hoi_pairs,
-                            self._hoi_covered)
 
-
-class DeviceDetectionEvaluator:
+class DeviceDetectionEvaluator(_DetectionEvaluatorBase):
     """DetectionEvaluator on the device, for batches of any size: one skg_eval_det_match_f32 launch (ground-truth NMS,
     association, num_gt by integer atomics) and one skg_eval_pair_cover_u8 launch per `add`, no host synchronisation there;
     scores, classes, labels and coverage flags stay on the device.  `summary()` drops the -1 cells and ranks the others with
     _class_aps_device; max_rec comes from an index_add_ of the labels.  Same labels, flags and numbers as
     the host evaluator, same interface; the `last_*` lists are views of device tensors.  An image with more than
     SKG_EVAL_DET_MAX_GT ground-truth boxes (2 per pair) and a class outside [0, num_classes) are reported by `summary()`."""
-    batched = True
 
     def __init__(self, num_classes=80, human_idx=49, min_iou=0.5, nms_thresh=0.5, algorithm="AUC", num_hoi=None, device="cuda"):
-        self.algorithm = _check_algorithm(algorithm)
-        if not 0 <= int(human_idx) < int(num_classes):
-            raise ValueError("human_idx %d is outside the %d classes" % (human_idx, num_classes))
-        self.num_classes, self.human_idx = int(num_classes), int(human_idx)
-        self.min_iou, self.nms_thresh = float(min_iou), float(nms_thresh)
-        self.num_hoi = None if num_hoi is None else int(num_hoi)
-        self.device = torch.device(device)
-        self.num_gt = torch.zeros(self.num_classes, dtype=torch.int64, device=self.device)
+        super().__init__(num_classes, human_idx, min_iou, nms_thresh, algorithm, num_hoi, device)
         self.status = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self._scores, self._cls, self._labels, self._covered, self._hoi = [], [], [], [], []
-        self.last_gt_keep, self.last_matched, self.last_covered = [], [], []
 
     def add(self, detections, targets):
         """As DetectionEvaluator.add; the returned tensors are views of one device tensor."""
@@ -1409,43 +1398,21 @@ class DeviceDetectionEvaluator:
         _capi.check(_capi.lib().skg_eval_pair_cover_u8(
             boxes_p.data_ptr(), cls_p.data_ptr(), labels.data_ptr(), det_off, n, gt_h.data_ptr(), gt_o.data_ptr(),
             gt_ob.data_ptr(), gt_off, self.human_idx, self.min_iou, covered.data_ptr(), _stream()), "skg_eval_pair_cover_u8")
-        self._scores.append(scores); self._cls.append(cls); self._labels.append(labels[:L]); self._covered.append(covered[:Ng])
+        self.log.append(scores=scores, cls=cls, labels=labels[:L], covered=covered[:Ng])
         if self.num_hoi is not None:                                 # -1: a pair of a target without `hoi`
-            self._hoi.append(torch.cat([t[3] if t[3] is not None else torch.full_like(t[2], -1) for t in tg]))
+            self.log.append(hoi=torch.cat([t[3] if t[3] is not None else torch.full_like(t[2], -1) for t in tg]))
         self.last_gt_keep = list(gt_keep[:2 * Ng].split([2 * g for g in gts]))
         self.last_matched = list(matched[:L].split(per)); self.last_covered = list(covered[:Ng].split(gts))
         return list(labels[:L].split(per))
 
-    def summary(self):
-        """As DetectionEvaluator.summary (tensors on the host)."""
+    def _check_log(self, cls):
         from . import _capi
-        dev, C = self.device, self.num_classes
         over, outside = self.status.cpu().tolist()
         if over:
             raise _capi.SkgError("an image has %d ground-truth boxes; skg_eval_det_match_f32 keeps at most %d per image"
                                  % (over, _capi.EVAL_DET_MAX_GT))
-        ap = torch.zeros(C, dtype=torch.float64, device=dev)
-        tp = torch.zeros(C, dtype=torch.float64, device=dev)
-        pairs = covered = 0
-        if self._scores:
-            scores = torch.cat(self._scores); cls = torch.cat(self._cls); labels = torch.cat(self._labels)
-            if outside or bool(((cls < 0) | (cls >= C)).any()):
-                raise IndexError("a detection or ground-truth class is outside [0, %d)" % C)
-            live = labels >= 0                                       # dropped detections never reach the ranking
-            cl, lab = cls[live], labels[live]
-            ap = _class_aps_device(self.algorithm, scores[live], cl, lab, C, self.num_gt)
-            tp.index_add_(0, cl, lab.double())
-            cov = torch.cat(self._covered)
-            pairs, covered = int(cov.numel()), int(cov.sum())
-        hoi_pairs = hoi_covered = None
-        if self.num_hoi is not None:
-            hoi_pairs = torch.zeros(self.num_hoi, dtype=torch.int64); hoi_covered = hoi_pairs.clone()
-            if self._hoi:
-                hoi = torch.cat(self._hoi)
-                inside = (hoi >= 0) & (hoi < self.num_hoi)
-                hoi_pairs = torch.bincount(hoi[inside], minlength=self.num_hoi).cpu()
-                hoi_covered = torch.bincount(hoi[inside & cov.bool()], minlength=self.num_hoi).cpu()
-        return _det_summary(ap.cpu(), self.num_gt.cpu(), tp.cpu(), pairs, covered, hoi_pairs, hoi_covered)
+        if outside or bool(((cls < 0) | (cls >= self.num_classes)).any()):
+            raise IndexError("a detection or ground-truth class is outside [0, %d)" % self.num_classes)
 
 
 # ----------------------------------------------------------------------------------------------- pair NMS

@@ -49,6 +49,22 @@ def _bar(name, got, ref64, y32):
     assert err <= bound, "%s: err %.3e > max(8 * %.3e, 4 * 2^-24 * %.3e)" % (name, err, e32, scale)
 
 
+def _same_tree(a, b, where="summary"):
+    """Two evaluator summaries: the same keys in the same order, tensors of one dtype and torch.equal (NaN in the same
+    places), everything else == (NaN equal to NaN)."""
+    if isinstance(a, dict):
+        assert isinstance(b, dict) and list(a) == list(b), "%s: keys %s against %s" % (where, list(a), list(b))
+        for k in a:
+            _same_tree(a[k], b[k], "%s[%r]" % (where, k))
+    elif torch.is_tensor(a):
+        assert torch.is_tensor(b) and a.dtype == b.dtype and a.shape == b.shape, where
+        a, b = a.cpu(), b.cpu()
+        nan = torch.isnan(a) if a.is_floating_point() else torch.zeros_like(a, dtype=torch.bool)
+        assert torch.equal(nan, torch.isnan(b) if b.is_floating_point() else nan) and torch.equal(a[~nan], b[~nan]), where
+    else:
+        assert a == b or (a != a and b != b), "%s: %r against %r" % (where, a, b)
+
+
 def _twice(launch):
     """Runs `launch` twice on fresh buffers; the outputs must be identical bit for bit.  Returns the first run's."""
     a = launch(); b = launch()

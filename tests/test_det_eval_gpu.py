@@ -21,7 +21,7 @@ import pytest
 import torch
 
 import det_eval_refs as R
-from kernel_test_helpers import _out, _take, _twice
+from kernel_test_helpers import _out, _same_tree, _take, _twice
 from skghoi_amd import _capi, cache, evaluate as ev, synth
 from skghoi_amd.engine import _stream
 from test_det_eval_host import check_summary
@@ -248,3 +248,25 @@ def test_kept_detections_of_produce_shard(tmp_path):
         assert abs(s[k] - w[k]) <= 1e-12, k
     print("produce_shard: %d kept detections, map_present %.4f, mean_max_rec_present %.4f, pair_recall %.4f" % (
         sum(x.numel() for x in got), s["map_present"], s["mean_max_rec_present"], s["pair_recall"]))
+
+
+@pytest.mark.parametrize("algorithm", ["AUC", "11P"])
+def test_empty_and_degenerate_logs_host_equals_device(algorithm):
+    """The shared summary() without any `add`, over an image with ground truth and no detection, and over an image with
+    detections and no ground truth: host and device return the same keys in the same order and equal tensors (every AP is 0
+    on both sides)."""
+    dets, tgts = R.make_case(0)
+    assert dets[1]["scores"].numel() == 0 and tgts[1]["object"].numel() == 1
+    assert dets[2]["scores"].numel() == 5 and tgts[2]["object"].numel() == 0
+    for num_hoi, images in [(n, i) for n in (R.N_HOI, None) for i in ([], [1], [2], [1, 2])]:
+        kw = dict(num_hoi=num_hoi, algorithm=algorithm)
+        host = ev.DetectionEvaluator(**kw); dev = ev.DeviceDetectionEvaluator(**kw)
+        if images:
+            want = host.add([dets[b] for b in images], [tgts[b] for b in images])
+            got = dev.add([_cu(dets[b]) for b in images], [_cu(tgts[b]) for b in images])
+            assert all(torch.equal(g.cpu(), w) for g, w in zip(got, want))
+        sh, sd = host.summary(), dev.summary()
+        assert list(sd) == ["ap", "num_gt", "max_rec", "map", "mean_max_rec", "map_present", "mean_max_rec_present",
+                            "pair_recall"] + ["pair_recall_hoi"] * (num_hoi is not None)
+        _same_tree(sh, sd, "num_hoi %s, images %s" % (num_hoi, images))
+        assert float(sd["ap"].abs().max()) == 0 and int(sd["num_gt"].sum()) == (2 if 1 in images else 0)

@@ -14,6 +14,7 @@ Measured on an MI355X: the kernel's "11P" is bit-equal to the loop at every n_bo
 against _class_aps_device 0 and 1.2e-16; the device evaluator's replicate means within 3.5e-18 of the loop's on both seeds (the
 tests print them); the file's 24 tests take 5 s (pytest's own figure)."""
 import functools
+import itertools
 from collections import OrderedDict
 
 import pytest
@@ -23,7 +24,7 @@ import bootstrap_refs as B
 import cases
 import gpu_run
 import hoi_error_refs as R
-from kernel_test_helpers import _out, _take, _twice
+from kernel_test_helpers import _out, _same_tree, _take, _twice
 from skghoi_amd import _capi, evaluate as ev, synth, trainer
 from skghoi_amd.engine import _stream
 
@@ -245,3 +246,50 @@ def test_trainer_test_with_bootstrap():
     print("trainer.test: full %.6f, bootstrap mean %.6f std %.6f [%.6f, %.6f]" % (s["full"], bs["full"]["mean"], bs["full"]["std"],
                                                                                 bs["full"]["lo"], bs["full"]["hi"]))
     print(ev.format_bootstrap(s))
+
+
+def _tiny_case():
+    """A 3 x 4 lookup table and three images: 0 with a true positive; 1 with ground truth and no cell; 2 with cells and no
+    ground truth."""
+    box = lambda k: [10. + 100 * k, 10., 60. + 100 * k, 90.]
+    outs = [R._pack([box(0)], [box(1)], [1], [0, 0], [0, 2], [0.9, 0.4]),
+            R._pack([box(0)], [box(2)], [2], [], [], []),
+            R._pack([box(1), box(3)], [box(2), box(0)], [0, 2], [0, 1, 1], [1, 0, 3], [0.5, 0.5, 0.7])]
+    tgts = [R._pack_gt([box(0)], [box(1)], [4]), R._pack_gt([box(0), box(3)], [box(2), box(1)], [8, 5]), R._pack_gt([], [], [])]
+    return outs, tgts, torch.arange(12).reshape(3, 4)
+
+
+@pytest.mark.parametrize("algorithm", ALGORITHMS)
+@pytest.mark.parametrize("known_object,errors,bootstrap", list(itertools.product((False, True), (False, True), (None, 4))))
+def test_empty_and_degenerate_logs_host_equals_device(known_object, errors, bootstrap, algorithm):
+    """The shared summary() over a log without cells, without ground truth, or without anything: host and device return the
+    same keys in the same order and equal tensors (every AP here is 0 on both sides: nothing to round)."""
+    outs, tgts, lut = _tiny_case()
+    kw = dict(num_anno_train=[5, 50] * 6, algorithm=algorithm, splits=dict(odd=[1, 3, 5]), known_object=known_object, errors=errors,
+              bootstrap=bootstrap)
+    keys = ["ap", "full", "rare", "non_rare", "odd"] + [k for k, on in (("known_object", known_object), ("errors", errors),
+                                                                       ("bootstrap", bootstrap)) if on]
+    for images in ([], [1], [2], [1, 2]):                           # no `add` at all; no cells; no ground truth; both
+        num_gt = B.counted_num_gt([tgts[b] for b in images], 12)
+        host = ev.HOIEvaluator(num_gt, lut, **kw); dev = ev.DeviceHOIEvaluator(num_gt, lut, **kw)
+        for b in images:
+            want = host.add(outs[b], tgts[b]); got = dev.add([_cu(outs[b])], [_cu(tgts[b])])
+            assert torch.equal(got[0].cpu(), want) and want.numel() == outs[b]["scores"].numel()
+        sh, sd = host.summary(), dev.summary()
+        assert list(sd) == keys and float(sd["ap"].abs().max()) == 0 and sd["ap"].shape == (12,)
+        _same_tree(sh, sd, "images %s" % images)
+        if errors:
+            assert int(sd["errors"]["cells_total"].sum()) == sum(outs[b]["scores"].numel() for b in images)
+            assert int(sd["errors"]["gt_total"].sum()) == sum(num_gt)
+        if bootstrap:
+            assert sd["bootstrap"]["n_images"] == len(images) and sd["bootstrap"]["replicates"]["full"].shape == (4,)
+    # the whole case, so that the degenerate images sit beside a scored one: image 0's cell of class 4 is its true positive
+    num_gt = B.counted_num_gt(tgts, 12)
+    host = ev.HOIEvaluator(num_gt, lut, **kw); dev = ev.DeviceHOIEvaluator(num_gt, lut, **kw)
+    for o, t in zip(outs, tgts):
+        host.add(o, t)
+    dev.add([_cu(o) for o in outs], [_cu(t) for t in tgts])
+    sh, sd = host.summary(), dev.summary()
+    err = float((sd["ap"] - sh["ap"]).abs().max())
+    assert list(sd) == list(sh) == keys and (err == 0 if algorithm == "11P" else err <= B.AUC_BAR)
+    assert abs(float(sd["ap"][4]) - 1.0) <= B.AUC_BAR and float(sd["ap"].sum()) == float(sd["ap"][4])

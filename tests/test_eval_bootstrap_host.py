@@ -132,6 +132,34 @@ def test_bootstrap_off_is_todays_evaluator():
     for e in (a, b):
         assert e.bootstrap is None and not [k for k in vars(e) if k.startswith("_boot")]      # nothing extra is stored
     assert on.bootstrap == dict(n_boot=8, seed=0, level=0.95) and on._boot_images == 7
+    for e in (a, b):                                                # and the log: no image ids; the classes only for `errors`
+        assert "img" not in e.log and "gt_img" not in e.log and "gt_hoi" in e.log
+    assert "img" in on.log and "gt_img" in on.log and "gt_hoi" in on.log
+    assert "gt_hoi" not in _evaluator(0, "11P", known_object=True).log
+
+
+def test_log_columns_follow_the_options():
+    """A column exists only if its option is on; `errors` and `bootstrap` share the ground-truth classes; every column grows
+    by one tensor per `add`, per cell or per ground-truth pair."""
+    lut = R.make_case(0)[2]
+    columns = lambda **kw: sorted(ev.HOIEvaluator([0] * (int(lut.max()) + 1), lut, **kw).log.parts)
+    cells = ["hoi", "labels", "scores"]
+    assert columns() == cells
+    assert columns(known_object=True) == sorted(cells + ["keep"])
+    assert columns(errors=True) == sorted(cells + ["category", "gt_hoi", "gt_status"])
+    assert columns(bootstrap=4) == sorted(cells + ["img", "gt_hoi", "gt_img"])
+    every = sorted(cells + ["keep", "category", "img", "gt_hoi", "gt_status", "gt_img"])
+    assert columns(known_object=True, errors=True, bootstrap=4) == every
+    e = _evaluator(0, "11P", known_object=True, errors=True, bootstrap=4)
+    tgts = R.make_case(0)[1]
+    assert sorted(e.log.parts) == every and all(len(p) == len(tgts) == 7 for p in e.log.parts.values())
+    n_cells = e.log.column("scores").numel()
+    assert n_cells > 0 and all(e.log.column(k).shape == (n_cells,) for k in ("hoi", "labels", "keep", "category", "img"))
+    assert all(e.log.column(k).shape == (sum(t["hoi"].numel() for t in tgts),) for k in ("gt_hoi", "gt_status", "gt_img"))
+    assert all(t.device.type == "cpu" for p in e.log.parts.values() for t in p)
+    assert e.log.column("img").unique().tolist() == [b for b in range(7) if R.make_case(0)[0][b]["scores"].numel()]
+    empty = ev.HOIEvaluator([0] * (int(lut.max()) + 1), lut, known_object=True).log
+    assert empty.column("keep").dtype == torch.bool and empty.column("scores").shape == (0,) and empty.column("hoi").dtype == torch.int64
 
 
 def test_bootstrap_argument_errors():

@@ -256,3 +256,48 @@ def test_shared_device_ranking_at_the_scan_tile_boundaries():
         assert float(want[0]) == 0.0 and float(want[6]) == 0.0 and float(want[2:6].min()) > 0.0
         empty = ev._class_aps_device(algorithm, sc[:0].cuda(), cl[:0].cuda(), lb[:0].cuda(), 7, ngt_d)
         assert empty.dtype == torch.float64 and torch.equal(empty.cpu(), torch.zeros(7, dtype=torch.float64))
+
+
+def _class_aps_case():
+    """About 200 cells over 7 classes (two-decimal scores: ties inside every class with cells); class 3 without cells, class 5
+    without a positive, class 6 with cells and num_gt 0, class 1 with three ground-truth items more than positives."""
+    sc, cl, lb = _meter_case(3, n=200)
+    num_gt = [int(lb[cl == c].sum()) for c in range(7)]
+    num_gt[1] += 3; num_gt[6] = 0
+    assert all(sc[cl == c].unique().numel() < int((cl == c).sum()) for c in (0, 1, 2, 4, 5, 6)) and not bool((cl == 3).any())
+    assert int(lb[cl == 6].sum()) > 0 and num_gt[5] == 0 and num_gt[1] > int(lb[cl == 1].sum()) > 0
+    return sc, cl, lb, num_gt
+
+
+def test_class_aps_dispatches_on_the_tensors_device():
+    """evaluate._class_aps, the one AP entry of the evaluators, on CPU tensors: the host meter over the same triples, bit for
+    bit, float64 on the host; an empty log gives zeros."""
+    sc, cl, lb, num_gt = _class_aps_case()
+    for algorithm in ("11P", "AUC"):
+        meter = ev.DetectionAPMeter(7, num_gt, algorithm); meter.append(sc, cl, lb)
+        got = ev._class_aps(algorithm, sc, cl, lb, 7, torch.tensor(num_gt))
+        assert got.dtype == torch.float64 and got.device.type == "cpu" and torch.equal(got, meter.eval())
+        assert [float(got[c]) for c in (3, 5, 6)] == [0.0] * 3 and float(got[[0, 1, 2, 4]].min()) > 0.0
+        # appended batch by batch, the per-class lists are the same lists: arrival order inside a class
+        parts = ev.DetectionAPMeter(7, num_gt, algorithm)
+        for lo in range(0, 200, 37):
+            parts.append(sc[lo:lo + 37], cl[lo:lo + 37], lb[lo:lo + 37])
+        assert torch.equal(parts.eval(), got)
+        empty = ev._class_aps(algorithm, sc[:0], cl[:0], lb[:0], 7, torch.tensor(num_gt))
+        assert empty.dtype == torch.float64 and torch.equal(empty, torch.zeros(7, dtype=torch.float64))
+
+
+@pytest.mark.gpu
+def test_class_aps_on_the_device_matches_the_host():
+    """The same log through evaluate._class_aps on the device: '11P' bit for bit, 'AUC' within 1e-12."""
+    sc, cl, lb, num_gt = _class_aps_case()
+    ngt_d = torch.tensor(num_gt, dtype=torch.int64, device="cuda")
+    for algorithm in ("11P", "AUC"):
+        want = ev._class_aps(algorithm, sc, cl, lb, 7, torch.tensor(num_gt))
+        got = ev._class_aps(algorithm, sc.cuda(), cl.cuda(), lb.cuda(), 7, ngt_d)
+        assert got.dtype == torch.float64 and got.is_cuda
+        err = float((got.cpu() - want).abs().max())
+        print("_class_aps %s: device against host %.3e" % (algorithm, err))
+        assert err == 0 if algorithm == "11P" else err <= 1e-12
+        empty = ev._class_aps(algorithm, sc[:0].cuda(), cl[:0].cuda(), lb[:0].cuda(), 7, ngt_d)
+        assert empty.is_cuda and torch.equal(empty.cpu(), torch.zeros(7, dtype=torch.float64))

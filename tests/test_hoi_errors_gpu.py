@@ -222,7 +222,7 @@ def test_trainer_test_with_the_error_breakdown():
     class Recording(ev.DeviceHOIEvaluator):
         def add(self, outputs, targets):
             labels = super().add(outputs, targets)
-            seen.append((labels[0].cpu(), self.last_category[0].cpu(), self.last_gt_status[0].cpu(), self._hoi[-1].cpu().long(),
+            seen.append((labels[0].cpu(), self.last_category[0].cpu(), self.last_gt_status[0].cpu(), self.log.parts["hoi"][-1].cpu().long(),
                          targets[0]["hoi"].cpu()))
             return labels
 

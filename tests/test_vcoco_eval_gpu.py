@@ -18,7 +18,7 @@ import pytest
 import torch
 
 import vcoco_eval_refs as R
-from kernel_test_helpers import _out, _take, _twice
+from kernel_test_helpers import _out, _same_tree, _take, _twice
 from skghoi_amd import _capi, evaluate as ev, synth
 from skghoi_amd.engine import _stream
 from test_evaluate import VCOCO_ACTIONS
@@ -75,6 +75,24 @@ def test_device_evaluator_matches_host_and_toolkit_loop(seed):
     for k in ("mean_s1", "mean_s2", "toolkit_mean_s1", "toolkit_mean_s2"):
         assert abs(s[k] - want[k]) <= 1e-12, k
     assert float(torch.nansum(s["role_ap_s1"])) > 0 and float(torch.nansum(s["role_ap_s2"])) > 0
+
+
+def test_empty_and_degenerate_logs_host_equals_device():
+    """The shared summary() without any `add`, over an image with a person and no cell, and over an image with cells and no
+    person: host and device return the same keys in the same order and equal tensors (every AP is 0 or NaN on both sides)."""
+    outs, tgts, _, _ = R.make_case(3, VCOCO_ACTIONS)
+    assert outs[3]["scores"].numel() == 0 and tgts[3]["persons"].shape[0] == 1
+    assert outs[4]["scores"].numel() > 0 and tgts[4]["persons"].shape[0] == 0
+    for images in ([], [3], [4], [3, 4]):
+        host = ev.VCOCOEvaluator(VCOCO_ACTIONS); dev = ev.DeviceVCOCOEvaluator(VCOCO_ACTIONS)
+        if images:
+            want = host.add([outs[b] for b in images], [tgts[b] for b in images])
+            got = dev.add([_cu(outs[b]) for b in images], [_cu(tgts[b]) for b in images])
+            assert all(torch.equal(g.cpu(), w) for g, w in zip(got, want))
+        sh, sd = host.summary(), dev.summary()
+        assert list(sd) == ["role_ap_s1", "role_ap_s2", "npos", "mean_s1", "toolkit_mean_s1", "mean_s2", "toolkit_mean_s2"]
+        _same_tree(sh, sd, "images %s" % images)
+        assert int(sd["npos"].sum()) == (1 if 3 in images else 0) and float(torch.nan_to_num(sd["role_ap_s2"]).abs().max()) == 0
 
 
 def test_ap_voc_kernel():

@@ -149,8 +149,8 @@ def test_host_meter_auc_is_the_all_point_ap(seed):
     # defaults unchanged, unknown algorithms refused, the evaluators pass the keyword on
     assert ev.DeviceAPMeter(7, device="cpu").algorithm == "11P"
     lut = ev.hico_object_n_verb_to_interaction()
-    assert ev.HOIEvaluator([0] * 600, lut).meter.algorithm == "11P"
-    assert ev.HOIEvaluator([0] * 600, lut, algorithm="AUC").meter.algorithm == "AUC"
+    assert ev.HOIEvaluator([0] * 600, lut).algorithm == "11P"
+    assert ev.HOIEvaluator([0] * 600, lut, algorithm="AUC").algorithm == "AUC"
     for make in (lambda: ev.DeviceAPMeter(7, device="cpu", algorithm="VOC07"),
                  lambda: ev.DeviceHOIEvaluator([0] * 600, lut, device="cpu", algorithm="VOC07")):
         with pytest.raises(ValueError):

@@ -62,9 +62,10 @@ def make_evaluator(log, bootstrap, lut, nat):
     scores, classes, labels, img, gt_cls, gt_img = (t.cuda() for t in log)
     num_gt = torch.bincount(log[4], minlength=NUM_CLS).tolist()
     e = ev.DeviceHOIEvaluator(num_gt, lut, num_anno_train=nat, bootstrap=bootstrap)
-    e._scores, e._hoi, e._labels = [scores], [classes.to(torch.int32)], [labels]
+    e.log.append(scores=scores, hoi=classes.to(torch.int32), labels=labels)
     if bootstrap is not None:
-        e._boot_img, e._boot_gt, e._boot_images = [img], [(gt_cls, gt_img)], N_IMAGES
+        e.log.append(img=img, gt_hoi=gt_cls, gt_img=gt_img)
+        e._boot_images = N_IMAGES
     return e
 
 

@@ -7,7 +7,8 @@
   error breakdown of the Default setting, cells by category and ground-truth pairs by status; --pair-nms THRESH: the same
   numbers again behind the pair NMS over the scored triplets, evaluate.pair_nms -- opt-in, not the reference's;
   --bootstrap N: confidence intervals of every mean from N image-level bootstrap replicates, and with --pair-nms the paired
-  comparison of the filtered run against the plain run)
+  comparison of the filtered run against the plain run; --transh-rng device: the per-image TransH tables generated on the
+  device from each image's detections instead of drawn from the global CPU generator -- opt-in, this project's own rule)
   -> the producer's kept detections judged against the same ground truth (object-detection mAP, maximum recall, pair
   coverage) -> HICO-DET .mat cells / V-COCO-style pickle.
 
@@ -32,14 +33,15 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None, bootstrap=None):
+def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None, bootstrap=None, transh_rng="host"):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_cache_")
     o2v = synth.hico_object_to_verb()
     lut = evaluate.hico_object_n_verb_to_interaction()
     gh = GraphHead(256, 7, 1024, 1024, 117, 49, o2v)
     head = InteractionHead(MultiScaleRoIAlign(["0", "1", "2", "3"], 7, 2), gh, torch.nn.Linear(2048, 1),
-                           torch.nn.Linear(2048, 117), human_idx=49, num_classes=117).to(dev).eval()
+                           torch.nn.Linear(2048, 117), human_idx=49, num_classes=117,
+                           transh_rng=transh_rng, transh_seed=seed).to(dev).eval()
     head.load_state_dict(synth.make_state_dict(117, 256, 7, seed=seed))
     H, W = 800, 1216
     g = torch.Generator().manual_seed(seed)
@@ -135,5 +137,8 @@ if __name__ == "__main__":
                     help="evaluate a second time behind evaluate.pair_nms(outputs, THRESH); with --errors both tables are printed")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="N image-level bootstrap replicates: intervals of every mean; with --pair-nms the paired comparison")
+    ap.add_argument("--transh-rng", choices=("host", "device"), default="host",
+                    help="device: TransH tables keyed by each image's detections (opt-in, not the reference's stream): the "
+                         "numbers no longer depend on --batch or on the order of the images, up to the last bits of the products")
     a = ap.parse_args()
-    main(a.images, a.batch, a.out, errors=a.errors, pair_nms=a.pair_nms, bootstrap=a.bootstrap)
+    main(a.images, a.batch, a.out, errors=a.errors, pair_nms=a.pair_nms, bootstrap=a.bootstrap, transh_rng=a.transh_rng)

@@ -508,6 +508,56 @@ int skg_transh_draw_train_f32(void* torch_cpu_rng_state, int64_t state_bytes, in
                               int64_t* perm_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * TransH tables keyed by image content, generated on the device.  NOT what the reference does (it draws from the global
+ * CPU generator, above): opt-in, this project's own definition -- parity unpinned.  The distribution is the reference's,
+ * U(+-sqrt(6 / (rows + 50))) on 24-bit uniforms; the stream is a counter-based generator whose key is a hash of the image's
+ * selected detections, so an image gets the same tables whatever its position, batch, rank or route, and the host
+ * generator is not touched.  The rule (one implementation, host and device: csrc/skg_transh_philox.h):
+ *   generator  Philox4x32-10: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85; per round
+ *              hi0:lo0 = M0 * c0, hi1:lo1 = M1 * c2, counter <- (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0).
+ *   image key  uint64: h = 0xcbf29ce484222325; per 32-bit word w, in order, h = (h ^ w) * 0x100000001b3; then splitmix64's
+ *              finaliser (h ^= h >> 30, h *= 0xbf58476d1ce4e5b9, h ^= h >> 27, h *= 0x94d049bb133111eb, h ^= h >> 31).
+ *              Words: seed low, seed high, salt low, salt high; the bits of img_h, img_w; n_h, n; per selected node in the
+ *              head's node order (rows box_off .. box_off + n of the packed selection) the bits of x1, y1, x2, y2, the bits
+ *              of the score, the low word of the label.  Philox is keyed with (key low, key high).
+ *   tables     element e of table s (0 = ent [80, 50], 1 = rel [K, 50], 2 = nrm [K, 50]) = word e % 4 of Philox at counter
+ *              (e / 4, s, 0, 0), mapped x -> fadd(fmul((float)(x >> 8) * 2^-24, 2 a), -a), multiply and add rounded
+ *              separately: a value in [-a, a).  a = (float)sqrt(6.0 / (rows + 50)), computed by the caller in double.
+ *   negatives  (training; replaces randperm(n_neg)[:m], HEAD:938-939) rank r among the image's zero cells gets the
+ *              composite c(r) = (uint64(word) << 32) | r, word = word r % 4 of Philox at counter (r / 4, 3, 0, 0); the sample
+ *              is the m ranks with the smallest c, in ascending c -- the composites are distinct, so this is a uniform
+ *              ordered sample without replacement.  m <= n_neg.
+ * Two images with identical selections (and sizes) share their key, hence their tables.
+ *
+ * skg_transh_keys_u64: keys_out [n_active], one key per active image, from the packed selection (boxes [sumN_all, 4],
+ * scores, labels [sumN_all]) and meta.  skg_transh_fill_f32: ent [n_active, 80, 50] and, when need_relations, rel / nrm
+ * [n_active, K, 50] -- the buffers skg_concat_entity_*, skg_transh_scores_f32 and the training plan read; one launch, one
+ * thread per Philox quad, 16-byte stores where the address allows (a table of an odd K ends in half a quad and starts 8
+ * bytes off in every second image).  skg_transh_negatives_i64: per image a the m = pos_off[a + 1] - pos_off[a] sampled
+ * ranks at perm_out[pos_off[a]], as skg_transh_sample_f32 takes them; n_neg [n_active], pos_off [n_active + 1] int32 on
+ * the device.  One workgroup per image (one sweep over the ranks that keeps the composites below a cut in LDS and sorts
+ * them; a radix select over LDS histograms with a sort inside perm_out where the cut does not serve, e.g. m above 4096):
+ * no workspace and no compiled-in cap on m.  The device arrays cannot be checked by the host: an image with m > n_neg
+ * gets n_neg ranks and the rest of its slice is left alone.
+ * Errors: SKG_E_ARG for n_active < 0, K < 1 or a null pointer; SKG_E_LIMIT for K above 2^20; n_active == 0 launches nothing.
+ * The *_host twins run the same rule on host memory (no GPU work; every pointer is a host pointer):
+ * skg_transh_negatives_host_i64 returns SKG_E_ARG for a negative n_neg or an m outside 0 .. n_neg.                    */
+int skg_transh_keys_u64(const float* boxes, const float* scores, const int64_t* labels, const skg_image_meta* meta,
+                        int n_active, uint64_t seed, uint64_t salt, uint64_t* keys_out, void* stream);
+int skg_transh_fill_f32(const uint64_t* keys, int n_active, int K, int need_relations, float a_ent, float a_rel,
+                        float* ent, float* rel, float* nrm, void* stream);
+int skg_transh_negatives_i64(const uint64_t* keys, int n_active, const int32_t* n_neg, const int32_t* pos_off,
+                             int64_t* perm_out, void* stream);
+int skg_transh_philox_host_u32(const uint32_t* counter_host, const uint32_t* key_host, uint32_t* out_host);  /* one block: [4], [2] -> [4] */
+int skg_transh_keys_host_u64(const float* boxes_host, const float* scores_host, const int64_t* labels_host,
+                             const skg_image_meta* meta_host, int n_active, uint64_t seed, uint64_t salt,
+                             uint64_t* keys_host);
+int skg_transh_fill_host_f32(const uint64_t* keys_host, int n_active, int K, int need_relations, float a_ent, float a_rel,
+                             float* ent_host, float* rel_host, float* nrm_host);
+int skg_transh_negatives_host_i64(const uint64_t* keys_host, int n_active, const int32_t* n_neg_host,
+                                  const int32_t* pos_off_host, int64_t* perm_out_host);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * TransH hyperplane scores (heads/TransH/TransH.py:56-106) for every (kept pair, relation):
  *   w = norm(nrm[k]); h = ent[human_idx] - (ent[human_idx].w) w; t = ent[y] - (ent[y].w) w
  *   score[p, k] = || norm(h) + norm(rel[k]) - norm(t) ||_2        (F.normalize eps 1e-12)

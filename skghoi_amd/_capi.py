@@ -194,6 +194,13 @@ PROTOTYPES = {
     "skg_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "skg_transh_draw_f32": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "skg_transh_draw_train_f32": (C.c_int, [_vp, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skg_transh_keys_u64": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "skg_transh_fill_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "skg_transh_negatives_i64": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "skg_transh_philox_host_u32": (C.c_int, [_vp, _vp, _vp]),
+    "skg_transh_keys_host_u64": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_uint64, C.c_uint64, _vp]),
+    "skg_transh_fill_host_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _vp]),
+    "skg_transh_negatives_host_i64": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "skg_gemm_dot_partials": (C.c_int, [C.POINTER(GemmDesc)]),
     "skg_split_weights_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "skg_split_weights_f16x2": (C.c_int, [_vp, C.c_int, C.c_int, _i64, _f32, _vp, _vp]),

@@ -315,6 +315,7 @@ class _Ready:
 
 _INFERENCE_PRECISIONS = (None, "fp32", "fp16x2", "bf16")
 _INFERENCE_ACTIVATIONS = (None, "fp32", "bf16")
+_TRANSH_RNGS = ("host", "device")
 
 
 class InteractionHead(Module):
@@ -350,6 +351,15 @@ class InteractionHead(Module):
           Every result is bit-identical to inference_activations=None under inference_precision="bf16": the consumer
           rounded these operands to bf16 anyway, and the producer stores them with the same conversion.
         Training, validation (eval with targets), the fp32 / fp16x2 paths and engine.debug never take it.
+      transh_rng: str = "host", transh_seed: int = 0 -- keyword-only; where the per-image TransH tables (and, in training,
+        the sampled negatives) come from; plain attributes like inference_precision, together with `transh_salt` (int, 0;
+        the trainer sets it to the epoch number while it trains):
+        "host" (default): the reference's draws from the global CPU generator, bit for bit and draw for draw.
+        "device" (opt-in, this project's own rule: include/skghoi.h): a counter-based generator on the device, keyed by
+          (transh_seed, transh_salt) and the CONTENT of the image's selected detections.  An image gets the same tables
+          whatever its position, batch, rank or route, and the global generator is never touched.  Two images with the
+          same selection share their tables.  Scores of one image in different batch compositions can still differ in the
+          last bits: the products' summation order depends on the batch's row count.
       reference_quirks: bool = True -- reproduce (a) the node-offset bug on skipped images and (b) the
         eval-mode label-list zip with skipped images in a batch > 1 (HEAD:298-310: truncated results / IndexError).
         With False every image gets its own (possibly empty) result.
@@ -359,7 +369,8 @@ class InteractionHead(Module):
                  box_pair_predictor: Module, human_idx: int, num_classes: int, box_nms_thresh: float = 0.5,
                  box_score_thresh: float = 0.2, max_human: int = 15, max_object: int = 15,
                  distributed: bool = False, reference_quirks: bool = True, precision: str = "fp32",
-                 inference_precision: Optional[str] = None, inference_activations: Optional[str] = None) -> None:
+                 inference_precision: Optional[str] = None, inference_activations: Optional[str] = None, *,
+                 transh_rng: str = "host", transh_seed: int = 0) -> None:
         super().__init__()
         self.box_roi_pool = box_roi_pool
         self.box_pair_head = box_pair_head
@@ -382,6 +393,11 @@ class InteractionHead(Module):
         if inference_activations not in _INFERENCE_ACTIVATIONS:
             raise ValueError("inference_activations must be None, 'fp32' or 'bf16'")
         self.inference_activations = inference_activations
+        if transh_rng not in _TRANSH_RNGS:
+            raise ValueError("transh_rng must be 'host' or 'device'")
+        self.transh_rng = transh_rng
+        self.transh_seed = int(transh_seed)
+        self.transh_salt = 0
         self.fused_training = True      # False: training through autograd over per-layer Functions (skghoi_amd/train_graph.py)
         self.grad_mode = "autograd"     # "direct": the fused step writes p.grad itself (skghoi_amd/train_fused.py, StepFn)
         self._engine = None
@@ -429,6 +445,11 @@ class InteractionHead(Module):
             raise ValueError("inference_activations='bf16' needs the bf16 eval path (inference_precision='bf16'); "
                              "inference_precision=%r with precision=%r resolves to %r" % (ip, self.precision, e.eval_precision()))
         e.inference_activations = ia
+        rng = getattr(self, "transh_rng", "host")
+        if rng not in _TRANSH_RNGS:
+            raise ValueError("transh_rng must be 'host' or 'device'")
+        # None: the reference's stream from the global CPU generator; else the (seed, salt) of the device rule
+        e.transh_device = (int(getattr(self, "transh_seed", 0)), int(getattr(self, "transh_salt", 0))) if rng == "device" else None
         return e
 
     # ------------------------------------------------------------------------------------------ HEAD:92-151

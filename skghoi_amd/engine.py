@@ -731,6 +731,7 @@ class HeadEngine:
         self.faithful_skip_offset = faithful_skip_offset
         self.chunk_images = 128     # active images per graph chunk (RNG/GPU overlap + cache-sized intermediates)
         self.debug = False          # keep per-chunk intermediates (spatial46, h_node, node, adjacency) in graph()
+        self.transh_device = None   # (seed, salt): TransH tables generated on the device (skghoi_amd/transh.py); None: host RNG
         self._slots = None
         self._streams = None
         self.n_streams = 2          # chunks alternate over this many side streams: one chunk's kernel tails and small
@@ -1104,7 +1105,8 @@ class HeadEngine:
         # The reference's RNG stream (~27k mt19937 draws per image) is produced by a helper thread, chunk by chunk and
         # in image order, while this thread enqueues GPU work; torch releases the GIL inside the draws.
         drawer = None
-        if tables is None:
+        on_device = tables is None and self.transh_device is not None     # the device rule: no host draw, no upload
+        if tables is None and not on_device:
             drawer = _TableDrawer(self.K, [b - a for a, b in bounds], want_scores,
                                   self._table_slots(max(b - a for a, b in bounds), want_scores))
         try:
@@ -1135,15 +1137,19 @@ class HeadEngine:
             for ci in range(min(lookahead, len(bounds))):
                 phase_a(ci)
             for ci, (a0, a1) in enumerate(bounds):
-                if tables is None:
+                if on_device:
+                    with on_stream(ci):                 # filled on the chunk's stream, right in front of their consumers
+                        t = transh.device_tables(pre.boxes, pre.scores, pre.labels, ctxs[ci]["meta"], a1 - a0, self.K,
+                                                 want_scores, *self.transh_device)
+                elif tables is None:
                     t = drawer.get(ci)
                 else:
                     t = tuple(None if x is None else x[a0:a1] for x in tables)
-                if self.debug:
-                    tabs.append(tuple(None if x is None else x.clone() for x in t))
                 with on_stream(ci):
+                    if self.debug:                      # (device tables are copied on the stream that filled them)
+                        tabs.append(tuple(None if x is None else x.clone() for x in t))
                     self._chunk_phase_b(ctxs.pop(ci), t, pw, pre, enc, PF, sc, keep)
-                    if tables is None:                  # staging slot is free again once its H2D copies are done
+                    if drawer is not None:              # staging slot is free again once its H2D copies are done
                         ev = torch.cuda.Event(); ev.record(current_stream_of(None))
                         drawer.release(ci, ev)
                 if ci + lookahead < len(bounds):

@@ -220,6 +220,7 @@ class SmallBatchRunner:
         p.lt_dev = p.dyn_dev[n_meta:n_meta + 4]
         p.ent_dev = p.dyn_dev[n_meta + 4:].view(torch.float32).view(A, _capi.TRANSH_ENT, _capi.TRANSH_DIM)
         p.h2d_done = None
+        p.transh_keys = None                             # device rule: one key per image, made per call
         # static inputs of the graph
         p.boxes = torch.zeros(max(NA, 1), 4, **f32)[:NA]
         p.scores = torch.zeros(max(NA, 1), **f32)[:NA]
@@ -390,17 +391,20 @@ class SmallBatchRunner:
             # report, from the place a loop without look-ahead sees it -- not this call's, which runs while the results of
             # the forward before are still on their way to the caller
             return False
-        state = torch.get_rng_state()
-        if self._ahead_stage is None:
-            self._ahead_stage = torch.empty(1, _capi.TRANSH_ENT, _capi.TRANSH_DIM)
-        transh.draw_batch(eng.K, 1, need_relations=False, out=(self._ahead_stage, None, None))
+        state = None
+        if eng.transh_device is None:              # (the device rule fills the table in front of the replay: nothing to draw)
+            state = torch.get_rng_state()
+            if self._ahead_stage is None:
+                self._ahead_stage = torch.empty(1, _capi.TRANSH_ENT, _capi.TRANSH_DIM)
+            transh.draw_batch(eng.K, 1, need_relations=False, out=(self._ahead_stage, None, None))
         self._ahead = (detections, detections[0], st, state, side)
         return True
 
     def drop_look_ahead(self):
         """An unclaimed look-ahead is abandoned: the generator goes back to where it stood before its table draw."""
         if self._ahead is not None:
-            torch.set_rng_state(self._ahead[3])
+            if self._ahead[3] is not None:
+                torch.set_rng_state(self._ahead[3])
             self._ahead = None
 
     def _claim_look_ahead(self, detections):
@@ -432,7 +436,7 @@ class SmallBatchRunner:
             st, predrawn = ahead
             self._ent_stage, self._ahead_stage = self._ahead_stage, self._ent_stage      # the table drawn with the look-ahead
             pre = eng.pre_launch_end(st)
-        elif len(detections) == 1:
+        elif len(detections) == 1 and eng.transh_device is None:
             # one image (the reference's evaluation mode): its TransH entity table (HEAD:574-580: ~4 000 normal draws from the
             # global CPU generator, ~20 us) is drawn while the selection kernel runs, not after the counts have arrived with
             # the GPU idle.  Same generator, same order -- unless the image turns out to have no pairs or the call leaves for
@@ -583,16 +587,30 @@ class SmallBatchRunner:
             p.meta_f32[:, 11] = [float(image_shapes[int(b)][1]) for b in act]
             Lt = int(L.sum())
         p.lt_host[0] = Lt
-        if self._predrawn is not None and lay.n_active == 1:
+        on_device = eng.transh_device is not None
+        if on_device:
+            self._undo_predraw()                   # (a draw made before the mode was switched); the entity region is filled
+                                                   # on the device, behind the records' copy
+        elif self._predrawn is not None and lay.n_active == 1:
             p.ent_host[0].copy_(self._ent_stage[0])          # drawn beside the selection kernel (top of this function)
             self._predrawn = None
         else:
             self._undo_predraw()
             transh.draw_batch(eng.K, lay.n_active, need_relations=False, out=(p.ent_host, None, None))
-        p.dyn_dev.copy_(p.dyn_host, non_blocking=True)
+        if on_device:
+            n_rec = lay.n_active * META_WORDS + 4  # meta and cell count only: 63 KB per image less to upload
+            p.dyn_dev[:n_rec].copy_(p.dyn_host[:n_rec], non_blocking=True)
+        else:
+            p.dyn_dev.copy_(p.dyn_host, non_blocking=True)
         if p.h2d_done is None:
             p.h2d_done = torch.cuda.Event()
         p.h2d_done.record(current_stream_of(dev))
+        if on_device:
+            # keyed by this call's selection (the plan's static inputs, filled above) and its records: two small launches
+            if p.transh_keys is None:
+                p.transh_keys = torch.empty(lay.n_active, dtype=torch.int64, device=dev)
+            transh.device_keys(p.boxes, p.scores, p.labels, p.meta_dev, lay.n_active, *eng.transh_device, out=p.transh_keys)
+            transh.device_fill(p.transh_keys, lay.n_active, eng.K, False, out=(p.ent_dev, None, None))
         if p.graph is None:
             self._capture(p)
         p.graph.replay()

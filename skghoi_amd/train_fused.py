@@ -1228,20 +1228,41 @@ def prepare_steps(head, eng, detections, image_shapes, targets, before_sync=None
     n_pos = npos_h.tolist()
     ppi = [int(v) for v in lay.pairs_per_image]
     neg_cnt = [ppi[a] * K - n_pos[a] for a in range(A)]
-    ent_h, rel_h, nrm_h, perm_h = transh.draw_train(K, neg_cnt, n_pos, pin=True)      # tables + randperm heads, natively
-    prep.ent = upload(ent_h); prep.rel = upload(rel_h)
-    prep.nrm = upload(nrm_h)
     pos_off_h = np.zeros(A + 1, np.int32); pos_off_h[1:] = np.cumsum(n_pos)
     M_pos = int(pos_off_h[-1])
     o_perm = (A + 1 + 1) // 2 * 2                                   # one staging block: pos_off | perm (int64, 8-byte aligned)
-    samp_d = E(o_perm + 2 * max(M_pos, 1), torch.int32)
-    sh = torch.empty(o_perm + 2 * max(M_pos, 1), dtype=torch.int32, pin_memory=True)
-    sh[:A + 1] = torch.from_numpy(pos_off_h)
-    sh[o_perm:o_perm + 2 * M_pos].view(torch.int64).copy_(perm_h)
-    samp_d.copy_(sh, non_blocking=True)
+    if eng.transh_device is None:
+        ent_h, rel_h, nrm_h, perm_h = transh.draw_train(K, neg_cnt, n_pos, pin=True)  # tables + randperm heads, natively
+        prep.ent = upload(ent_h); prep.rel = upload(rel_h)
+        prep.nrm = upload(nrm_h)
+        samp_d = E(o_perm + 2 * max(M_pos, 1), torch.int32)
+        sh = torch.empty(o_perm + 2 * max(M_pos, 1), dtype=torch.int32, pin_memory=True)
+        sh[:A + 1] = torch.from_numpy(pos_off_h)
+        sh[o_perm:o_perm + 2 * M_pos].view(torch.int64).copy_(perm_h)
+        samp_d.copy_(sh, non_blocking=True)
+        prep.perm_d = samp_d[o_perm:o_perm + 2 * max(M_pos, 1)].view(torch.int64)
+    else:
+        # the device rule (skghoi_amd/transh.py): tables and sampled negatives are generated where they are read -- no host
+        # draw, no table upload; what still travels is the counts the sampling is sized by, pos_off | n_neg (2 A + 1 ints)
+        if any(n_pos[a] > neg_cnt[a] for a in range(A)):
+            raise _capi.SkgError("TransH sampling: more positives than zero cells in an image (SKG_E_ARG)")
+        ent_h = rel_h = nrm_h = None
+        prep.ent = E((A, _capi.TRANSH_ENT, _capi.TRANSH_DIM), torch.float32)
+        prep.rel = E((A, K, _capi.TRANSH_DIM), torch.float32); prep.nrm = E((A, K, _capi.TRANSH_DIM), torch.float32)
+        keys = E(A, torch.int64)
+        transh.device_keys(pre.boxes, pre.scores, pre.labels, meta, A, *eng.transh_device, out=keys)
+        transh.device_fill(keys, A, K, True, out=(prep.ent, prep.rel, prep.nrm))
+        o_perm = (A + 1 + A + 1) // 2 * 2                             # pos_off | n_neg | perm (filled on the device)
+        samp_d = E(o_perm + 2 * max(M_pos, 1), torch.int32)
+        sh = torch.empty(A + 1 + A, dtype=torch.int32, pin_memory=True)
+        sh[:A + 1] = torch.from_numpy(pos_off_h)
+        sh[A + 1:] = torch.tensor(neg_cnt, dtype=torch.int32)
+        samp_d[:A + 1 + A].copy_(sh, non_blocking=True)
+        prep.perm_d = samp_d[o_perm:o_perm + 2 * max(M_pos, 1)].view(torch.int64)
+        transh.device_negatives(keys, A, samp_d[A + 1:A + 1 + A], samp_d[:A + 1], prep.perm_d)
+        prep.transh_keys = keys
     prep.n_pos, prep.M_pos = n_pos, M_pos
     prep.pos_off_d = samp_d[:A + 1]
-    prep.perm_d = samp_d[o_perm:o_perm + 2 * max(M_pos, 1)].view(torch.int64)
     # ---- TransH term (HEAD:207-235, intended semantics): the scores of the positives and of as many sampled negatives per
     # image, and per image sum_i max(p_i - n_i, -margin).  Nothing here depends on the head's weights (the embeddings are
     # drawn fresh per image), so it belongs to the preparation -- off the step's critical path when prefetched.
@@ -1264,7 +1285,8 @@ def prepare_steps(head, eng, detections, image_shapes, targets, before_sync=None
         prep.slot = arena
     else:
         prep.cross = (pre.boxes, pre.scores, pre.labels, ibuf, grid, keep, sp48, labels_all, prep.ent, prep.rel, prep.nrm,
-                      samp_d, gt_h, gt_o, gt_l, npos_d, scores_all, tr, sws)
+                      samp_d, gt_h, gt_o, gt_l, npos_d, scores_all, tr, sws) + \
+                     ((prep.transh_keys,) if eng.transh_device is not None else ())
         if prep.norm is not None:
             prep.cross += (prep.norm.vals,)
     prep.keep = (ent_h, rel_h, nrm_h, sh, npos_h, hbuf)             # pinned staging: alive until the copies have run

@@ -144,17 +144,23 @@ def graph_train(eng, gh, feat3, image_shapes, pooled, pre, targets, on_counts=No
         # length and the permutation itself is computed from the saved generator state by worker threads with private
         # generators, overlapped with the GPU work below (tests pin the equivalence against the reference goldens).
         tabs, perms = [], []
-        pool = ThreadPoolExecutor(max_workers=min(8, A))
-        for a in range(A):
-            tabs.append(transh.draw_tables(K, need_relations=True))
-            n_neg = ppi[a] * K - n_pos[a]
-            state = torch.get_rng_state()
-            if n_neg > 1:
-                torch.empty(n_neg - 1, dtype=torch.int32).random_()
-            perms.append(pool.submit(_perm, state, n_neg, n_pos[a]))
-        pool.shutdown(wait=False)
-        ent = torch.stack([t[0] for t in tabs]).to(dev); rel = torch.stack([t[1] for t in tabs]).to(dev)
-        nrm = torch.stack([t[2] for t in tabs]).to(dev)
+        if eng.transh_device is not None:
+            # the device rule (skghoi_amd/transh.py): tables and sampled negatives keyed by the image's content
+            tkeys = transh.device_keys(pre.boxes, pre.scores, pre.labels, meta, A, *eng.transh_device)
+            ent, rel, nrm = transh.device_fill(tkeys, A, K, True)
+            perm_dev = transh.device_negatives_counts(tkeys, [ppi[a] * K - n_pos[a] for a in range(A)], n_pos)
+        else:
+            pool = ThreadPoolExecutor(max_workers=min(8, A))
+            for a in range(A):
+                tabs.append(transh.draw_tables(K, need_relations=True))
+                n_neg = ppi[a] * K - n_pos[a]
+                state = torch.get_rng_state()
+                if n_neg > 1:
+                    torch.empty(n_neg - 1, dtype=torch.int32).random_()
+                perms.append(pool.submit(_perm, state, n_neg, n_pos[a]))
+            pool.shutdown(wait=False)
+            ent = torch.stack([t[0] for t in tabs]).to(dev); rel = torch.stack([t[1] for t in tabs]).to(dev)
+            nrm = torch.stack([t[2] for t in tabs]).to(dev)
         scores_all = torch.empty(max(Mp, 1), K, device=dev)
         _capi.check(lib.skg_transh_scores_f32(ent.data_ptr(), rel.data_ptr(), nrm.data_ptr(), K, gh.human_idx,
                                               meta.data_ptr(), A, scores_all.data_ptr(), st), "skg_transh_scores_f32")
@@ -201,7 +207,11 @@ def graph_train(eng, gh, feat3, image_shapes, pooled, pre, targets, on_counts=No
         zero_p, zero_k = torch.nonzero(labels_all == 0).unbind(1)
         neg_cnt = [ppi[a] * K - n_pos[a] for a in range(A)]
         neg_base = np.concatenate([[0], np.cumsum(neg_cnt)])
-        sel = torch.cat([perms[a].result() + int(neg_base[a]) for a in range(A)]).to(dev) if A else None
+        if eng.transh_device is not None:
+            sel = perm_dev + torch.repeat_interleave(torch.from_numpy(neg_base[:A].astype(np.int64)),
+                                                     torch.tensor(n_pos, dtype=torch.int64)).to(dev)
+        else:
+            sel = torch.cat([perms[a].result() + int(neg_base[a]) for a in range(A)]).to(dev) if A else None
         neg_p, neg_k = zero_p[sel], zero_k[sel]
         pos_img = pair_img[pos_p]
         hrow = ent[:, gh.human_idx]                                              # [A, 50]

@@ -1769,6 +1769,9 @@ class Trainer:
         if hasattr(sampler, "set_epoch"):
             sampler.set_epoch(self.epoch)                   # pocket: reshuffle the shards every epoch
         self.net.train()
+        for h in _interaction_heads(self.net):
+            h.transh_salt = self.epoch                      # device-generated TransH tables (transh_rng="device") differ by epoch,
+                                                            # not by order, rank or resume point; the host route ignores it
         if self.train_meter and self.meter is None:
             self.meter = self._new_meter()
         # the default step looks TWO batches ahead (train_step: prefetch / prefetch2): batch i + 2's preparation starts

@@ -946,6 +946,11 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             const char* wb = skg_uniform_ptr(w_base + (int64_t)kt * BK * 4);
 #pragma unroll
             for (int i = 0; i < T; ++i) {
+                // the offsets pass through an empty asm so that their zero-extension stays in the block of the DMA: hoisted
+                // out of the k loop it reaches instruction selection as an opaque 64-bit VGPR pair, and the loop rebuilds
+                // a vector address per DMA (v_lshl_add_u64) instead of taking the scalar base + 32-bit offset form.
+                // No instruction comes of it; the kernels go from 116 to 110 VGPRs (the 64-bit copies are gone)
+                asm volatile("" : "+v"(oa[i]), "+v"(ow[i]));
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ab + oa[i]),
                                                  (__attribute__((address_space(3))) void*)(a_s + i * 16 * BK), 16, 0, 0);
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wb + ow[i]),
@@ -961,7 +966,9 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
             const float* a_s = smem + cur * GT + (wr * 32 * T + li) * BK;
             const float* b_s = smem + 2 * GT + cur * GT + (wc * 32 * T + li) * BK;
             // all fragment reads of this tile first: hipcc waits vmcnt(0) before any ds_read while an LDS-DMA is in
-            // flight, so the next tile's DMA is issued only after them and lands under the MFMAs
+            // flight, so the next tile's DMA is issued only after them.  Per k-tile the ISA is: the ds_read_b128 of
+            // this tile, the global_load_lds_dwordx4 of the next, lgkmcnt(0), all T * T * 16 MFMAs, then vmcnt(0) and
+            // s_barrier -- the wave's own DMA is in flight under its own MFMAs
             float4 a[BK / 8][T], b[BK / 8][T];
 #pragma unroll
             for (int ks = 0; ks < BK / 8; ++ks) {
@@ -991,6 +998,11 @@ __device__ __forceinline__ void skg_gemm_tile(const skg_gemm_desc& d, int block_
                         for (int ni = 0; ni < T; ++ni)
                             acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi][t], bv[ni][t], acc[mi][ni], 0, 0, 0);
             }
+            // the MFMAs touch no memory, so without this fence the scheduler hoists the barrier and its vmcnt(0) to
+            // behind the FIRST of them and the wave sits out its own DMA's round trip before the other MFMAs issue.
+            // This fence and the scalar-base DMA form of stage() belong TOGETHER: measured on the M = 102400 launches,
+            // either one alone is slower than neither (+29 % / +11 %), both are 3-4 % faster (profiles/gemm_prefetch_ab.txt)
+            __builtin_amdgcn_sched_barrier(0);
             __syncthreads();                                          // vmcnt(0) + barrier: next tile landed, this one free
         }
     }

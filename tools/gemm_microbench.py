@@ -1,5 +1,7 @@
 """Developer aid (GPU box): times skg_gemm_f32 on the hot shapes of the 20x20 workload.
-usage: python tools/gemm_microbench.py [reps] [split | head]   (SKG_LIB=<path to .so> selects a kernel build; "split" times
+usage: python tools/gemm_microbench.py [reps] [split | head | shapes MxNxK ...]   (SKG_LIB=<path to .so> selects a kernel
+build; SKG_SMALL_MODE / SKG_SMALL_TILES / SKG_ROUTE_TILES the launcher's developer switches; "shapes" times the listed
+products instead of the built-in list; "split" times
 the fp16x2 split-operand loop and prints its max deviation from the exact fp32 loop; "head" times the launches of the
 B = 256 eval step as the head issues them -- 128-image chunks, N = K = 1024, index patterns of 40 pairs per image --
 one line per launch, for the epilogue knock-out builds of tools/build_variants.sh)"""
@@ -59,6 +61,8 @@ if head:
 
 shapes = [(51200, 1024, 1024, 1), (51200, 1024, 1024, 2), (51200, 1024, 1024, 3), (10240, 1024, 12544, 1),
           (2560, 1024, 1024, 0), (1280, 1024, 1024, 0), (51200, 1024, 256, 1), (199680, 118, 2048, 0)]
+if len(sys.argv) > 3 and sys.argv[2] == "shapes":                   # the caller's own list, BIAS_RELU each
+    shapes = [tuple(int(v) for v in s.split("x")) + (1,) for s in sys.argv[3:]]
 for M, N, K, epi in shapes:
     A = (torch.rand(M, K, generator=g) * 2 - 1).cuda(); W = ((torch.rand(N, K, generator=g) * 2 - 1) / K ** 0.5).cuda()
     b = torch.rand(N, generator=g).cuda(); C = torch.empty(M, N, device="cuda")

@@ -33,6 +33,15 @@ __device__ __forceinline__ float skg_wave_max(float v) {
 // in front of it as fmaxf needs on a loaded value.  Every ReLU of the library goes through here.
 __device__ __forceinline__ float skg_relu(float x) { return __builtin_elementwise_maximum(x, 0.f); }
 
+// IoU of two boxes (x1, y1, x2, y2) as torchvision's box_iou (inter / (a1 + a2 - inter), no eps); compiled without fma
+// contraction -> same decisions as the CPU code.  GT association (skg_post.hip) and the evaluators (skg_eval.hip).
+__device__ __forceinline__ float skg_iou(const float4 a, const float4 b) {
+    const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
+    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
+    const float inter = w * h;
+    return inter / (aa + ab - inter);
+}
+
 // Block-wide sum for 256-thread blocks (4 waves); `red` is a 4-float LDS scratch.  All threads get the result.
 __device__ __forceinline__ float skg_block_sum256(float v, float* red) {
     v = skg_wave_sum(v);
@@ -97,13 +106,16 @@ int skg_gemmx_f32_fused(const skg_gemmx_desc* descs_host, const skg_gemmx_fused*
 
 // ---- several independent launches of one per-row kernel as ONE launch (blockIdx.y picks the call).  A dependent chain of
 // ~100 kernels pays ~4.5 us per kernel boundary whatever the kernel does (a 1-wave kernel takes 4.7 us here): the training
-// plan (skg_train_plan.hip) issues its back-to-back calls of these kernels through the *_multi forms.  Same arithmetic,
-// same results; the calls of one launch must not depend on each other.  n <= SKG_MULTI_MAX.
+// plan (skg_train_plan.hip) issues its back-to-back calls of these kernels through the *_multi forms.  Each stage has ONE
+// kernel, one row body and one check of an args struct: the public one-call entries (skg_rows_mul_relu_f32 / _x,
+// skg_mul_bwd_f32, skg_segment_sum_f32 modes 0 / 1, skg_add_layernorm_f32, skg_layernorm_bwd_f32) fill one struct and go
+// through the same launcher with n = 1.  The calls of one launch must not depend on each other.  n <= SKG_MULTI_MAX.
 #define SKG_MULTI_MAX 4
 struct skg_rows_mul_args {
     const float* P; const int32_t* p_idx; int64_t ldp; const float* Q; const int32_t* q_idx; int64_t ldq; const float* mbias;
     const float* F; const int32_t* f_idx; int64_t ldf; int rows, cols; float* out; int64_t ldo;
-    uint16_t* out16;             // filled by the launcher from the twin map (callers leave it alone)
+    uint16_t* out16;             // filled by the launcher from the twin map (callers leave it alone); skg_rows_mul_relu_x
+                                 // with a bf16 output sets out = NULL and this to the output
 };
 int skg_rows_mul_relu_multi(const skg_rows_mul_args* calls, int n, void* stream);
 struct skg_mul_bwd_args {

@@ -57,13 +57,6 @@
 
 #define EV_MAX_GT 2048            // ground-truth pairs per image the association keeps in LDS
 
-__device__ __forceinline__ float ev_iou(const float4 a, const float4 b) {
-    const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
-    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-    const float inter = w * h;
-    return inter / (aa + ab - inter);
-}
-
 __device__ __forceinline__ uint32_t ev_orderable(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -118,8 +111,8 @@ __global__ __launch_bounds__(256) void skg_eval_associate_kernel(
             float best = -1.f;
             for (int g = 0; g < ng; ++g) {
                 if (gt_hoi[g0 + g] != hoi) continue;
-                const float v = fminf(ev_iou(*reinterpret_cast<const float4*>(gt_h + 4 * (int64_t)(g0 + g)), dh),
-                                      ev_iou(*reinterpret_cast<const float4*>(gt_o + 4 * (int64_t)(g0 + g)), dob));
+                const float v = fminf(skg_iou(*reinterpret_cast<const float4*>(gt_h + 4 * (int64_t)(g0 + g)), dh),
+                                      skg_iou(*reinterpret_cast<const float4*>(gt_o + 4 * (int64_t)(g0 + g)), dob));
                 if (v > best) { best = v; match = g; }       // first maximum, NaN never wins
             }
             if (!(best >= min_iou)) match = -1;
@@ -244,8 +237,8 @@ __global__ __launch_bounds__(256) void skg_eval_hoi_errors_kernel(
                 const int ot = hoi_object[t];
                 if (ot < 0 || ot != oc) continue;            // another object category: no predicate reads this pair
             }
-            const float ih = ev_iou(*reinterpret_cast<const float4*>(gt_h + 4 * (int64_t)(g0 + g)), dh);
-            const float io = ev_iou(*reinterpret_cast<const float4*>(gt_o + 4 * (int64_t)(g0 + g)), dob);
+            const float ih = skg_iou(*reinterpret_cast<const float4*>(gt_h + 4 * (int64_t)(g0 + g)), dh);
+            const float io = skg_iou(*reinterpret_cast<const float4*>(gt_o + 4 * (int64_t)(g0 + g)), dob);
             const bool ch = ih >= min_iou, co = io >= min_iou;       // NaN: false
             if (same) {
                 if (ch && co) { dup = true; atomicOr(&sflag[g], EV_ERR_SCORED); }
@@ -273,8 +266,8 @@ __global__ __launch_bounds__(256) void skg_eval_hoi_errors_kernel(
             const float4 gh = *reinterpret_cast<const float4*>(gt_h + 4 * (int64_t)(g0 + g));
             const float4 go = *reinterpret_cast<const float4*>(gt_o + 4 * (int64_t)(g0 + g));
             for (int p = p0; p < p1; ++p) {
-                if (ev_iou(gh, *reinterpret_cast<const float4*>(boxes_h + 4 * (int64_t)p)) >= min_iou &&
-                    ev_iou(go, *reinterpret_cast<const float4*>(boxes_o + 4 * (int64_t)p)) >= min_iou) {
+                if (skg_iou(gh, *reinterpret_cast<const float4*>(boxes_h + 4 * (int64_t)p)) >= min_iou &&
+                    skg_iou(go, *reinterpret_cast<const float4*>(boxes_o + 4 * (int64_t)p)) >= min_iou) {
                     st = 2;
                     break;
                 }
@@ -630,7 +623,7 @@ __global__ __launch_bounds__(256) void skg_eval_det_match_kernel(
             float best = -1.f;
             for (int j = 0; j < nb; ++j) {
                 if (ssup[j] || scls[j] != c) continue;
-                const float v = ev_iou(sbox[j], db);
+                const float v = skg_iou(sbox[j], db);
                 if (v > best) { best = v; match = j; }       // first maximum, NaN never wins
             }
             if (!(best >= min_iou)) match = -1;
@@ -707,8 +700,8 @@ __global__ __launch_bounds__(256) void skg_eval_pair_cover_kernel(
                 for (int k = 0; k < nk; ++k) {
                     if (sdrop[k]) continue;
                     const int64_t c = sdc[k];
-                    if (c == (int64_t)human_idx && ev_iou(bh, sdb[k]) >= min_iou) { if (nh++ == 0) fh = k0 + k; }
-                    if (c == ob && ev_iou(bo, sdb[k]) >= min_iou) { if (no++ == 0) fo = k0 + k; }
+                    if (c == (int64_t)human_idx && skg_iou(bh, sdb[k]) >= min_iou) { if (nh++ == 0) fh = k0 + k; }
+                    if (c == ob && skg_iou(bo, sdb[k]) >= min_iou) { if (no++ == 0) fo = k0 + k; }
                 }
             }
         }
@@ -842,8 +835,8 @@ __global__ __launch_bounds__(256) void skg_hoi_pair_nms_kernel(
             for (int k = 0; k < PN_SLOTS; ++k) {
                 const int j = k * 64 + lane;
                 if (j <= i || j >= n || !((alive >> k) & 1u)) continue;
-                const float ih = ev_iou(hi, *reinterpret_cast<const float4*>(boxes_h + 4 * pj[k]));
-                const float io = ev_iou(oi, *reinterpret_cast<const float4*>(boxes_o + 4 * pj[k]));
+                const float ih = skg_iou(hi, *reinterpret_cast<const float4*>(boxes_h + 4 * pj[k]));
+                const float io = skg_iou(oi, *reinterpret_cast<const float4*>(boxes_o + 4 * pj[k]));
                 // min: fminf(ih, io) > thresh where both are numbers; a NaN on either side makes it false
                 const bool over = measure == SKG_PAIR_NMS_PRODUCT ? ih * io > thresh : (ih > thresh && io > thresh);
                 if (over) alive &= ~(1u << k);

@@ -80,6 +80,29 @@ __global__ __launch_bounds__(256) void skg_graph_aggregate_kernel(
     }
 }
 
+// Entry checks and launch of both public forms.  half: U and V are bf16 only (8-byte aligned) and U16 / V16 are not read;
+// otherwise U and V are fp32 and U16 / V16 their bf16 twins (or NULL).  train: alpha_out and beta_out are required.
+static int skg_graph_aggregate_launch(const float* dot_partial, int n_partial, int64_t partial_ld, float adj_bias,
+                                      const skg_image_meta* meta, int n_active, const int32_t* hum_img,
+                                      const int32_t* node_img, int sum_h, int sum_n, const float* T_os, const float* T_so,
+                                      int64_t ldt, int cols, void* U, void* V, int64_t ldu, float* adj_out, bool train,
+                                      float* alpha_out, float* beta_out, bool half, uint16_t* U16, uint16_t* V16,
+                                      void* stream) {
+    if (n_active < 0 || sum_h < 0 || sum_n < 0 || n_partial <= 0 || cols <= 0 || (cols & 3)) return SKG_E_ARG;
+    if (sum_h + sum_n == 0) return 0;
+    if (!dot_partial || !meta || !hum_img || !node_img || !T_os || !T_so || !U || !V) return SKG_E_ARG;
+    if (train && (!alpha_out || !beta_out)) return SKG_E_ARG;
+    const uintptr_t amask = half ? 7u : 15u;
+    if ((ldt & 3) || (ldu & 3) || !skg_aligned16(T_os) || !skg_aligned16(T_so) || (((uintptr_t)U) & amask) ||
+        (((uintptr_t)V) & amask))
+        return SKG_E_ALIGN;
+    hipLaunchKernelGGL(skg_graph_aggregate_kernel, dim3(sum_h + sum_n), dim3(256), 0, (hipStream_t)stream, dot_partial,
+                       n_partial, partial_ld, adj_bias, meta, hum_img, node_img, sum_h, T_os, T_so, ldt, cols,
+                       half ? (float*)nullptr : (float*)U, half ? (float*)nullptr : (float*)V, ldu, adj_out, alpha_out,
+                       beta_out, half ? (uint16_t*)U : U16, half ? (uint16_t*)V : V16);
+    return skg_launch_status();
+}
+
 // out_dtype: element type of U and V only (SKG_DTYPE_F32, or SKG_DTYPE_BF16: the fp32 sums rounded once, 8-byte aligned
 // outputs); the inputs and adj_out stay fp32.
 extern "C" int skg_graph_aggregate_x(const float* dot_partial, int n_partial, int64_t partial_ld, float adj_bias,
@@ -87,21 +110,10 @@ extern "C" int skg_graph_aggregate_x(const float* dot_partial, int n_partial, in
                                      const int32_t* node_img, int sum_h, int sum_n, const float* T_os, const float* T_so,
                                      int64_t ldt, int cols, void* U, void* V, int64_t ldu, float* adj_out, int out_dtype,
                                      void* stream) {
-    if (n_active < 0 || sum_h < 0 || sum_n < 0 || n_partial <= 0 || cols <= 0 || (cols & 3)) return SKG_E_ARG;
     if (out_dtype != SKG_DTYPE_F32 && out_dtype != SKG_DTYPE_BF16) return SKG_E_ARG;
-    if (sum_h + sum_n == 0) return 0;
-    if (!dot_partial || !meta || !hum_img || !node_img || !T_os || !T_so || !U || !V) return SKG_E_ARG;
-    const bool half = out_dtype == SKG_DTYPE_BF16;
-    const uintptr_t amask = half ? 7u : 15u;
-    if ((ldt & 3) || (ldu & 3) || !skg_aligned16(T_os) || !skg_aligned16(T_so) || (((uintptr_t)U) & amask) ||
-        (((uintptr_t)V) & amask))
-        return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_graph_aggregate_kernel, dim3(sum_h + sum_n), dim3(256), 0, (hipStream_t)stream, dot_partial,
-                       n_partial, partial_ld, adj_bias, meta, hum_img, node_img, sum_h, T_os, T_so, ldt, cols,
-                       half ? (float*)nullptr : (float*)U, half ? (float*)nullptr : (float*)V, ldu, adj_out,
-                       (float*)nullptr, (float*)nullptr, half ? (uint16_t*)U : (uint16_t*)nullptr,
-                       half ? (uint16_t*)V : (uint16_t*)nullptr);
-    return skg_launch_status();
+    return skg_graph_aggregate_launch(dot_partial, n_partial, partial_ld, adj_bias, meta, n_active, hum_img, node_img, sum_h,
+                                      sum_n, T_os, T_so, ldt, cols, U, V, ldu, adj_out, false, nullptr, nullptr,
+                                      out_dtype == SKG_DTYPE_BF16, nullptr, nullptr, stream);
 }
 
 extern "C" int skg_graph_aggregate_f32(const float* dot_partial, int n_partial, int64_t partial_ld, float adj_bias,
@@ -120,48 +132,17 @@ extern "C" int skg_graph_aggregate_train_f32(const float* dot_partial, int n_par
                                              const int32_t* node_img, int sum_h, int sum_n, const float* T_os,
                                              const float* T_so, int64_t ldt, int cols, float* U, float* V, int64_t ldu,
                                              float* adj_out, float* alpha_out, float* beta_out, void* stream) {
-    if (n_active < 0 || sum_h < 0 || sum_n < 0 || n_partial <= 0 || cols <= 0 || (cols & 3)) return SKG_E_ARG;
-    if (sum_h + sum_n == 0) return 0;
-    if (!dot_partial || !meta || !hum_img || !node_img || !T_os || !T_so || !U || !V || !alpha_out || !beta_out)
-        return SKG_E_ARG;
-    if ((ldt & 3) || (ldu & 3) || !skg_aligned16(T_os) || !skg_aligned16(T_so) || !skg_aligned16(U) ||
-        !skg_aligned16(V))
-        return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_graph_aggregate_kernel, dim3(sum_h + sum_n), dim3(256), 0, (hipStream_t)stream, dot_partial,
-                       n_partial, partial_ld, adj_bias, meta, hum_img, node_img, sum_h, T_os, T_so, ldt, cols, U, V,
-                       ldu, adj_out, alpha_out, beta_out, skg_twin(U), skg_twin(V));
-    return skg_launch_status();
+    return skg_graph_aggregate_launch(dot_partial, n_partial, partial_ld, adj_bias, meta, n_active, hum_img, node_img, sum_h,
+                                      sum_n, T_os, T_so, ldt, cols, U, V, ldu, adj_out, true, alpha_out, beta_out, false,
+                                      skg_twin(U), skg_twin(V), stream);
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
 // nn.LayerNorm(1024) (HEAD:658-659): biased variance, eps inside the sqrt.  One workgroup per row, two passes over
 // registers (mean, then centred sum of squares).
-__global__ __launch_bounds__(256) void skg_layernorm_kernel(const float* __restrict__ x, int64_t ldx,
-                                                            const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, int cols, float eps,
-                                                            float* __restrict__ out, int64_t ldo) {
-    __shared__ float sred[4];
-    const int r = blockIdx.x;
-    const int c = threadIdx.x * 4;
-    const bool in = c < cols;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (in) v = *reinterpret_cast<const float4*>(x + (int64_t)r * ldx + c);
-    const float mean = skg_block_sum256((v.x + v.y) + (v.z + v.w), sred) / (float)cols;
-    float4 dlt = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
-    float sq = in ? (dlt.x * dlt.x + dlt.y * dlt.y) + (dlt.z * dlt.z + dlt.w * dlt.w) : 0.f;
-    const float var = skg_block_sum256(sq, sred) / (float)cols;
-    const float rstd = 1.f / sqrtf(var + eps);
-    if (in) {
-        const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-        const float4 bb = *reinterpret_cast<const float4*>(beta + c);
-        *reinterpret_cast<float4*>(out + (int64_t)r * ldo + c) =
-            make_float4(dlt.x * rstd * g.x + bb.x, dlt.y * rstd * g.y + bb.y, dlt.z * rstd * g.z + bb.z,
-                        dlt.w * rstd * g.w + bb.w);
-    }
-}
-
 // Two LayerNorms in one launch (norm_h on the human rows, norm_o on the node rows: HEAD:912-914, 923-925): workgroups
-// [0, rows0) take the first, the rest the second; per row the same arithmetic as skg_layernorm_kernel, bit for bit.
+// [0, rows0) take the first, the rest the second.  skg_layernorm_f32 is this launch with an empty second segment, so a
+// row gets the same bits from either entry.
 // out16 (skg_layernorm2_x with a bf16 output): the row goes there, rounded once, instead of to out
 struct skg_ln_seg { const float* x; int64_t ldx; const float* gamma; const float* beta; float* out; int64_t ldo; int rows; uint16_t* out16; };
 
@@ -219,13 +200,6 @@ extern "C" int skg_layernorm2_f32(const float* x0, int64_t ldx0, const float* ga
 
 extern "C" int skg_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const float* beta, int rows,
                                  int cols, float eps, float* out, int64_t ldo, void* stream) {
-    if (rows < 0 || cols <= 0 || cols > 1024 || (cols & 3)) return SKG_E_ARG;
-    if (rows == 0) return 0;
-    if (!x || !gamma || !beta || !out) return SKG_E_ARG;
-    if ((ldx & 3) || (ldo & 3) || !skg_aligned16(x) || !skg_aligned16(out) || !skg_aligned16(gamma) ||
-        !skg_aligned16(beta))
-        return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_layernorm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, beta, cols,
-                       eps, out, ldo);
-    return skg_launch_status();
+    return skg_layernorm2_x(x, ldx, gamma, beta, rows, out, ldo, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, cols, eps,
+                            SKG_DTYPE_F32, stream);
 }

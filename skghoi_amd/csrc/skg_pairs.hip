@@ -215,47 +215,12 @@ extern "C" int skg_concat_entity_f32(const float* enc, int64_t ld_enc, const int
 }
 
 // ------------------------------------------------------------------------------------------------ read-out fc_1 * fc_2
-__global__ __launch_bounds__(256) void skg_rows_mul_relu_kernel(const float* __restrict__ P,
-                                                                const int32_t* __restrict__ p_idx, int64_t ldp,
-                                                                const float* __restrict__ Q,
-                                                                const int32_t* __restrict__ q_idx, int64_t ldq,
-                                                                const float* __restrict__ mbias,
-                                                                const float* __restrict__ F,
-                                                                const int32_t* __restrict__ f_idx, int64_t ldf,
-                                                                int cols, float* __restrict__ out, int64_t ldo,
-                                                                uint16_t* __restrict__ out16) {
-    const int r = blockIdx.x;
-    const float* p = P + (int64_t)(p_idx ? p_idx[r] : r) * ldp;
-    const float* q = Q ? Q + (int64_t)(q_idx ? q_idx[r] : r) * ldq : nullptr;
-    const float* f = F + (int64_t)(f_idx ? f_idx[r] : r) * ldf;
-    float* o = out ? out + (int64_t)r * ldo : nullptr;
-    uint16_t* o16 = out16 ? out16 + (int64_t)r * ldo : nullptr;
-    for (int c = threadIdx.x * 4; c < cols; c += 1024) {
-        float4 m = *reinterpret_cast<const float4*>(p + c);
-        if (q) {
-            const float4 t = *reinterpret_cast<const float4*>(q + c);
-            m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
-        }
-        if (mbias) {
-            const float4 t = *reinterpret_cast<const float4*>(mbias + c);
-            m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
-        }
-        const float4 v = *reinterpret_cast<const float4*>(f + c);
-        const float4 res = make_float4(skg_relu(m.x * v.x), skg_relu(m.y * v.y), skg_relu(m.z * v.z), skg_relu(m.w * v.w));
-        if (o) *reinterpret_cast<float4*>(o + c) = res;
-        if (o16) skg_store_twin4(o16 + c, res);
-    }
-}
-
-struct skg_rows_mul_pack { skg_rows_mul_args a[SKG_MULTI_MAX]; };
-__global__ __launch_bounds__(256) void skg_rows_mul_relu_multi_kernel(const skg_rows_mul_pack pk) {
-    const skg_rows_mul_args& a = pk.a[blockIdx.y];
-    const int r = blockIdx.x;
-    if (r >= a.rows) return;
+// out[r] = relu((P[p_idx[r]] + Q[q_idx[r]] + mbias) * F[f_idx[r]]), row r of one call.  out NULL: bf16 output only (out16).
+__device__ __forceinline__ void skg_rows_mul_relu_row(const skg_rows_mul_args& a, int r) {
     const float* p = a.P + (int64_t)(a.p_idx ? a.p_idx[r] : r) * a.ldp;
     const float* q = a.Q ? a.Q + (int64_t)(a.q_idx ? a.q_idx[r] : r) * a.ldq : nullptr;
     const float* f = a.F + (int64_t)(a.f_idx ? a.f_idx[r] : r) * a.ldf;
-    float* o = a.out + (int64_t)r * a.ldo;
+    float* o = a.out ? a.out + (int64_t)r * a.ldo : nullptr;
     uint16_t* o16 = a.out16 ? a.out16 + (int64_t)r * a.ldo : nullptr;
     for (int c = threadIdx.x * 4; c < a.cols; c += 1024) {
         float4 m = *reinterpret_cast<const float4*>(p + c);
@@ -269,30 +234,51 @@ __global__ __launch_bounds__(256) void skg_rows_mul_relu_multi_kernel(const skg_
         }
         const float4 v = *reinterpret_cast<const float4*>(f + c);
         const float4 res = make_float4(skg_relu(m.x * v.x), skg_relu(m.y * v.y), skg_relu(m.z * v.z), skg_relu(m.w * v.w));
-        *reinterpret_cast<float4*>(o + c) = res;
+        if (o) *reinterpret_cast<float4*>(o + c) = res;
         if (o16) skg_store_twin4(o16 + c, res);
     }
 }
 
-int skg_rows_mul_relu_multi(const skg_rows_mul_args* calls, int n, void* stream) {
+struct skg_rows_mul_pack { skg_rows_mul_args a[SKG_MULTI_MAX]; };
+__global__ __launch_bounds__(256) void skg_rows_mul_relu_multi_kernel(const skg_rows_mul_pack pk) {
+    const skg_rows_mul_args a = pk.a[blockIdx.y];           // (a copy: all its scalar loads issue at once, up front)
+    if ((int)blockIdx.x >= a.rows) return;                 // (uniform per workgroup)
+    skg_rows_mul_relu_row(a, (int)blockIdx.x);
+}
+
+// Checks one call and fills its out16.  out_align 16: the output is a.out (fp32; its bf16 twin from the map, if any);
+// out_align 8: the caller set a.out = NULL and a.out16 = the bf16-only output.
+static int skg_rows_mul_relu_check(skg_rows_mul_args& a, uintptr_t out_align) {
+    if (a.rows < 0 || a.cols <= 0 || (a.cols & 3)) return SKG_E_ARG;
+    if (a.rows == 0) return 0;
+    const void* out = out_align == 8 ? (const void*)a.out16 : (const void*)a.out;
+    if (!a.P || !a.F || !out) return SKG_E_ARG;
+    if ((a.ldp & 3) || (a.ldf & 3) || (a.ldo & 3) || (a.Q && (a.ldq & 3))) return SKG_E_ALIGN;
+    if (!skg_aligned16(a.P) || !skg_aligned16(a.F) || (((uintptr_t)out) & (out_align - 1)) || !skg_aligned16(a.Q) ||
+        !skg_aligned16(a.mbias))                           // (null Q / mbias count as aligned)
+        return SKG_E_ALIGN;
+    if (out_align != 8) a.out16 = skg_twin(a.out);
+    return 0;
+}
+
+static int skg_rows_mul_relu_launch(const skg_rows_mul_args* calls, int n, uintptr_t out_align, void* stream) {
     if (!calls || n < 1 || n > SKG_MULTI_MAX) return SKG_E_ARG;
     skg_rows_mul_pack pk;
     int m = 0, rows = 0;
     for (int i = 0; i < n; ++i) {
-        const skg_rows_mul_args& a = calls[i];
-        if (a.rows < 0 || a.cols <= 0 || (a.cols & 3)) return SKG_E_ARG;
-        if (a.rows == 0) continue;
-        if (!a.P || !a.F || !a.out) return SKG_E_ARG;
-        if ((a.ldp & 3) || (a.ldf & 3) || (a.ldo & 3) || (a.Q && (a.ldq & 3))) return SKG_E_ALIGN;
-        if (!skg_aligned16(a.P) || !skg_aligned16(a.F) || !skg_aligned16(a.out) || !skg_aligned16(a.Q) || !skg_aligned16(a.mbias))
-            return SKG_E_ALIGN;
-        pk.a[m] = a;
-        pk.a[m++].out16 = skg_twin(a.out);
-        rows = a.rows > rows ? a.rows : rows;
+        pk.a[m] = calls[i];
+        if (const int e = skg_rows_mul_relu_check(pk.a[m], out_align)) return e;
+        if (pk.a[m].rows == 0) continue;
+        rows = pk.a[m].rows > rows ? pk.a[m].rows : rows;
+        ++m;
     }
     if (m == 0) return 0;
     hipLaunchKernelGGL(skg_rows_mul_relu_multi_kernel, dim3(rows, m), dim3(256), 0, (hipStream_t)stream, pk);
     return skg_launch_status();
+}
+
+int skg_rows_mul_relu_multi(const skg_rows_mul_args* calls, int n, void* stream) {
+    return skg_rows_mul_relu_launch(calls, n, 16, stream);
 }
 
 // out_dtype as in skg_concat_entity_x
@@ -300,18 +286,11 @@ extern "C" int skg_rows_mul_relu_x(const float* P, const int32_t* p_idx, int64_t
                                    const int32_t* q_idx, int64_t ldq, const float* mbias, const float* F,
                                    const int32_t* f_idx, int64_t ldf, int rows, int cols, void* out, int64_t ldo,
                                    int out_dtype, void* stream) {
-    if (rows < 0 || cols <= 0 || (cols & 3) || (out_dtype != SKG_DTYPE_F32 && out_dtype != SKG_DTYPE_BF16)) return SKG_E_ARG;
-    if (rows == 0) return 0;
-    if (!P || !F || !out) return SKG_E_ARG;
+    if (out_dtype != SKG_DTYPE_F32 && out_dtype != SKG_DTYPE_BF16) return SKG_E_ARG;
     const bool half = out_dtype == SKG_DTYPE_BF16;
-    if ((ldp & 3) || (ldf & 3) || (ldo & 3) || (Q && (ldq & 3))) return SKG_E_ALIGN;
-    if (!skg_aligned16(P) || !skg_aligned16(F) || (half ? (((uintptr_t)out) & 7u) != 0 : !skg_aligned16(out)) ||
-        (Q && !skg_aligned16(Q)) || (mbias && !skg_aligned16(mbias)))
-        return SKG_E_ALIGN;
-    float* o32 = half ? nullptr : (float*)out;
-    hipLaunchKernelGGL(skg_rows_mul_relu_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, p_idx, ldp, Q,
-                       q_idx, ldq, mbias, F, f_idx, ldf, cols, o32, ldo, half ? (uint16_t*)out : skg_twin(o32));
-    return skg_launch_status();
+    const skg_rows_mul_args a = {P, p_idx, ldp, Q, q_idx, ldq, mbias, F, f_idx, ldf, rows, cols,
+                                 half ? nullptr : (float*)out, ldo, half ? (uint16_t*)out : nullptr};
+    return skg_rows_mul_relu_launch(&a, 1, half ? 8 : 16, stream);
 }
 
 extern "C" int skg_rows_mul_relu_f32(const float* P, const int32_t* p_idx, int64_t ldp, const float* Q,

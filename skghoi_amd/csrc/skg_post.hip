@@ -191,16 +191,8 @@ extern "C" const char* skg_build_info(void) { return "libskghoi_hip gfx950 " __V
 
 // ------------------------------------------------------------------------------------------------ GT association
 // GraphHead.associate_with_ground_truth (HEAD:703-719) for every active image in one launch: labels[p, verb] = 1 where
-// min(IoU(box_h, gt_h), IoU(box_o, gt_o)) >= thresh for a ground-truth pair with that verb.  IoU as torchvision's
-// box_iou (inter / (a1 + a2 - inter), no eps); compiled without fma contraction -> same decisions as the CPU code.
+// min(IoU(box_h, gt_h), IoU(box_o, gt_o)) >= thresh for a ground-truth pair with that verb (skg_iou, skg_common.h).
 // labels must be zero-filled by the caller; npos[a] = number of non-zero labels of image a (HEAD:936, 166).
-__device__ __forceinline__ float skg_iou(const float4 a, const float4 b) {
-    const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
-    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-    const float inter = w * h;
-    return inter / (aa + ab - inter);
-}
-
 __global__ __launch_bounds__(256) void skg_associate_kernel(const float* __restrict__ boxes,
                                                             const skg_image_meta* __restrict__ meta,
                                                             const int64_t* __restrict__ x_keep,

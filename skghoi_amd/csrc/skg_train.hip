@@ -40,43 +40,42 @@ extern "C" int skg_rowdot_f32(const float* X, int64_t ld, const float* w, int ro
 
 // ------------------------------------------------------------------------------------------------ add + LayerNorm
 // x = a + b (node + message, HEAD:912-914 / 923-925), y = LayerNorm(x); keeps x and (mean, rstd) for the backward.
-__device__ __forceinline__ void skg_add_layernorm_row(const float* __restrict__ a, int64_t lda,
-                                                      const float* __restrict__ b, int64_t ldb,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      float eps, float* __restrict__ xsum, float* __restrict__ y,
-                                                      float* __restrict__ stats, int r, uint16_t* __restrict__ y16) {
+__device__ __forceinline__ void skg_add_layernorm_row(const skg_add_layernorm_args& s, float eps, int r) {
     __shared__ float sred[4];
     const int c = threadIdx.x * 4;
-    const float4 va = *reinterpret_cast<const float4*>(a + (int64_t)r * lda + c);
-    const float4 vb = *reinterpret_cast<const float4*>(b + (int64_t)r * ldb + c);
+    const float4 va = *reinterpret_cast<const float4*>(s.a + (int64_t)r * s.lda + c);
+    const float4 vb = *reinterpret_cast<const float4*>(s.b + (int64_t)r * s.ldb + c);
     const float4 v = make_float4(va.x + vb.x, va.y + vb.y, va.z + vb.z, va.w + vb.w);
     const float mean = skg_block_sum256((v.x + v.y) + (v.z + v.w), sred) / (float)TR_COLS;
     const float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
     const float var = skg_block_sum256((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w), sred) / (float)TR_COLS;
     const float rstd = 1.f / sqrtf(var + eps);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-    const float4 bb = *reinterpret_cast<const float4*>(beta + c);
-    *reinterpret_cast<float4*>(xsum + (int64_t)r * TR_COLS + c) = v;
+    const float4 g = *reinterpret_cast<const float4*>(s.gamma + c);
+    const float4 bb = *reinterpret_cast<const float4*>(s.beta + c);
+    *reinterpret_cast<float4*>(s.xsum + (int64_t)r * TR_COLS + c) = v;
     const float4 yo = make_float4(d.x * rstd * g.x + bb.x, d.y * rstd * g.y + bb.y, d.z * rstd * g.z + bb.z, d.w * rstd * g.w + bb.w);
-    *reinterpret_cast<float4*>(y + (int64_t)r * TR_COLS + c) = yo;
-    if (y16) skg_store_twin4(y16 + (int64_t)r * TR_COLS + c, yo);
-    if (threadIdx.x == 0) { stats[2 * r] = mean; stats[2 * r + 1] = rstd; }
-}
-
-__global__ __launch_bounds__(256) void skg_add_layernorm_kernel(const float* __restrict__ a, int64_t lda,
-                                                                const float* __restrict__ b, int64_t ldb,
-                                                                const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, float eps,
-                                                                float* __restrict__ xsum, float* __restrict__ y,
-                                                                float* __restrict__ stats, uint16_t* __restrict__ y16) {
-    skg_add_layernorm_row(a, lda, b, ldb, gamma, beta, eps, xsum, y, stats, (int)blockIdx.x, y16);
+    *reinterpret_cast<float4*>(s.y + (int64_t)r * TR_COLS + c) = yo;
+    if (s.y16) skg_store_twin4(s.y16 + (int64_t)r * TR_COLS + c, yo);
+    if (threadIdx.x == 0) { s.stats[2 * r] = mean; s.stats[2 * r + 1] = rstd; }
 }
 
 struct skg_add_layernorm_pack { skg_add_layernorm_args a[SKG_MULTI_MAX]; };
 __global__ __launch_bounds__(256) void skg_add_layernorm_multi_kernel(const skg_add_layernorm_pack pk, float eps) {
-    const skg_add_layernorm_args& a = pk.a[blockIdx.y];
+    const skg_add_layernorm_args a = pk.a[blockIdx.y];       // (a copy: all its scalar loads issue at once, up front)
     if ((int)blockIdx.x >= a.rows) return;                 // (uniform per workgroup)
-    skg_add_layernorm_row(a.a, a.lda, a.b, a.ldb, a.gamma, a.beta, eps, a.xsum, a.y, a.stats, (int)blockIdx.x, a.y16);
+    skg_add_layernorm_row(a, eps, (int)blockIdx.x);
+}
+
+// Checks one call and fills its y16 from the twin map
+static int skg_add_layernorm_check(skg_add_layernorm_args& a) {
+    if (a.rows < 0) return SKG_E_ARG;
+    if (a.rows == 0) return 0;
+    if (!a.a || !a.b || !a.gamma || !a.beta || !a.xsum || !a.y || !a.stats) return SKG_E_ARG;
+    if ((a.lda & 3) || (a.ldb & 3) || !skg_aligned16(a.a) || !skg_aligned16(a.b) || !skg_aligned16(a.gamma) ||
+        !skg_aligned16(a.beta) || !skg_aligned16(a.xsum) || !skg_aligned16(a.y))
+        return SKG_E_ALIGN;
+    a.y16 = skg_twin(a.y);
+    return 0;
 }
 
 int skg_add_layernorm_multi(const skg_add_layernorm_args* calls, int n, float eps, void* stream) {
@@ -84,16 +83,11 @@ int skg_add_layernorm_multi(const skg_add_layernorm_args* calls, int n, float ep
     skg_add_layernorm_pack pk;
     int m = 0, rows = 0;
     for (int i = 0; i < n; ++i) {
-        const skg_add_layernorm_args& a = calls[i];
-        if (a.rows < 0) return SKG_E_ARG;
-        if (a.rows == 0) continue;
-        if (!a.a || !a.b || !a.gamma || !a.beta || !a.xsum || !a.y || !a.stats) return SKG_E_ARG;
-        if ((a.lda & 3) || (a.ldb & 3) || !skg_aligned16(a.a) || !skg_aligned16(a.b) || !skg_aligned16(a.gamma) ||
-            !skg_aligned16(a.beta) || !skg_aligned16(a.xsum) || !skg_aligned16(a.y))
-            return SKG_E_ALIGN;
-        pk.a[m] = a;
-        pk.a[m++].y16 = skg_twin(a.y);
-        rows = a.rows > rows ? a.rows : rows;
+        pk.a[m] = calls[i];
+        if (const int e = skg_add_layernorm_check(pk.a[m])) return e;
+        if (pk.a[m].rows == 0) continue;
+        rows = pk.a[m].rows > rows ? pk.a[m].rows : rows;
+        ++m;
     }
     if (m == 0) return 0;
     hipLaunchKernelGGL(skg_add_layernorm_multi_kernel, dim3(rows, m), dim3(256), 0, (hipStream_t)stream, pk, eps);
@@ -103,107 +97,84 @@ int skg_add_layernorm_multi(const skg_add_layernorm_args* calls, int n, float ep
 extern "C" int skg_add_layernorm_f32(const float* a, int64_t lda, const float* b, int64_t ldb, const float* gamma,
                                      const float* beta, int rows, float eps, float* xsum, float* y, float* stats,
                                      void* stream) {
-    if (rows < 0) return SKG_E_ARG;
-    if (rows == 0) return 0;
-    if (!a || !b || !gamma || !beta || !xsum || !y || !stats) return SKG_E_ARG;
-    if ((lda & 3) || (ldb & 3) || !skg_aligned16(a) || !skg_aligned16(b) || !skg_aligned16(gamma) ||
-        !skg_aligned16(beta) || !skg_aligned16(xsum) || !skg_aligned16(y))
-        return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_add_layernorm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, gamma,
-                       beta, eps, xsum, y, stats, skg_twin(y));
-    return skg_launch_status();
+    const skg_add_layernorm_args s = {a, lda, b, ldb, gamma, beta, rows, xsum, y, stats};
+    return skg_add_layernorm_multi(&s, 1, eps, stream);
 }
 
 // dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma,  xhat = (x - mean) * rstd.
-__device__ __forceinline__ void skg_layernorm_bwd_row(const float* __restrict__ dy, int64_t lddy,
-                                                      const float* __restrict__ x, const float* __restrict__ stats,
-                                                      const float* __restrict__ gamma, float* __restrict__ dx,
-                                                      const float* __restrict__ relu_src, float* __restrict__ dx_masked,
-                                                      int r, uint16_t* __restrict__ dx16, uint16_t* __restrict__ dxm16) {
+__device__ __forceinline__ void skg_layernorm_bwd_row(const skg_layernorm_bwd_args& a, int r) {
     __shared__ float sred[4];
     const int c = threadIdx.x * 4;
-    const float mean = stats[2 * r], rstd = stats[2 * r + 1];
-    const float4 vx = *reinterpret_cast<const float4*>(x + (int64_t)r * TR_COLS + c);
-    const float4 vd = *reinterpret_cast<const float4*>(dy + (int64_t)r * lddy + c);
-    const float4 gm = *reinterpret_cast<const float4*>(gamma + c);
+    const float mean = a.stats[2 * r], rstd = a.stats[2 * r + 1];
+    const float4 vx = *reinterpret_cast<const float4*>(a.x + (int64_t)r * TR_COLS + c);
+    const float4 vd = *reinterpret_cast<const float4*>(a.dy + (int64_t)r * a.lddy + c);
+    const float4 gm = *reinterpret_cast<const float4*>(a.gamma + c);
     const float4 xh = make_float4((vx.x - mean) * rstd, (vx.y - mean) * rstd, (vx.z - mean) * rstd, (vx.w - mean) * rstd);
     const float4 g = make_float4(vd.x * gm.x, vd.y * gm.y, vd.z * gm.z, vd.w * gm.w);
     const float c1 = skg_block_sum256((g.x + g.y) + (g.z + g.w), sred) / (float)TR_COLS;
     const float c2 = skg_block_sum256((g.x * xh.x + g.y * xh.y) + (g.z * xh.z + g.w * xh.w), sred) / (float)TR_COLS;
     const float4 o = make_float4(rstd * (g.x - c1 - xh.x * c2), rstd * (g.y - c1 - xh.y * c2),
                                  rstd * (g.z - c1 - xh.z * c2), rstd * (g.w - c1 - xh.w * c2));
-    *reinterpret_cast<float4*>(dx + (int64_t)r * TR_COLS + c) = o;
-    if (dx16) skg_store_twin4(dx16 + (int64_t)r * TR_COLS + c, o);
-    if (dx_masked) {
-        const float4 m = *reinterpret_cast<const float4*>(relu_src + (int64_t)r * TR_COLS + c);
+    *reinterpret_cast<float4*>(a.dx + (int64_t)r * TR_COLS + c) = o;
+    if (a.dx16) skg_store_twin4(a.dx16 + (int64_t)r * TR_COLS + c, o);
+    if (a.dx_masked) {
+        const float4 m = *reinterpret_cast<const float4*>(a.relu_src + (int64_t)r * TR_COLS + c);
         const float4 om = make_float4(m.x > 0.f ? o.x : 0.f, m.y > 0.f ? o.y : 0.f, m.z > 0.f ? o.z : 0.f, m.w > 0.f ? o.w : 0.f);
-        *reinterpret_cast<float4*>(dx_masked + (int64_t)r * TR_COLS + c) = om;
-        if (dxm16) skg_store_twin4(dxm16 + (int64_t)r * TR_COLS + c, om);
+        *reinterpret_cast<float4*>(a.dx_masked + (int64_t)r * TR_COLS + c) = om;
+        if (a.dx_masked16) skg_store_twin4(a.dx_masked16 + (int64_t)r * TR_COLS + c, om);
     }
-}
-
-__global__ __launch_bounds__(256) void skg_layernorm_bwd_kernel(const float* __restrict__ dy, int64_t lddy,
-                                                                const float* __restrict__ x,
-                                                                const float* __restrict__ stats,
-                                                                const float* __restrict__ gamma,
-                                                                float* __restrict__ dx,
-                                                                const float* __restrict__ relu_src,
-                                                                float* __restrict__ dx_masked,
-                                                                uint16_t* __restrict__ dx16, uint16_t* __restrict__ dxm16) {
-    skg_layernorm_bwd_row(dy, lddy, x, stats, gamma, dx, relu_src, dx_masked, (int)blockIdx.x, dx16, dxm16);
 }
 
 // dgamma[c] = sum_r dy[r, c] * xhat[r, c],  dbeta[c] = sum_r dy[r, c]: one thread per column and row group, rows in order.
 // 64 columns x 16 row groups per workgroup (16 workgroups of 1024 threads): rows r = g, g + 16, ... per group, groups added
 // in a fixed tree.  (Four row groups walked ~80 node rows in 20 dependent round trips: 14 us for 0.7 MB; sixteen: 5.)
 #define TR_RG 16
-__device__ __forceinline__ void skg_layernorm_param_grad_cols(const float* __restrict__ dy, int64_t lddy,
-                                                              const float* __restrict__ x,
-                                                              const float* __restrict__ stats, int rows,
-                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                              int blk) {
+__device__ __forceinline__ void skg_layernorm_param_grad_cols(const skg_layernorm_bwd_args& a, int blk) {
     __shared__ float sg_s[TR_RG][64], sb_s[TR_RG][64];
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c = blk * 64 + cl;
     float sg = 0.f, sb = 0.f;
-    for (int r = g; r < rows; r += TR_RG) {
-        const float d = dy[(int64_t)r * lddy + c];
-        sg += d * ((x[(int64_t)r * TR_COLS + c] - stats[2 * r]) * stats[2 * r + 1]);
+    for (int r = g; r < a.rows; r += TR_RG) {
+        const float d = a.dy[(int64_t)r * a.lddy + c];
+        sg += d * ((a.x[(int64_t)r * TR_COLS + c] - a.stats[2 * r]) * a.stats[2 * r + 1]);
         sb += d;
     }
     sg_s[g][cl] = sg; sb_s[g][cl] = sb;
     __syncthreads();
     if (g == 0) {
-        float a = 0.f, b = 0.f;
+        float sa = 0.f, b = 0.f;
 #pragma unroll
         for (int q = 0; q < TR_RG; q += 4) {
-            a += (sg_s[q][cl] + sg_s[q + 1][cl]) + (sg_s[q + 2][cl] + sg_s[q + 3][cl]);
+            sa += (sg_s[q][cl] + sg_s[q + 1][cl]) + (sg_s[q + 2][cl] + sg_s[q + 3][cl]);
             b += (sb_s[q][cl] + sb_s[q + 1][cl]) + (sb_s[q + 2][cl] + sb_s[q + 3][cl]);
         }
-        dgamma[c] = a;
-        dbeta[c] = b;
+        a.dgamma[c] = sa;
+        a.dbeta[c] = b;
     }
-}
-
-__global__ __launch_bounds__(64 * TR_RG) void skg_layernorm_param_grad_kernel(const float* __restrict__ dy, int64_t lddy,
-                                                                       const float* __restrict__ x,
-                                                                       const float* __restrict__ stats, int rows,
-                                                                       float* __restrict__ dgamma,
-                                                                       float* __restrict__ dbeta) {
-    skg_layernorm_param_grad_cols(dy, lddy, x, stats, rows, dgamma, dbeta, (int)blockIdx.x);
 }
 
 // Both LayerNorms of the step in two launches instead of four: (a) every row's input gradient, (b) the parameter gradients
 struct skg_layernorm_bwd_pack { skg_layernorm_bwd_args a[SKG_MULTI_MAX]; };
 __global__ __launch_bounds__(256) void skg_layernorm_bwd_multi_kernel(const skg_layernorm_bwd_pack pk) {
-    const skg_layernorm_bwd_args& a = pk.a[blockIdx.y];
+    const skg_layernorm_bwd_args a = pk.a[blockIdx.y];       // (a copy: all its scalar loads issue at once, up front)
     if ((int)blockIdx.x >= a.rows) return;                 // (uniform per workgroup)
-    skg_layernorm_bwd_row(a.dy, a.lddy, a.x, a.stats, a.gamma, a.dx, a.relu_src, a.dx_masked, (int)blockIdx.x, a.dx16,
-                          a.dx_masked16);
+    skg_layernorm_bwd_row(a, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(64 * TR_RG) void skg_layernorm_param_grad_multi_kernel(const skg_layernorm_bwd_pack pk) {
-    const skg_layernorm_bwd_args& a = pk.a[blockIdx.y];
-    skg_layernorm_param_grad_cols(a.dy, a.lddy, a.x, a.stats, a.rows, a.dgamma, a.dbeta, (int)blockIdx.x);
+    const skg_layernorm_bwd_args a = pk.a[blockIdx.y];
+    skg_layernorm_param_grad_cols(a, (int)blockIdx.x);
+}
+
+// Checks one call and fills its twins.  A call without rows is still checked in full: its parameter gradients are zeroed.
+static int skg_layernorm_bwd_check(skg_layernorm_bwd_args& a) {
+    if (a.rows < 0) return SKG_E_ARG;
+    if (!a.dy || !a.x || !a.stats || !a.gamma || !a.dx || !a.dgamma || !a.dbeta || (a.dx_masked && !a.relu_src)) return SKG_E_ARG;
+    if ((a.lddy & 3) || !skg_aligned16(a.dy) || !skg_aligned16(a.x) || !skg_aligned16(a.gamma) || !skg_aligned16(a.dx) ||
+        !skg_aligned16(a.relu_src) || !skg_aligned16(a.dx_masked))
+        return SKG_E_ALIGN;
+    a.dx16 = skg_twin(a.dx);
+    a.dx_masked16 = a.dx_masked ? skg_twin(a.dx_masked) : nullptr;
+    return 0;
 }
 
 int skg_layernorm_bwd_multi(const skg_layernorm_bwd_args* calls, int n, void* stream) {
@@ -211,16 +182,9 @@ int skg_layernorm_bwd_multi(const skg_layernorm_bwd_args* calls, int n, void* st
     skg_layernorm_bwd_pack pk;
     int rows = 0;
     for (int i = 0; i < n; ++i) {
-        const skg_layernorm_bwd_args& a = calls[i];
-        if (a.rows < 0) return SKG_E_ARG;
-        if (!a.dy || !a.x || !a.stats || !a.gamma || !a.dx || !a.dgamma || !a.dbeta || (a.dx_masked && !a.relu_src)) return SKG_E_ARG;
-        if ((a.lddy & 3) || !skg_aligned16(a.dy) || !skg_aligned16(a.x) || !skg_aligned16(a.gamma) || !skg_aligned16(a.dx) ||
-            !skg_aligned16(a.relu_src) || !skg_aligned16(a.dx_masked))
-            return SKG_E_ALIGN;
-        pk.a[i] = a;
-        pk.a[i].dx16 = skg_twin(a.dx);
-        pk.a[i].dx_masked16 = a.dx_masked ? skg_twin(a.dx_masked) : nullptr;
-        rows = a.rows > rows ? a.rows : rows;
+        pk.a[i] = calls[i];
+        if (const int e = skg_layernorm_bwd_check(pk.a[i])) return e;
+        rows = pk.a[i].rows > rows ? pk.a[i].rows : rows;
     }
     if (rows)
         hipLaunchKernelGGL(skg_layernorm_bwd_multi_kernel, dim3(rows, n), dim3(256), 0, (hipStream_t)stream, pk);
@@ -231,59 +195,15 @@ int skg_layernorm_bwd_multi(const skg_layernorm_bwd_args* calls, int n, void* st
 extern "C" int skg_layernorm_bwd_f32(const float* dy, int64_t lddy, const float* x, const float* stats,
                                      const float* gamma, int rows, float* dx, const float* relu_src, float* dx_masked,
                                      float* dgamma, float* dbeta, void* stream) {
-    if (rows < 0) return SKG_E_ARG;
-    if (!dy || !x || !stats || !gamma || !dx || !dgamma || !dbeta || (dx_masked && !relu_src)) return SKG_E_ARG;
-    if ((lddy & 3) || !skg_aligned16(dy) || !skg_aligned16(x) || !skg_aligned16(gamma) || !skg_aligned16(dx) ||
-        !skg_aligned16(relu_src) || !skg_aligned16(dx_masked))
-        return SKG_E_ALIGN;
-    if (rows)
-        hipLaunchKernelGGL(skg_layernorm_bwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dy, lddy, x, stats,
-                           gamma, dx, relu_src, dx_masked, skg_twin(dx), dx_masked ? skg_twin(dx_masked) : (uint16_t*)nullptr);
-    hipLaunchKernelGGL(skg_layernorm_param_grad_kernel, dim3(TR_COLS / 64), dim3(64 * TR_RG), 0, (hipStream_t)stream, dy, lddy,
-                       x, stats, rows, dgamma, dbeta);
-    return skg_launch_status();
+    const skg_layernorm_bwd_args a = {dy, lddy, x, stats, gamma, rows, dx, relu_src, dx_masked, dgamma, dbeta};
+    return skg_layernorm_bwd_multi(&a, 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ fc_1 * fc_2 backward
 // Forward (MBF / MessageMBF, HEAD:469-474, 509-527):  t = relu(m * f),  m = P[pi] + Q[qi] + mbias,  f = F[fi].
 // Given g = dt (already zeroed where t <= 0):   dF[fi] (+)= g * m,   dm = g * f  (written over g, in place).
 // f_idx must be injective: row r owns dF row f_idx[r] (read, add, write without atomics); two rows on one dF row race.
-__global__ __launch_bounds__(256) void skg_mul_bwd_kernel(float* __restrict__ g, int64_t ldg,
-                                                          const float* __restrict__ F, const int32_t* __restrict__ f_idx,
-                                                          int64_t ldf, const float* __restrict__ P,
-                                                          const int32_t* __restrict__ p_idx, int64_t ldp,
-                                                          const float* __restrict__ Q, const int32_t* __restrict__ q_idx,
-                                                          int64_t ldq, const float* __restrict__ mbias,
-                                                          float* __restrict__ dF, int64_t lddf, int accumulate,
-                                                          uint16_t* __restrict__ dF16) {
-    const int r = blockIdx.x;
-    const int c = threadIdx.x * 4;
-    const int fi = f_idx ? f_idx[r] : r;
-    float4 m = *reinterpret_cast<const float4*>(P + (int64_t)(p_idx ? p_idx[r] : r) * ldp + c);
-    if (Q) {
-        const float4 t = *reinterpret_cast<const float4*>(Q + (int64_t)(q_idx ? q_idx[r] : r) * ldq + c);
-        m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
-    }
-    if (mbias) {
-        const float4 t = *reinterpret_cast<const float4*>(mbias + c);
-        m.x += t.x; m.y += t.y; m.z += t.z; m.w += t.w;
-    }
-    float4* gp = reinterpret_cast<float4*>(g + (int64_t)r * ldg + c);
-    const float4 gv = *gp;
-    const float4 fv = *reinterpret_cast<const float4*>(F + (int64_t)fi * ldf + c);
-    float4* dp = reinterpret_cast<float4*>(dF + (int64_t)fi * lddf + c);
-    float4 o = make_float4(gv.x * m.x, gv.y * m.y, gv.z * m.z, gv.w * m.w);
-    if (accumulate) { const float4 t = *dp; o.x += t.x; o.y += t.y; o.z += t.z; o.w += t.w; }
-    *dp = o;
-    if (dF16) skg_store_twin4(dF16 + (int64_t)fi * lddf + c, o);
-    *gp = make_float4(gv.x * fv.x, gv.y * fv.y, gv.z * fv.z, gv.w * fv.w);
-}
-
-struct skg_mul_bwd_pack { skg_mul_bwd_args a[SKG_MULTI_MAX]; };
-__global__ __launch_bounds__(256) void skg_mul_bwd_multi_kernel(const skg_mul_bwd_pack pk) {
-    const skg_mul_bwd_args& a = pk.a[blockIdx.y];
-    const int r = blockIdx.x;
-    if (r >= a.rows) return;
+__device__ __forceinline__ void skg_mul_bwd_row(const skg_mul_bwd_args& a, int r) {
     const int c = threadIdx.x * 4;
     const int fi = a.f_idx ? a.f_idx[r] : r;
     float4 m = *reinterpret_cast<const float4*>(a.P + (int64_t)(a.p_idx ? a.p_idx[r] : r) * a.ldp + c);
@@ -306,22 +226,36 @@ __global__ __launch_bounds__(256) void skg_mul_bwd_multi_kernel(const skg_mul_bw
     *gp = make_float4(gv.x * fv.x, gv.y * fv.y, gv.z * fv.z, gv.w * fv.w);
 }
 
+struct skg_mul_bwd_pack { skg_mul_bwd_args a[SKG_MULTI_MAX]; };
+__global__ __launch_bounds__(256) void skg_mul_bwd_multi_kernel(const skg_mul_bwd_pack pk) {
+    const skg_mul_bwd_args a = pk.a[blockIdx.y];       // (a copy: all its scalar loads issue at once, up front)
+    if ((int)blockIdx.x >= a.rows) return;                 // (uniform per workgroup)
+    skg_mul_bwd_row(a, (int)blockIdx.x);
+}
+
+// Checks one call and fills its dF16 from the twin map
+static int skg_mul_bwd_check(skg_mul_bwd_args& a) {
+    if (a.rows < 0) return SKG_E_ARG;
+    if (a.rows == 0) return 0;
+    if (!a.g || !a.F || !a.P || !a.dF) return SKG_E_ARG;
+    if ((a.ldg & 3) || (a.ldf & 3) || (a.ldp & 3) || (a.lddf & 3) || (a.Q && (a.ldq & 3))) return SKG_E_ALIGN;
+    if (!skg_aligned16(a.g) || !skg_aligned16(a.F) || !skg_aligned16(a.P) || !skg_aligned16(a.dF) || !skg_aligned16(a.Q) ||
+        !skg_aligned16(a.mbias))                           // (null Q / mbias count as aligned)
+        return SKG_E_ALIGN;
+    a.dF16 = skg_twin(a.dF);
+    return 0;
+}
+
 int skg_mul_bwd_multi(const skg_mul_bwd_args* calls, int n, void* stream) {
     if (!calls || n < 1 || n > SKG_MULTI_MAX) return SKG_E_ARG;
     skg_mul_bwd_pack pk;
     int m = 0, rows = 0;
     for (int i = 0; i < n; ++i) {
-        const skg_mul_bwd_args& a = calls[i];
-        if (a.rows < 0) return SKG_E_ARG;
-        if (a.rows == 0) continue;
-        if (!a.g || !a.F || !a.P || !a.dF) return SKG_E_ARG;
-        if ((a.ldg & 3) || (a.ldf & 3) || (a.ldp & 3) || (a.lddf & 3) || (a.Q && (a.ldq & 3))) return SKG_E_ALIGN;
-        if (!skg_aligned16(a.g) || !skg_aligned16(a.F) || !skg_aligned16(a.P) || !skg_aligned16(a.dF) || !skg_aligned16(a.Q) ||
-            !skg_aligned16(a.mbias))
-            return SKG_E_ALIGN;
-        pk.a[m] = a;
-        pk.a[m++].dF16 = skg_twin(a.dF);
-        rows = a.rows > rows ? a.rows : rows;
+        pk.a[m] = calls[i];
+        if (const int e = skg_mul_bwd_check(pk.a[m])) return e;
+        if (pk.a[m].rows == 0) continue;
+        rows = pk.a[m].rows > rows ? pk.a[m].rows : rows;
+        ++m;
     }
     if (m == 0) return 0;
     hipLaunchKernelGGL(skg_mul_bwd_multi_kernel, dim3(rows, m), dim3(256), 0, (hipStream_t)stream, pk);
@@ -331,16 +265,8 @@ int skg_mul_bwd_multi(const skg_mul_bwd_args* calls, int n, void* stream) {
 extern "C" int skg_mul_bwd_f32(float* g, int64_t ldg, const float* F, const int32_t* f_idx, int64_t ldf, const float* P,
                                const int32_t* p_idx, int64_t ldp, const float* Q, const int32_t* q_idx, int64_t ldq,
                                const float* mbias, int rows, float* dF, int64_t lddf, int accumulate, void* stream) {
-    if (rows < 0) return SKG_E_ARG;
-    if (rows == 0) return 0;
-    if (!g || !F || !P || !dF) return SKG_E_ARG;
-    if ((ldg & 3) || (ldf & 3) || (ldp & 3) || (lddf & 3) || (Q && (ldq & 3))) return SKG_E_ALIGN;
-    if (!skg_aligned16(g) || !skg_aligned16(F) || !skg_aligned16(P) || !skg_aligned16(dF) || (Q && !skg_aligned16(Q)) ||
-        (mbias && !skg_aligned16(mbias)))
-        return SKG_E_ALIGN;
-    hipLaunchKernelGGL(skg_mul_bwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, g, ldg, F, f_idx, ldf, P, p_idx,
-                       ldp, Q, q_idx, ldq, mbias, dF, lddf, accumulate, skg_twin(dF));
-    return skg_launch_status();
+    const skg_mul_bwd_args a = {g, ldg, F, f_idx, ldf, P, p_idx, ldp, Q, q_idx, ldq, mbias, rows, dF, lddf, accumulate};
+    return skg_mul_bwd_multi(&a, 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ neighbourhood sums
@@ -351,69 +277,35 @@ extern "C" int skg_mul_bwd_f32(float* g, int64_t ldg, const float* F, const int3
 //   mode 2  src = kept pairs:  outH[meta[a].image] = sum of all pairs of active image a   (outN unused); outH rows of
 //           the batch's images that are not in meta (skipped: no human, or a single box) keep the caller's value
 // One workgroup per destination row, rows added in index order.
-__device__ __forceinline__ void skg_segment_sum_body(const float* __restrict__ src, int64_t ld,
-                                                     const skg_image_meta* __restrict__ meta,
+__device__ __forceinline__ void skg_segment_sum_body(const skg_segment_sum_args& a, const skg_image_meta* __restrict__ meta,
                                                      const int32_t* __restrict__ hum_img,
-                                                     const int32_t* __restrict__ node_img, int n_dst_h, int mode,
-                                                     float* __restrict__ outH, float* __restrict__ outN, int accumulate,
-                                                     int blk, uint16_t* __restrict__ outH16, uint16_t* __restrict__ outN16) {
+                                                     const int32_t* __restrict__ node_img, int n_dst_h, int blk) {
     const bool to_h = blk < n_dst_h;
     const int dst = to_h ? blk : blk - n_dst_h;
-    float* out = to_h ? outH : outN;
-    uint16_t* out16 = to_h ? outH16 : outN16;
+    float* out = to_h ? a.outH : a.outN;
+    uint16_t* out16 = to_h ? a.outH16 : a.outN16;
     if (!out) return;
-    const int a = mode == 2 ? dst : (to_h ? hum_img[dst] : node_img[dst]);
-    const skg_image_meta mt = meta[a];
+    const skg_image_meta mt = meta[to_h ? hum_img[dst] : node_img[dst]];
     const int c = threadIdx.x * 4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     auto add = [&](int64_t row) {
-        const float4 v = *reinterpret_cast<const float4*>(src + row * ld + c);
+        const float4 v = *reinterpret_cast<const float4*>(a.src + row * a.ld + c);
         acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     };
-    if (mode == 0) {
+    if (a.mode == 0) {
         if (to_h) { const int i = dst - mt.hum_off; for (int j = 0; j < mt.n; ++j) add((int64_t)mt.grid_off + (int64_t)i * mt.n + j); }
         else { const int j = dst - mt.node_off; for (int i = 0; i < mt.n_h; ++i) add((int64_t)mt.grid_off + (int64_t)i * mt.n + j); }
-    } else if (mode == 1) {
+    } else {
         if (to_h) { const int i = dst - mt.hum_off; for (int jj = 0; jj < mt.n - 1; ++jj) add((int64_t)mt.pair_off + (int64_t)i * (mt.n - 1) + jj); }
         else {
             const int j = dst - mt.node_off;
             for (int i = 0; i < mt.n_h; ++i) if (i != j) add((int64_t)mt.pair_off + (int64_t)i * (mt.n - 1) + (j < i ? j : j - 1));
         }
-    } else {
-        // all kept pairs of the image: hundreds of rows through one workgroup -- four independent chains keep four loads in
-        // flight per lane (a single chain walks 780 rows of a 20 x 20 image at one L2 round trip each: 190 us, measured)
-        const int P = mt.n_h * (mt.n - 1);
-        float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f), a2 = a1, a3 = a1;
-        const float* base = src + (int64_t)mt.pair_off * ld + c;
-        int p = 0;
-        for (; p + 3 < P; p += 4) {
-            const float4 v0 = *reinterpret_cast<const float4*>(base + (int64_t)p * ld);
-            const float4 v1 = *reinterpret_cast<const float4*>(base + (int64_t)(p + 1) * ld);
-            const float4 v2 = *reinterpret_cast<const float4*>(base + (int64_t)(p + 2) * ld);
-            const float4 v3 = *reinterpret_cast<const float4*>(base + (int64_t)(p + 3) * ld);
-            acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-            a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
-            a2.x += v2.x; a2.y += v2.y; a2.z += v2.z; a2.w += v2.w;
-            a3.x += v3.x; a3.y += v3.y; a3.z += v3.z; a3.w += v3.w;
-        }
-        for (; p < P; ++p) add((int64_t)mt.pair_off + p);
-        acc.x = (acc.x + a1.x) + (a2.x + a3.x); acc.y = (acc.y + a1.y) + (a2.y + a3.y);
-        acc.z = (acc.z + a1.z) + (a2.z + a3.z); acc.w = (acc.w + a1.w) + (a2.w + a3.w);
     }
-    float4* o = reinterpret_cast<float4*>(out + (int64_t)(mode == 2 ? mt.image : dst) * TR_COLS + c);
-    if (accumulate) { const float4 t = *o; acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w; }
+    float4* o = reinterpret_cast<float4*>(out + (int64_t)dst * TR_COLS + c);
+    if (a.accumulate) { const float4 t = *o; acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w; }
     *o = acc;
-    if (out16) skg_store_twin4(out16 + (int64_t)(mode == 2 ? mt.image : dst) * TR_COLS + c, acc);
-}
-
-__global__ __launch_bounds__(256) void skg_segment_sum_kernel(const float* __restrict__ src, int64_t ld,
-                                                              const skg_image_meta* __restrict__ meta,
-                                                              const int32_t* __restrict__ hum_img,
-                                                              const int32_t* __restrict__ node_img, int n_dst_h, int mode,
-                                                              float* __restrict__ outH, float* __restrict__ outN,
-                                                              int accumulate, uint16_t* __restrict__ outH16,
-                                                              uint16_t* __restrict__ outN16) {
-    skg_segment_sum_body(src, ld, meta, hum_img, node_img, n_dst_h, mode, outH, outN, accumulate, (int)blockIdx.x, outH16, outN16);
+    if (out16) skg_store_twin4(out16 + (int64_t)dst * TR_COLS + c, acc);
 }
 
 struct skg_segment_sum_pack { skg_segment_sum_args a[SKG_MULTI_MAX]; };
@@ -421,9 +313,17 @@ __global__ __launch_bounds__(256) void skg_segment_sum_multi_kernel(const skg_se
                                                                     const skg_image_meta* __restrict__ meta,
                                                                     const int32_t* __restrict__ hum_img,
                                                                     const int32_t* __restrict__ node_img, int n_dst_h) {
-    const skg_segment_sum_args& a = pk.a[blockIdx.y];
-    skg_segment_sum_body(a.src, a.ld, meta, hum_img, node_img, n_dst_h, a.mode, a.outH, a.outN, a.accumulate, (int)blockIdx.x,
-                         a.outH16, a.outN16);
+    const skg_segment_sum_args a = pk.a[blockIdx.y];
+    skg_segment_sum_body(a, meta, hum_img, node_img, n_dst_h, (int)blockIdx.x);
+}
+
+// Checks the source and the outputs of one call (any mode) and fills its twins from the twin map
+static int skg_segment_sum_check(skg_segment_sum_args& a) {
+    if (!a.src || (!a.outH && !a.outN)) return SKG_E_ARG;
+    if ((a.ld & 3) || !skg_aligned16(a.src) || !skg_aligned16(a.outH) || !skg_aligned16(a.outN)) return SKG_E_ALIGN;
+    a.outH16 = a.outH ? skg_twin(a.outH) : nullptr;
+    a.outN16 = a.outN ? skg_twin(a.outN) : nullptr;
+    return 0;
 }
 
 int skg_segment_sum_multi(const skg_segment_sum_args* calls, int n, const skg_image_meta* meta, const int32_t* hum_img,
@@ -433,12 +333,9 @@ int skg_segment_sum_multi(const skg_segment_sum_args* calls, int n, const skg_im
     if (!meta || !hum_img || !node_img) return SKG_E_ARG;
     skg_segment_sum_pack pk;
     for (int i = 0; i < n; ++i) {
-        const skg_segment_sum_args& a = calls[i];
-        if (a.mode < 0 || a.mode > 1 || !a.src || (!a.outH && !a.outN)) return SKG_E_ARG;
-        if ((a.ld & 3) || !skg_aligned16(a.src) || !skg_aligned16(a.outH) || !skg_aligned16(a.outN)) return SKG_E_ALIGN;
-        pk.a[i] = a;
-        pk.a[i].outH16 = a.outH ? skg_twin(a.outH) : nullptr;
-        pk.a[i].outN16 = a.outN ? skg_twin(a.outN) : nullptr;
+        pk.a[i] = calls[i];
+        if (pk.a[i].mode < 0 || pk.a[i].mode > 1) return SKG_E_ARG;
+        if (const int e = skg_segment_sum_check(pk.a[i])) return e;
     }
     hipLaunchKernelGGL(skg_segment_sum_multi_kernel, dim3(sum_h + sum_n, n), dim3(256), 0, (hipStream_t)stream, pk, meta,
                        hum_img, node_img, sum_h);
@@ -487,19 +384,14 @@ extern "C" int skg_segment_sum_f32(const float* src, int64_t ld, const skg_image
                                    const int32_t* hum_img, const int32_t* node_img, int sum_h, int sum_n, int mode,
                                    float* outH, float* outN, int accumulate, void* stream) {
     if (n_active < 0 || sum_h < 0 || sum_n < 0 || mode < 0 || mode > 2) return SKG_E_ARG;
-    const int nh = mode == 2 ? n_active : sum_h, nn = mode == 2 ? 0 : sum_n;
-    if (nh + nn == 0) return 0;
-    if (!src || !meta || (mode != 2 && (!hum_img || !node_img)) || (!outH && !outN)) return SKG_E_ARG;
-    if ((ld & 3) || !skg_aligned16(src) || !skg_aligned16(outH) || !skg_aligned16(outN)) return SKG_E_ALIGN;
-    if (mode == 2) {
-        if (!outH) return SKG_E_ARG;
-        hipLaunchKernelGGL(skg_segment_sum_image_kernel, dim3(n_active, TR_COLS / 64), dim3(256), 0, (hipStream_t)stream, src,
-                           ld, meta, outH, accumulate, skg_twin(outH));
-        return skg_launch_status();
-    }
-    hipLaunchKernelGGL(skg_segment_sum_kernel, dim3(nh + nn), dim3(256), 0, (hipStream_t)stream, src, ld, meta, hum_img,
-                       node_img, nh, mode, outH, outN, accumulate, outH ? skg_twin(outH) : (uint16_t*)nullptr,
-                       outN ? skg_twin(outN) : (uint16_t*)nullptr);
+    skg_segment_sum_args a = {src, ld, mode, outH, outN, accumulate};
+    if (mode != 2) return skg_segment_sum_multi(&a, 1, meta, hum_img, node_img, sum_h, sum_n, stream);
+    if (n_active == 0) return 0;
+    if (!meta) return SKG_E_ARG;
+    if (const int e = skg_segment_sum_check(a)) return e;
+    if (!outH) return SKG_E_ARG;
+    hipLaunchKernelGGL(skg_segment_sum_image_kernel, dim3(n_active, TR_COLS / 64), dim3(256), 0, (hipStream_t)stream, src, ld,
+                       meta, outH, accumulate, a.outH16);
     return skg_launch_status();
 }
 

@@ -39,8 +39,8 @@ Compared exactly instead (no figure): rows_mul_relu against fp32 torch in the ke
 fp64), every bf16 output against `.to(bfloat16)` of the fp32 output, layernorm2 against skg_layernorm_f32 row by row,
 concat_entity and the two transposes as integer views, the _f32 entries against their _x twins.
 
-Which kernels needed a fix.  One: the ReLU of skg_rows_mul_relu_* (and of the multi form the training plan launches) was
-fmaxf(x, 0.f), which returns 0 for NaN where torch.relu and clamp(min=0) return NaN, so a NaN or an inf * 0 in P, Q, mbias or
+Which kernels needed a fix.  One: the ReLU of skg_rows_mul_relu_* (one kernel: the training plan's grouped launch and the
+one-call entries tested here run the same row body) was fmaxf(x, 0.f), which returns 0 for NaN where torch.relu and clamp(min=0) return NaN, so a NaN or an inf * 0 in P, Q, mbias or
 F came out as a finite 0 and the forward went on as if nothing had happened.  The same expression stood in every GEMM
 epilogue and split-K reduce (skg_gemm.hip, skg_gemm_x.hip, skg_gemm_bf16.hip; tests/test_gemm_epilogue_gpu.py and
 tests/test_gemmx_gpu.py hold those).  All of them now go through skg_relu (skg_common.h): IEEE 754-2019 maximum, one

@@ -343,7 +343,11 @@ int skg_gemm_group_tile(const skg_gemm_desc* descs_host, int n);
  * operand (a_rows gather, any K % 4 == 0), rounded in registers; inf / nan propagate as on the exact loop.  d.w_split
  * and d.a_exp are treated as NULL (the launch works on a copy with both cleared).  Tile scale and split-K rules as for
  * the fp32 launches of that copy: skg_gemm_dot_partials / skg_gemm_group_tile give this launch's slab count / tile
- * scale when queried with w_split = NULL.  Never routed to skg_gemmx_f32.  w16_host: one twin pointer per descriptor. */
+ * scale when queried with w_split = NULL.  Never routed to skg_gemmx_f32.  w16_host: one twin pointer per descriptor.
+ * skg_gemm_b16_f32(d, w16) is skg_gemm_b16_x (below) with io = {w16, NULL, NULL, 0} and skg_gemm_b16_a16_f32(d, a16, w16)
+ * with io = {w16, a16, NULL, 0}: one launch path, the same kernels, grid and checks; an entry differs in the counters it
+ * moves.  A descriptor that breaks one rule gets that rule's code from every entry; one that breaks several is answered in
+ * the order of skg_gemm_b16_x's checks (io rules, a16 rules, the rules of skg_gemm_f32, then the twin's).             */
 int skg_gemm_b16_f32(const skg_gemm_desc* desc_host, const uint16_t* w16, void* stream);
 int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uint16_t* const* w16_host, int n, void* stream);
 /* skg_gemm_b16_f32 with A given in bf16: a16 holds the M x K operand with row stride d.lda ELEMENTS; d.A is not read.

@@ -1269,22 +1269,25 @@ struct skg_gemm_group_args {
     int n;
 };
 
-__global__ __launch_bounds__(256, SKG_MINW) void skg_gemm_group_kernel(const skg_gemm_group_args g) {
-    __shared__ __attribute__((aligned(16))) float smem[2 * (A_TILE + B_TILE)];
+// The member whose block range [start[k], start[k + 1]) holds this workgroup.
+__device__ __forceinline__ int skg_gemm_group_member(const skg_gemm_group_args& g) {
     int k = 0;
 #pragma unroll
     for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
         if (t < g.n && (int)blockIdx.x >= g.start[t]) k = t;
+    return k;
+}
+
+__global__ __launch_bounds__(256, SKG_MINW) void skg_gemm_group_kernel(const skg_gemm_group_args g) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * (A_TILE + B_TILE)];
+    const int k = skg_gemm_group_member(g);
     skg_gemm_tile<-1, 0, 2>(g.d[k], blockIdx.x - g.start[k], smem);
 }
 
 // the same with the fp16x2 loop (every descriptor of the group carries a weight twin)
 __global__ __launch_bounds__(256, SKG_MINW) void skg_gemm_group_split_kernel(const skg_gemm_group_args g) {
     __shared__ __attribute__((aligned(16))) float smem[2 * (A_TILE + B_TILE)];
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < g.n && (int)blockIdx.x >= g.start[t]) k = t;
+    const int k = skg_gemm_group_member(g);
     skg_gemm_tile<-1, 2, 2>(g.d[k], blockIdx.x - g.start[k], smem);
 }
 
@@ -1294,37 +1297,25 @@ __global__ __launch_bounds__(256, SKG_MINW) void skg_gemm_group_split_kernel(con
 // plus split-K for the one-tile-high problems, put the whole chip on them.
 __global__ __launch_bounds__(256, SKG_MINW) void skg_gemm_group_small_kernel(const skg_gemm_group_args g) {
     __shared__ __attribute__((aligned(16))) float smem[4 * 32 * 36];
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < g.n && (int)blockIdx.x >= g.start[t]) k = t;
+    const int k = skg_gemm_group_member(g);
     skg_gemm_tile<-1, 1, 1>(g.d[k], blockIdx.x - g.start[k], smem);
 }
 
 __global__ __launch_bounds__(256, SKG_NB4 > 2 ? 1 : SKG_MINW) void skg_gemm_group_direct_kernel(const skg_gemm_group_args g) {
     __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM4];
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < g.n && (int)blockIdx.x >= g.start[t]) k = t;
+    const int k = skg_gemm_group_member(g);
     skg_gemm_tile<-1, 4, 1>(g.d[k], blockIdx.x - g.start[k], smem);
 }
 
 __global__ __launch_bounds__(256, SKG_MINW) void skg_gemm_group_latency_kernel(const skg_gemm_group_args g) {
     __shared__ __attribute__((aligned(16))) float smem[SKG_SMEM3];
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < g.n && (int)blockIdx.x >= g.start[t]) k = t;
+    const int k = skg_gemm_group_member(g);
     skg_gemm_tile<-1, 3, 1>(g.d[k], blockIdx.x - g.start[k], smem);
 }
 
 __global__ __launch_bounds__(512, 1) void skg_gemm_group_khalves_kernel(const skg_gemm_group_args g) {
     __shared__ __attribute__((aligned(16))) float smem[SKG_SMEM3];
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < g.n && (int)blockIdx.x >= g.start[t]) k = t;
+    const int k = skg_gemm_group_member(g);
     skg_gemm_tile<-1, 5, 1>(g.d[k], blockIdx.x - g.start[k], smem);
 }
 
@@ -1351,10 +1342,7 @@ struct skg_gemm_group_b16_args {
 template <int T>
 __global__ __launch_bounds__(256, 2) void skg_gemm_group_b16_kernel(const skg_gemm_group_b16_args a) {
     __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < a.g.n && (int)blockIdx.x >= a.g.start[t]) k = t;
+    const int k = skg_gemm_group_member(a.g);
     skg_gemm_tile<-1, 6, T>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k]);
 }
 
@@ -1391,10 +1379,7 @@ __global__ __launch_bounds__(256) void skg_splitk_reduce_kernel(const skg_gemm_d
 }
 
 __global__ __launch_bounds__(256) void skg_splitk_reduce_group_kernel(const skg_gemm_group_args g) {
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < g.n && (int)blockIdx.x >= g.start[t]) k = t;
+    const int k = skg_gemm_group_member(g);
     skg_splitk_reduce_one(g.d[k], (int64_t)(blockIdx.x - g.start[k]) * 256 + threadIdx.x);
 }
 
@@ -1479,6 +1464,52 @@ extern "C" int skg_row_exponents_f32(const float* A, int64_t lda, const int32_t*
     return skg_launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------ bf16 activations (skg_gemm_b16_x)
+// The bf16 launches with an optional bf16 A (a16, MODE 7) and an optional bf16 output (c16, beside or instead of d.C): what
+// inference_activations = "bf16" stores the GEMM-only panels of the eval forward in.  The launch shape -- tile scale, block
+// map, split-K -- is that of skg_gemm_b16_f32 / skg_gemm_group_b16_f32 on the same descriptor: it never depends on whether A
+// or C is bf16, so a chain of these launches reproduces the fp32-panel chain bit for bit (the consumer would have rounded
+// the fp32 panel with the conversion the producer stored it with).
+template <int EPI, int MODE, int T>
+__global__ __launch_bounds__(256, 2) void skg_gemm_b16x_kernel(const skg_gemm_desc d, const uint16_t* a16, const uint16_t* w16,
+                                                               uint16_t* c16, int64_t ldc16) {
+    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
+    skg_gemm_tile<EPI, MODE, T, true>(d, blockIdx.x, smem, w16, a16, c16, ldc16);
+}
+
+struct skg_gemm_group_b16x_args {
+    skg_gemm_group_args g;
+    const uint16_t* w16[SKG_GEMM_GROUP_MAX];
+    const uint16_t* a16[SKG_GEMM_GROUP_MAX];
+    uint16_t* c16[SKG_GEMM_GROUP_MAX];
+    int64_t ldc16[SKG_GEMM_GROUP_MAX];
+};
+
+// members mix freely: the main loop (MODE 6 / 7) is picked per member on a workgroup-uniform flag
+template <int T>
+__global__ __launch_bounds__(256, 2) void skg_gemm_group_b16x_kernel(const skg_gemm_group_b16x_args a) {
+    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
+    const int k = skg_gemm_group_member(a.g);
+    if (a.a16[k]) skg_gemm_tile<-1, 7, T, true>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k], a.a16[k], a.c16[k], a.ldc16[k]);
+    else skg_gemm_tile<-1, 6, T, true>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k], nullptr, a.c16[k], a.ldc16[k]);
+}
+
+__global__ __launch_bounds__(256) void skg_splitk_reduce_x_kernel(const skg_gemm_desc d, uint16_t* c16, int64_t ldc16) {
+    skg_splitk_reduce_one(d, (int64_t)blockIdx.x * 256 + threadIdx.x, c16, ldc16);
+}
+
+struct skg_splitk_reduce_group_x_args {
+    skg_gemm_group_args g;
+    uint16_t* c16[SKG_GEMM_GROUP_MAX];
+    int64_t ldc16[SKG_GEMM_GROUP_MAX];
+};
+
+__global__ __launch_bounds__(256) void skg_splitk_reduce_group_x_kernel(const skg_splitk_reduce_group_x_args a) {
+    const int k = skg_gemm_group_member(a.g);
+    skg_splitk_reduce_one(a.g.d[k], (int64_t)(blockIdx.x - a.g.start[k]) * 256 + threadIdx.x, a.c16[k], a.ldc16[k]);
+}
+
+// ------------------------------------------------------------------------------------------------ host side: launch policy
 // Which 64 x 64 loop the small launches take: 4 = latency loop staged straight into LDS (64 k per step; needs K % 64 == 0,
 // otherwise 3), 3 = latency loop (64 k per step, register staged), 1 = DMA-staged 16-k steps.  A developer switch for A/B measurements (tools/small_batch_loop.py); both give bit-identical results only
 // with themselves (the summation order over k differs).
@@ -1493,14 +1524,24 @@ extern "C" int skg_row_exponents_f32(const float* A, int64_t lda, const int32_t*
 // A launch (or group) counts as small -- 64 x 64 tiles -- below this many 128 x 128 tiles (split-K slices included): 384.
 #define g_small_tiles skg_tune_small_tiles()
 
+// The predicates every entry point decides by, one definition each.
+// The descriptor can take the DMA-staged loop: whole 16-k steps, no row gather, tile offsets within 32 bits.
+static inline bool skg_gemm_can_dma(const skg_gemm_desc& d) {
+    return SKG_USE_GLDS && BK == 16 && (d.K % BK) == 0 && !d.a_rows &&
+           (int64_t)BM * d.lda * 4 < 0xffffffffLL && (int64_t)BN * d.ldw * 4 < 0xffffffffLL;
+}
+// The fp16x2 split-operand loop applies: a weight twin with its scale, whole 16-k steps.
+static inline bool skg_gemm_fp16x2(const skg_gemm_desc& d) { return d.w_split && (d.K % 16) == 0 && d.w_scale > 0.f; }
+static inline int skg_gemm_slices(const skg_gemm_desc& d) { return d.split_k > 1 ? d.split_k : 1; }
+// 128 x 128 tiles of the M x N grid; ... of the launch, split-K slices included
+static inline int64_t skg_gemm_grid128(const skg_gemm_desc& d) { return (int64_t)((d.M + 127) / 128) * ((d.N + 127) / 128); }
+static inline int64_t skg_gemm_tiles128(const skg_gemm_desc& d) { return skg_gemm_grid128(d) * skg_gemm_slices(d); }
+
 // 64 x 64 tiles when the 128 x 128 grid would leave most CUs idle (small M: low-batch inference); needs the DMA path.
 static int skg_gemm_tile_scale(const skg_gemm_desc* d) {
-    const bool glds = SKG_USE_GLDS && BK == 16 && (d->K % BK) == 0 && !d->a_rows &&
-                      (int64_t)BM * d->lda * 4 < 0xffffffffLL && (int64_t)BN * d->ldw * 4 < 0xffffffffLL;
-    const int64_t tiles128 = (int64_t)((d->M + 127) / 128) * ((d->N + 127) / 128) * (d->split_k > 1 ? d->split_k : 1);
-    if (d->w_split && (d->K % 16) == 0 && d->w_scale > 0.f) return 2;
+    if (skg_gemm_fp16x2(*d)) return 2;
     // M <= 64: a 128-row tile would spend half of its MFMAs on padding rows whatever the grid size (box_head at one image)
-    return (glds && (tiles128 < g_small_tiles || d->M <= 64)) ? 1 : 2;
+    return (skg_gemm_can_dma(*d) && (skg_gemm_tiles128(*d) < g_small_tiles || d->M <= 64)) ? 1 : 2;
 }
 
 extern "C" int skg_gemm_dot_partials(const skg_gemm_desc* dh) {
@@ -1561,16 +1602,15 @@ static bool skg_route_desc(const skg_gemm_desc& d, skg_gemmx_desc& x, skg_gemmx_
 }
 
 // 64 x 64 tiles for a whole group?  Every member must be able to take the DMA-staged loop, none may carry a weight twin,
-// and together they must be small (the same bound as a single launch: fewer than 384 tiles of 128 x 128).
+// and together they must be small (the same bound as a single launch: fewer than 384 tiles of 128 x 128; a group counts
+// its members' tiles without their split slices).
 static bool skg_gemm_group_small(const skg_gemm_desc* descs, int n) {
     int64_t tiles128 = 0;
     for (int i = 0; i < n; ++i) {
         const skg_gemm_desc& d = descs[i];
         if (d.M == 0) continue;
-        const bool glds = SKG_USE_GLDS && BK == 16 && (d.K % BK) == 0 && !d.a_rows &&
-                          (int64_t)BM * d.lda * 4 < 0xffffffffLL && (int64_t)BN * d.ldw * 4 < 0xffffffffLL;
-        if (!glds || (d.w_split && d.w_scale > 0.f)) return false;
-        tiles128 += (int64_t)((d.M + 127) / 128) * ((d.N + 127) / 128);
+        if (!skg_gemm_can_dma(d) || (d.w_split && d.w_scale > 0.f)) return false;
+        tiles128 += skg_gemm_grid128(d);
     }
     return tiles128 < g_small_tiles;
 }
@@ -1592,12 +1632,67 @@ extern "C" int skg_gemm_group_tile(const skg_gemm_desc* descs_host, int n) {
     return skg_gemm_group_small(descs_host, n) ? 1 : 2;
 }
 
+// ---- what every entry point launches through
+// d.epilogue as the kernels' compile-time EPI: f is called with std::integral_constant<int, EPI> (the descriptor passed
+// skg_gemm_validate, so the epilogue is one of the five).  The deduced return type has it instantiated where it is called,
+// which keeps the kernels of the code object in the order of the launches in this file.
+template <class F>
+static auto skg_gemm_with_epilogue(int epilogue, F&& f) {
+    switch (epilogue) {
+        case SKG_EPI_BIAS:          f(std::integral_constant<int, SKG_EPI_BIAS>{}); break;
+        case SKG_EPI_BIAS_RELU:     f(std::integral_constant<int, SKG_EPI_BIAS_RELU>{}); break;
+        case SKG_EPI_MUL_RELU:      f(std::integral_constant<int, SKG_EPI_MUL_RELU>{}); break;
+        case SKG_EPI_RELU_DOT:      f(std::integral_constant<int, SKG_EPI_RELU_DOT>{}); break;
+        case SKG_EPI_BIAS_RES_RELU: f(std::integral_constant<int, SKG_EPI_BIAS_RES_RELU>{}); break;
+    }
+}
+
+// The split-K reduce behind a single launch.  x: the launch came through skg_gemm_b16_x, whose reduce kernel takes c16
+// (NULL: fp32 only); the other entries have no bf16 output.
+static void skg_gemm_reduce_tail(const skg_gemm_desc& d, hipStream_t s, bool x = false, uint16_t* c16 = nullptr,
+                                 int64_t ldc16 = 0) {
+    if (d.split_k <= 1) return;
+    const dim3 grid((unsigned)(((int64_t)d.M * d.N + 255) / 256));
+    if (x) hipLaunchKernelGGL(skg_splitk_reduce_x_kernel, grid, dim3(256), 0, s, d, c16, ldc16);
+    else hipLaunchKernelGGL(skg_splitk_reduce_kernel, grid, dim3(256), 0, s, d);
+}
+
+// The member loop of a grouped launch: g gets the members with rows, r those of them that need the split-K reduce, both with
+// their block ranges (tails padded).  src / rsrc: the caller's index of each member (the bf16 entries carry per-member
+// pointers beside the descriptors); blocks / rblocks: the two grids.  The descriptors have passed their checks.
+struct skg_gemm_group_plan {
+    int src[SKG_GEMM_GROUP_MAX], rsrc[SKG_GEMM_GROUP_MAX];
+    int64_t blocks, rblocks;
+};
+
+static int skg_gemm_group_fill(const skg_gemm_desc* descs, int n, bool small, skg_gemm_group_args& g,
+                               skg_gemm_group_args& r, skg_gemm_group_plan& p) {
+    g.n = r.n = 0;
+    p.blocks = p.rblocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const skg_gemm_desc& d = descs[i];
+        if (d.split_k > 1 && !small) return SKG_E_ARG;                   // split-K only with the 64 x 64 tiles
+        if (d.M == 0) continue;
+        const int64_t nb = skg_gemm_blocks(d.M, d.N, d.K, small ? 1 : 2) * skg_gemm_slices(d);
+        if (p.blocks + nb > 0x7fffffffLL) return SKG_E_LIMIT;
+        g.d[g.n] = d;
+        g.start[g.n] = (int)p.blocks;
+        p.src[g.n++] = i;
+        p.blocks += nb;
+        if (d.split_k > 1) {
+            r.d[r.n] = d;
+            r.start[r.n] = (int)p.rblocks;
+            p.rsrc[r.n++] = i;
+            p.rblocks += ((int64_t)d.M * d.N + 255) / 256;
+        }
+    }
+    for (int i = g.n; i <= SKG_GEMM_GROUP_MAX; ++i) g.start[i] = (int)p.blocks;
+    for (int i = r.n; i <= SKG_GEMM_GROUP_MAX; ++i) r.start[i] = (int)p.rblocks;
+    return 0;
+}
+
 extern "C" int skg_gemm_group_f32(const skg_gemm_desc* descs_host, int n, void* stream) {
     if (!descs_host || n < 1 || n > SKG_GEMM_GROUP_MAX) return SKG_E_ARG;
-    skg_gemm_group_args g, r;
-    g.n = r.n = 0;
-    int64_t blocks = 0, rblocks = 0;
-    bool split = true;
     for (int i = 0; i < n; ++i) {
         const int rc = skg_gemm_validate(descs_host[i]);
         if (rc) return rc;
@@ -1609,49 +1704,33 @@ extern "C" int skg_gemm_group_f32(const skg_gemm_desc* descs_host, int n, void* 
         int64_t tiles128 = 0;
         bool ok = true;
         for (int i = 0; i < n && ok; ++i) {
-            const skg_gemm_desc& d = descs_host[i];
-            ok = skg_route_desc(d, xs[i], fs[i]);
-            tiles128 += (int64_t)((d.M + 127) / 128) * ((d.N + 127) / 128) * (d.split_k > 1 ? d.split_k : 1);
+            ok = skg_route_desc(descs_host[i], xs[i], fs[i]);
+            tiles128 += skg_gemm_tiles128(descs_host[i]);
         }
         if (ok && tiles128 >= g_route_tiles && tiles128 < 4 * g_small_tiles) {
             skg_gemm_count(SKG_GEMM_PATH_ROUTED);
             return skg_gemmx_f32_fused(xs, fs, n, stream);
         }
     }
-    for (int i = 0; i < n; ++i) {
-        const skg_gemm_desc& d = descs_host[i];
-        if (d.split_k > 1 && !small) return SKG_E_ARG;                     // split-K only with the 64 x 64 tiles
-        if (d.M == 0) continue;
-        split = split && d.w_split && (d.K % 16) == 0 && d.w_scale > 0.f;
-        const int64_t nb = skg_gemm_blocks(d.M, d.N, d.K, small ? 1 : 2) * (d.split_k > 1 ? d.split_k : 1);
-        if (blocks + nb > 0x7fffffffLL) return SKG_E_LIMIT;
-        g.d[g.n] = d;
-        g.start[g.n] = (int)blocks;
-        blocks += nb;
-        ++g.n;
-        if (d.split_k > 1) {
-            r.d[r.n] = d;
-            r.start[r.n] = (int)rblocks;
-            rblocks += ((int64_t)d.M * d.N + 255) / 256;
-            ++r.n;
-        }
-    }
-    if (g.n == 0) return 0;
-    for (int i = g.n; i <= SKG_GEMM_GROUP_MAX; ++i) g.start[i] = (int)blocks;
+    skg_gemm_group_args g, r;
+    skg_gemm_group_plan p;
+    const int rc = skg_gemm_group_fill(descs_host, n, small, g, r, p);
+    if (rc || g.n == 0) return rc;
+    bool split = true;                                      // every member carries a weight twin: the fp16x2 loop
+    for (int i = 0; i < g.n; ++i) split = split && skg_gemm_fp16x2(g.d[i]);
     bool direct = small && g_small_mode == 4;               // every member with whole 64-k steps: the direct-to-LDS loop
     for (int i = 0; i < g.n && direct; ++i) direct = (g.d[i].K % 64) == 0;
-    const bool halves = small && (g_small_mode == 5 || (g_small_mode == 6 && blocks <= g_khalves_blocks));
+    const bool halves = small && (g_small_mode == 5 || (g_small_mode == 6 && p.blocks <= g_khalves_blocks));
+    const dim3 grid((unsigned)p.blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
     skg_gemm_count(split && !small ? SKG_GEMM_PATH_FP16X2 : SKG_GEMM_PATH_EXACT);
-    if (direct) hipLaunchKernelGGL(skg_gemm_group_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g);
-    else if (halves) hipLaunchKernelGGL(skg_gemm_group_khalves_kernel, dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, g);
-    else if (small && g_small_mode >= 3) hipLaunchKernelGGL(skg_gemm_group_latency_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g);
-    else if (small) hipLaunchKernelGGL(skg_gemm_group_small_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g);
-    else if (split) hipLaunchKernelGGL(skg_gemm_group_split_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(skg_gemm_group_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g);
-    if (r.n) {
-        for (int i = r.n; i <= SKG_GEMM_GROUP_MAX; ++i) r.start[i] = (int)rblocks;
-        hipLaunchKernelGGL(skg_splitk_reduce_group_kernel, dim3((unsigned)rblocks), dim3(256), 0, (hipStream_t)stream, r);
-    }
+    if (direct) hipLaunchKernelGGL(skg_gemm_group_direct_kernel, grid, block, 0, s, g);
+    else if (halves) hipLaunchKernelGGL(skg_gemm_group_khalves_kernel, grid, dim3(512), 0, s, g);
+    else if (small && g_small_mode >= 3) hipLaunchKernelGGL(skg_gemm_group_latency_kernel, grid, block, 0, s, g);
+    else if (small) hipLaunchKernelGGL(skg_gemm_group_small_kernel, grid, block, 0, s, g);
+    else if (split) hipLaunchKernelGGL(skg_gemm_group_split_kernel, grid, block, 0, s, g);
+    else hipLaunchKernelGGL(skg_gemm_group_kernel, grid, block, 0, s, g);
+    if (r.n) hipLaunchKernelGGL(skg_splitk_reduce_group_kernel, dim3((unsigned)p.rblocks), block, 0, s, r);
     return skg_launch_status();
 }
 
@@ -1661,50 +1740,42 @@ extern "C" int skg_gemm_f32(const skg_gemm_desc* dh, void* stream) {
     const int rc = skg_gemm_validate(d);
     if (rc) return rc;
     if (d.M == 0) return 0;
-    const bool glds = SKG_USE_GLDS && BK == 16 && (d.K % BK) == 0 && !d.a_rows &&
-                      (int64_t)BM * d.lda * 4 < 0xffffffffLL && (int64_t)BN * d.ldw * 4 < 0xffffffffLL;
-    const bool split = d.w_split && (d.K % 16) == 0 && d.w_scale > 0.f;
-    const int T = split ? 2 : skg_gemm_tile_scale(&d);
+    const bool glds = skg_gemm_can_dma(d), split = skg_gemm_fp16x2(d);
+    const int T = skg_gemm_tile_scale(&d);
     if (!split && T == 1 && d.M > 64) {                    // mid-size launch: the free-layout GEMM (see g_route_tiles)
-        const int64_t tiles128 = (int64_t)((d.M + 127) / 128) * ((d.N + 127) / 128) * (d.split_k > 1 ? d.split_k : 1);
         skg_gemmx_desc x; skg_gemmx_fused f;
-        if (tiles128 >= g_route_tiles && skg_route_desc(d, x, f)) {
+        if (skg_gemm_tiles128(d) >= g_route_tiles && skg_route_desc(d, x, f)) {
             skg_gemm_count(SKG_GEMM_PATH_ROUTED);
             return skg_gemmx_f32_fused(&x, &f, 1, stream);
         }
     }
-    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
+    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * skg_gemm_slices(d);
     if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
-    dim3 grid((unsigned)nblk), block(256);
+    const dim3 grid((unsigned)nblk), block(256);
     hipStream_t s = (hipStream_t)stream;
+    const bool tiny = glds && T == 1;                       // 64 x 64 tiles: the loop g_small_mode names
     skg_gemm_count(split ? SKG_GEMM_PATH_FP16X2 : SKG_GEMM_PATH_EXACT);
-#define SKG_LAUNCH(E)                                                                              \
-    if (split) hipLaunchKernelGGL((skg_gemm_kernel<E, 2, 2>), grid, block, 0, s, d);               \
-    else if (glds && T == 1 && g_small_mode == 4 && (d.K % 64) == 0) hipLaunchKernelGGL((skg_gemm_kernel<E, 4, 1>), grid, block, 0, s, d); \
-    else if (glds && T == 1 && (g_small_mode == 5 || (g_small_mode == 6 && nblk <= g_khalves_blocks))) hipLaunchKernelGGL((skg_gemm_kernel<E, 5, 1>), grid, dim3(512), 0, s, d); \
-    else if (glds && T == 1 && g_small_mode >= 3) hipLaunchKernelGGL((skg_gemm_kernel<E, 3, 1>), grid, block, 0, s, d); \
-    else if (glds && T == 1) hipLaunchKernelGGL((skg_gemm_kernel<E, 1, 1>), grid, block, 0, s, d); \
-    else if (glds) hipLaunchKernelGGL((skg_gemm_kernel<E, 1, 2>), grid, block, 0, s, d);           \
-    else hipLaunchKernelGGL((skg_gemm_kernel<E, 0, 2>), grid, block, 0, s, d);
-    switch (d.epilogue) {
-        case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
-        case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;
-        case SKG_EPI_MUL_RELU:      SKG_LAUNCH(SKG_EPI_MUL_RELU) break;
-        case SKG_EPI_RELU_DOT:      SKG_LAUNCH(SKG_EPI_RELU_DOT) break;
-        case SKG_EPI_BIAS_RES_RELU: SKG_LAUNCH(SKG_EPI_BIAS_RES_RELU) break;
-    }
-#undef SKG_LAUNCH
-    if (d.split_k > 1) {
-        const int64_t total = (int64_t)d.M * d.N;
-        hipLaunchKernelGGL(skg_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d);
-    }
+    skg_gemm_with_epilogue(d.epilogue, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        if (split) hipLaunchKernelGGL((skg_gemm_kernel<E, 2, 2>), grid, block, 0, s, d);
+        else if (tiny && g_small_mode == 4 && (d.K % 64) == 0) hipLaunchKernelGGL((skg_gemm_kernel<E, 4, 1>), grid, block, 0, s, d);
+        else if (tiny && (g_small_mode == 5 || (g_small_mode == 6 && nblk <= g_khalves_blocks))) hipLaunchKernelGGL((skg_gemm_kernel<E, 5, 1>), grid, dim3(512), 0, s, d);
+        else if (tiny && g_small_mode >= 3) hipLaunchKernelGGL((skg_gemm_kernel<E, 3, 1>), grid, block, 0, s, d);
+        else if (tiny) hipLaunchKernelGGL((skg_gemm_kernel<E, 1, 1>), grid, block, 0, s, d);
+        else if (glds) hipLaunchKernelGGL((skg_gemm_kernel<E, 1, 2>), grid, block, 0, s, d);
+        else hipLaunchKernelGGL((skg_gemm_kernel<E, 0, 2>), grid, block, 0, s, d);
+    });
+    skg_gemm_reduce_tail(d, s);
     return skg_launch_status();
 }
 
-// ------------------------------------------------------------------------------------------------ bf16 operands (MODE 6)
+// ------------------------------------------------------------------------------------------------ bf16 operands (MODE 6 / 7)
 // Same descriptor, tile map, split-K and epilogues as skg_gemm_f32; the tile scale follows skg_gemm_tile_scale /
 // skg_gemm_group_small, so skg_gemm_dot_partials and skg_gemm_group_tile hold for these launches too.  Never routed to the
 // fp32 free-layout GEMM.  w16: bf16 twin of d.W with the same element indexing (skg_twin_bf16 of the fp32 buffer).
+// One launch path serves the entry points: skg_gemm_b16_f32 and skg_gemm_b16_a16_f32 are skg_gemm_b16_x with an io that
+// names no bf16 output, the two grouped entries share their checks and their member loop.  An entry keeps its counters,
+// its kernels (the grouped ones) and its split-K reduce kernel.
 static int skg_gemm_b16_check(const skg_gemm_desc& d, const uint16_t* w16) {
     const int rc = skg_gemm_validate(d);
     if (rc) return rc;
@@ -1713,189 +1784,7 @@ static int skg_gemm_b16_check(const skg_gemm_desc& d, const uint16_t* w16) {
     return 0;
 }
 
-extern "C" int skg_gemm_b16_f32(const skg_gemm_desc* dh, const uint16_t* w16, void* stream) {
-    if (!dh) return SKG_E_ARG;
-    skg_gemm_desc d = *dh;
-    d.w_split = nullptr; d.a_exp = nullptr;                         // ignored here (the tile scale reads w_split)
-    const int rc = skg_gemm_b16_check(d, w16);
-    if (rc) return rc;
-    if (d.M == 0) return 0;
-    const int T = skg_gemm_tile_scale(&d);
-    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
-    if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
-    dim3 grid((unsigned)nblk), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    skg_gemm_count(SKG_GEMM_PATH_BF16);
-#define SKG_LAUNCH(E)                                                                               \
-    if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 1>), grid, block, 0, s, d, w16);         \
-    else hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 2>), grid, block, 0, s, d, w16);
-    switch (d.epilogue) {
-        case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
-        case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;
-        case SKG_EPI_MUL_RELU:      SKG_LAUNCH(SKG_EPI_MUL_RELU) break;
-        case SKG_EPI_RELU_DOT:      SKG_LAUNCH(SKG_EPI_RELU_DOT) break;
-        case SKG_EPI_BIAS_RES_RELU: SKG_LAUNCH(SKG_EPI_BIAS_RES_RELU) break;
-    }
-#undef SKG_LAUNCH
-    if (d.split_k > 1) {
-        const int64_t total = (int64_t)d.M * d.N;
-        hipLaunchKernelGGL(skg_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d);
-    }
-    return skg_launch_status();
-}
-
-// bf16 A (MODE 7): the launch of skg_gemm_b16_f32 with A staged from a16 like W.  The checks run on a copy whose A is a16
-// (only skg_gemm_validate reads it there: non-null, aligned); the tile scale therefore follows the caller's descriptor.
-static std::atomic<long long> g_gemm_a16_launches;
-
-extern "C" void skg_gemm_b16_a16_launches(int64_t* out_host, int reset) {
-    if (out_host) *out_host = g_gemm_a16_launches.load(std::memory_order_relaxed);
-    if (reset) g_gemm_a16_launches.store(0, std::memory_order_relaxed);
-}
-
-extern "C" int skg_gemm_b16_a16_f32(const skg_gemm_desc* dh, const uint16_t* a16, const uint16_t* w16, void* stream) {
-    if (!dh || !a16) return SKG_E_ARG;
-    skg_gemm_desc d = *dh;
-    d.w_split = nullptr; d.a_exp = nullptr;                         // ignored here, as in skg_gemm_b16_f32
-    if (d.a_rows) return SKG_E_ARG;                                 // no gathers: A is staged by whole rows
-    if (!skg_aligned16(a16) || (d.lda & 7) || (d.K & 7)) return SKG_E_ALIGN;   // 16-byte DMA pieces of whole k-chunks
-    d.A = reinterpret_cast<const float*>(a16);
-    const int rc = skg_gemm_b16_check(d, w16);
-    if (rc) return rc;
-    if (d.M == 0) return 0;
-    const int T = skg_gemm_tile_scale(&d);
-    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
-    if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
-    dim3 grid((unsigned)nblk), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    skg_gemm_count(SKG_GEMM_PATH_BF16);
-    g_gemm_a16_launches.fetch_add(1, std::memory_order_relaxed);
-#define SKG_LAUNCH(E)                                                                                   \
-    if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 1>), grid, block, 0, s, d, a16, w16);    \
-    else hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 2>), grid, block, 0, s, d, a16, w16);
-    switch (d.epilogue) {
-        case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
-        case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;
-        case SKG_EPI_MUL_RELU:      SKG_LAUNCH(SKG_EPI_MUL_RELU) break;
-        case SKG_EPI_RELU_DOT:      SKG_LAUNCH(SKG_EPI_RELU_DOT) break;
-        case SKG_EPI_BIAS_RES_RELU: SKG_LAUNCH(SKG_EPI_BIAS_RES_RELU) break;
-    }
-#undef SKG_LAUNCH
-    if (d.split_k > 1) {
-        const int64_t total = (int64_t)d.M * d.N;
-        hipLaunchKernelGGL(skg_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d);
-    }
-    return skg_launch_status();
-}
-
-extern "C" int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uint16_t* const* w16_host, int n,
-                                      void* stream) {
-    if (!descs_host || !w16_host || n < 1 || n > SKG_GEMM_GROUP_MAX) return SKG_E_ARG;
-    skg_gemm_desc descs[SKG_GEMM_GROUP_MAX];
-    for (int i = 0; i < n; ++i) {
-        descs[i] = descs_host[i];
-        descs[i].w_split = nullptr; descs[i].a_exp = nullptr;          // ignored here (the tile scale reads w_split)
-        const int rc = skg_gemm_b16_check(descs[i], w16_host[i]);
-        if (rc) return rc;
-    }
-    const bool small = skg_gemm_group_small(descs, n);
-    skg_gemm_group_b16_args a;
-    skg_gemm_group_args r;
-    a.g.n = r.n = 0;
-    int64_t blocks = 0, rblocks = 0;
-    for (int i = 0; i < n; ++i) {
-        const skg_gemm_desc& d = descs[i];
-        if (d.split_k > 1 && !small) return SKG_E_ARG;                     // split-K only with the 64 x 64 tiles
-        if (d.M == 0) continue;
-        const int64_t nb = skg_gemm_blocks(d.M, d.N, d.K, small ? 1 : 2) * (d.split_k > 1 ? d.split_k : 1);
-        if (blocks + nb > 0x7fffffffLL) return SKG_E_LIMIT;
-        a.g.d[a.g.n] = d;
-        a.w16[a.g.n] = w16_host[i];
-        a.g.start[a.g.n] = (int)blocks;
-        blocks += nb;
-        ++a.g.n;
-        if (d.split_k > 1) {
-            r.d[r.n] = d;
-            r.start[r.n] = (int)rblocks;
-            rblocks += ((int64_t)d.M * d.N + 255) / 256;
-            ++r.n;
-        }
-    }
-    if (a.g.n == 0) return 0;
-    for (int i = a.g.n; i <= SKG_GEMM_GROUP_MAX; ++i) a.g.start[i] = (int)blocks;
-    for (int i = a.g.n; i < SKG_GEMM_GROUP_MAX; ++i) a.w16[i] = nullptr;
-    skg_gemm_count(SKG_GEMM_PATH_BF16);
-    if (small) hipLaunchKernelGGL(skg_gemm_group_b16_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(skg_gemm_group_b16_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    if (r.n) {
-        for (int i = r.n; i <= SKG_GEMM_GROUP_MAX; ++i) r.start[i] = (int)rblocks;
-        hipLaunchKernelGGL(skg_splitk_reduce_group_kernel, dim3((unsigned)rblocks), dim3(256), 0, (hipStream_t)stream, r);
-    }
-    return skg_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------ bf16 activations (skg_gemm_b16_x)
-// The bf16 launches with an optional bf16 A (a16, MODE 7) and an optional bf16 output (c16, beside or instead of d.C): what
-// inference_activations = "bf16" stores the GEMM-only panels of the eval forward in.  The launch shape -- tile scale, block
-// map, split-K -- is that of skg_gemm_b16_f32 / skg_gemm_group_b16_f32 on the same descriptor: it never depends on whether A
-// or C is bf16, so a chain of these launches reproduces the fp32-panel chain bit for bit (the consumer would have rounded
-// the fp32 panel with the conversion the producer stored it with).
-template <int EPI, int MODE, int T>
-__global__ __launch_bounds__(256, 2) void skg_gemm_b16x_kernel(const skg_gemm_desc d, const uint16_t* a16, const uint16_t* w16,
-                                                               uint16_t* c16, int64_t ldc16) {
-    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
-    skg_gemm_tile<EPI, MODE, T, true>(d, blockIdx.x, smem, w16, a16, c16, ldc16);
-}
-
-struct skg_gemm_group_b16x_args {
-    skg_gemm_group_args g;
-    const uint16_t* w16[SKG_GEMM_GROUP_MAX];
-    const uint16_t* a16[SKG_GEMM_GROUP_MAX];
-    uint16_t* c16[SKG_GEMM_GROUP_MAX];
-    int64_t ldc16[SKG_GEMM_GROUP_MAX];
-};
-
-// members mix freely: the main loop (MODE 6 / 7) is picked per member on a workgroup-uniform flag
-template <int T>
-__global__ __launch_bounds__(256, 2) void skg_gemm_group_b16x_kernel(const skg_gemm_group_b16x_args a) {
-    __shared__ __attribute__((aligned(1024))) float smem[SKG_SMEM6(T)];
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < a.g.n && (int)blockIdx.x >= a.g.start[t]) k = t;
-    if (a.a16[k]) skg_gemm_tile<-1, 7, T, true>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k], a.a16[k], a.c16[k], a.ldc16[k]);
-    else skg_gemm_tile<-1, 6, T, true>(a.g.d[k], blockIdx.x - a.g.start[k], smem, a.w16[k], nullptr, a.c16[k], a.ldc16[k]);
-}
-
-__global__ __launch_bounds__(256) void skg_splitk_reduce_x_kernel(const skg_gemm_desc d, uint16_t* c16, int64_t ldc16) {
-    skg_splitk_reduce_one(d, (int64_t)blockIdx.x * 256 + threadIdx.x, c16, ldc16);
-}
-
-struct skg_splitk_reduce_group_x_args {
-    skg_gemm_group_args g;
-    uint16_t* c16[SKG_GEMM_GROUP_MAX];
-    int64_t ldc16[SKG_GEMM_GROUP_MAX];
-};
-
-__global__ __launch_bounds__(256) void skg_splitk_reduce_group_x_kernel(const skg_splitk_reduce_group_x_args a) {
-    int k = 0;
-#pragma unroll
-    for (int t = 1; t < SKG_GEMM_GROUP_MAX; ++t)
-        if (t < a.g.n && (int)blockIdx.x >= a.g.start[t]) k = t;
-    skg_splitk_reduce_one(a.g.d[k], (int64_t)(blockIdx.x - a.g.start[k]) * 256 + threadIdx.x, a.c16[k], a.ldc16[k]);
-}
-
-// launches, members with a16, members with c16 (members of M == 0 launch nothing and are not counted)
-static std::atomic<long long> g_gemm_b16x[3];
-
-extern "C" void skg_gemm_b16_x_counts(int64_t* out3, int reset) {
-    for (int i = 0; i < 3; ++i) {
-        if (out3) out3[i] = g_gemm_b16x[i].load(std::memory_order_relaxed);
-        if (reset) g_gemm_b16x[i].store(0, std::memory_order_relaxed);
-    }
-}
-
-// Checks one member and prepares the descriptor the kernels get: w_split / a_exp cleared, as in skg_gemm_b16_f32.  The
+// Checks one member and prepares the descriptor the kernels get: w_split / a_exp cleared (the tile scale reads w_split).  The
 // generic checks run on a copy whose A is a16 and whose C is c16 where those stand in (only non-null / aligned is asked).
 static int skg_gemm_b16x_check(skg_gemm_desc& d, const skg_gemm_b16_io* io) {
     if (!io || !io->w16) return SKG_E_ARG;
@@ -1905,14 +1794,85 @@ static int skg_gemm_b16x_check(skg_gemm_desc& d, const skg_gemm_b16_io* io) {
     skg_gemm_desc v = d;
     if (io->a16) {
         if (d.a_rows) return SKG_E_ARG;                                 // no gathers: A is staged by whole rows
-        if (!skg_aligned16(io->a16) || (d.lda & 7) || (d.K & 7)) return SKG_E_ALIGN;
+        if (!skg_aligned16(io->a16) || (d.lda & 7) || (d.K & 7)) return SKG_E_ALIGN;   // 16-byte DMA pieces of whole k-chunks
         v.A = reinterpret_cast<const float*>(io->a16);
     }
     if (!v.C) v.C = reinterpret_cast<float*>(io->c16);
     return skg_gemm_b16_check(v, io->w16);
 }
 
-extern "C" int skg_gemm_b16_x(const skg_gemm_desc* dh, const skg_gemm_b16_io* io, void* stream) {
+// launches of skg_gemm_b16_a16_f32; of skg_gemm_b16_x / skg_gemm_group_b16_x: launches, members with a16, members with c16
+// (members of M == 0 launch nothing and are not counted)
+static std::atomic<long long> g_gemm_a16_launches;
+static std::atomic<long long> g_gemm_b16x[3];
+
+extern "C" void skg_gemm_b16_a16_launches(int64_t* out_host, int reset) {
+    if (out_host) *out_host = g_gemm_a16_launches.load(std::memory_order_relaxed);
+    if (reset) g_gemm_a16_launches.store(0, std::memory_order_relaxed);
+}
+
+extern "C" void skg_gemm_b16_x_counts(int64_t* out3, int reset) {
+    for (int i = 0; i < 3; ++i) {
+        if (out3) out3[i] = g_gemm_b16x[i].load(std::memory_order_relaxed);
+        if (reset) g_gemm_b16x[i].store(0, std::memory_order_relaxed);
+    }
+}
+
+// The main kernel of a single launch that stores fp32 only: MODE 6, or MODE 7 with A staged from a16 like W.
+static void skg_gemm_b16_launch_f32(const skg_gemm_desc& d, const uint16_t* a16, const uint16_t* w16, int T, dim3 grid,
+                                    hipStream_t s) {
+    const dim3 block(256);
+    if (!a16) skg_gemm_with_epilogue(d.epilogue, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 1>), grid, block, 0, s, d, w16);
+        else hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 2>), grid, block, 0, s, d, w16);
+    });
+    else skg_gemm_with_epilogue(d.epilogue, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 1>), grid, block, 0, s, d, a16, w16);
+        else hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 2>), grid, block, 0, s, d, a16, w16);
+    });
+}
+
+// Checks and member loop of the grouped bf16 entries (descriptors and ios by the caller's index); small: 64 x 64 tiles.
+static int skg_gemm_group_b16_fill(const skg_gemm_desc* descs_host, const skg_gemm_b16_io* ios, int n, bool& small,
+                                   skg_gemm_group_args& g, skg_gemm_group_args& r, skg_gemm_group_plan& p) {
+    skg_gemm_desc descs[SKG_GEMM_GROUP_MAX];
+    for (int i = 0; i < n; ++i) {
+        descs[i] = descs_host[i];
+        const int rc = skg_gemm_b16x_check(descs[i], &ios[i]);
+        if (rc) return rc;
+    }
+    small = skg_gemm_group_small(descs, n);                            // (reads M, N, K, lda, ldw, a_rows: not A / C)
+    return skg_gemm_group_fill(descs, n, small, g, r, p);
+}
+
+extern "C" int skg_gemm_group_b16_f32(const skg_gemm_desc* descs_host, const uint16_t* const* w16_host, int n,
+                                      void* stream) {
+    if (!descs_host || !w16_host || n < 1 || n > SKG_GEMM_GROUP_MAX) return SKG_E_ARG;
+    skg_gemm_b16_io ios[SKG_GEMM_GROUP_MAX];
+    for (int i = 0; i < n; ++i) ios[i] = {w16_host[i], nullptr, nullptr, 0};
+    skg_gemm_group_b16_args a;
+    skg_gemm_group_args r;
+    skg_gemm_group_plan p;
+    bool small;
+    const int rc = skg_gemm_group_b16_fill(descs_host, ios, n, small, a.g, r, p);
+    if (rc || a.g.n == 0) return rc;
+    for (int m = 0; m < SKG_GEMM_GROUP_MAX; ++m) a.w16[m] = m < a.g.n ? w16_host[p.src[m]] : nullptr;
+    const dim3 grid((unsigned)p.blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    skg_gemm_count(SKG_GEMM_PATH_BF16);
+    if (small) hipLaunchKernelGGL(skg_gemm_group_b16_kernel<1>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(skg_gemm_group_b16_kernel<2>, grid, block, 0, s, a);
+    if (r.n) hipLaunchKernelGGL(skg_splitk_reduce_group_kernel, dim3((unsigned)p.rblocks), block, 0, s, r);
+    return skg_launch_status();
+}
+
+// The single bf16 launch behind skg_gemm_b16_f32, skg_gemm_b16_a16_f32 and skg_gemm_b16_x.  What differs per entry: which
+// counters move, and that skg_gemm_b16_x reduces its split-K slices with the kernel that takes c16.
+enum skg_gemm_b16_entry { SKG_B16_F32, SKG_B16_A16_F32, SKG_B16_X };
+
+static int skg_gemm_b16_single(const skg_gemm_desc* dh, const skg_gemm_b16_io* io, void* stream, skg_gemm_b16_entry entry) {
     if (!dh) return SKG_E_ARG;
     skg_gemm_desc d = *dh;
     const int rc = skg_gemm_b16x_check(d, io);
@@ -1922,96 +1882,74 @@ extern "C" int skg_gemm_b16_x(const skg_gemm_desc* dh, const skg_gemm_b16_io* io
     const uint16_t* w16 = io->w16;
     uint16_t* c16 = io->c16;
     const int64_t ldc16 = io->ldc16;
-    if (a16) d.A = reinterpret_cast<const float*>(a16);                 // (not read by MODE 7; as skg_gemm_b16_a16_f32 passes it)
+    if (a16) d.A = reinterpret_cast<const float*>(a16);                 // (not read by MODE 7: the kernels get a non-null A)
     const int T = skg_gemm_tile_scale(&d);
-    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * (d.split_k > 1 ? d.split_k : 1);
+    const int64_t nblk = skg_gemm_blocks(d.M, d.N, d.K, T) * skg_gemm_slices(d);
     if (nblk > 0x7fffffffLL) return SKG_E_LIMIT;
-    dim3 grid((unsigned)nblk), block(256);
+    const dim3 grid((unsigned)nblk), block(256);
     hipStream_t s = (hipStream_t)stream;
     skg_gemm_count(SKG_GEMM_PATH_BF16);
-    g_gemm_b16x[0].fetch_add(1, std::memory_order_relaxed);
-    if (a16) g_gemm_b16x[1].fetch_add(1, std::memory_order_relaxed);
-    if (c16) g_gemm_b16x[2].fetch_add(1, std::memory_order_relaxed);
-    // a split-K main kernel writes split_ws only, and a launch without c16 stores fp32 only: the kernels of
-    // skg_gemm_b16_f32 / skg_gemm_b16_a16_f32 serve both
-    const bool plain = !c16 || d.split_k > 1;
-#define SKG_LAUNCH(E)                                                                                                   \
-    if (plain && a16 && T == 1) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 1>), grid, block, 0, s, d, a16, w16);       \
-    else if (plain && a16) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<E, 2>), grid, block, 0, s, d, a16, w16);            \
-    else if (plain && T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 1>), grid, block, 0, s, d, w16);                  \
-    else if (plain) hipLaunchKernelGGL((skg_gemm_b16_kernel<E, 2>), grid, block, 0, s, d, w16);                            \
-    else if (a16 && T == 1) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 7, 1>), grid, block, 0, s, d, a16, w16, c16, ldc16); \
-    else if (a16) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 7, 2>), grid, block, 0, s, d, a16, w16, c16, ldc16);         \
-    else if (T == 1) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 6, 1>), grid, block, 0, s, d, a16, w16, c16, ldc16);      \
-    else hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 6, 2>), grid, block, 0, s, d, a16, w16, c16, ldc16);
-    switch (d.epilogue) {
-        case SKG_EPI_BIAS:          SKG_LAUNCH(SKG_EPI_BIAS) break;
-        case SKG_EPI_BIAS_RELU:     SKG_LAUNCH(SKG_EPI_BIAS_RELU) break;
-        case SKG_EPI_MUL_RELU:      SKG_LAUNCH(SKG_EPI_MUL_RELU) break;
-        case SKG_EPI_BIAS_RES_RELU: SKG_LAUNCH(SKG_EPI_BIAS_RES_RELU) break;
-        case SKG_EPI_RELU_DOT:                                          // (never with c16: checked above)
-            if (a16 && T == 1) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<SKG_EPI_RELU_DOT, 1>), grid, block, 0, s, d, a16, w16);
-            else if (a16) hipLaunchKernelGGL((skg_gemm_b16_a16_kernel<SKG_EPI_RELU_DOT, 2>), grid, block, 0, s, d, a16, w16);
-            else if (T == 1) hipLaunchKernelGGL((skg_gemm_b16_kernel<SKG_EPI_RELU_DOT, 1>), grid, block, 0, s, d, w16);
-            else hipLaunchKernelGGL((skg_gemm_b16_kernel<SKG_EPI_RELU_DOT, 2>), grid, block, 0, s, d, w16);
-            break;
+    if (entry == SKG_B16_A16_F32) g_gemm_a16_launches.fetch_add(1, std::memory_order_relaxed);
+    if (entry == SKG_B16_X) {
+        g_gemm_b16x[0].fetch_add(1, std::memory_order_relaxed);
+        if (a16) g_gemm_b16x[1].fetch_add(1, std::memory_order_relaxed);
+        if (c16) g_gemm_b16x[2].fetch_add(1, std::memory_order_relaxed);
     }
-#undef SKG_LAUNCH
-    if (d.split_k > 1) {
-        const int64_t total = (int64_t)d.M * d.N;
-        hipLaunchKernelGGL(skg_splitk_reduce_x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d, c16, ldc16);
-    }
+    // a split-K main kernel writes split_ws only, and a launch without c16 stores fp32 only: the fp32-store kernels serve both
+    if (!c16 || d.split_k > 1) skg_gemm_b16_launch_f32(d, a16, w16, T, grid, s);
+    else skg_gemm_with_epilogue(d.epilogue, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        if constexpr (E != SKG_EPI_RELU_DOT) {                          // RELU_DOT never takes the C16 kernels (checked above)
+            if (a16 && T == 1) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 7, 1>), grid, block, 0, s, d, a16, w16, c16, ldc16);
+            else if (a16) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 7, 2>), grid, block, 0, s, d, a16, w16, c16, ldc16);
+            else if (T == 1) hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 6, 1>), grid, block, 0, s, d, a16, w16, c16, ldc16);
+            else hipLaunchKernelGGL((skg_gemm_b16x_kernel<E, 6, 2>), grid, block, 0, s, d, a16, w16, c16, ldc16);
+        }
+    });
+    skg_gemm_reduce_tail(d, s, entry == SKG_B16_X, c16, ldc16);
     return skg_launch_status();
+}
+
+extern "C" int skg_gemm_b16_f32(const skg_gemm_desc* dh, const uint16_t* w16, void* stream) {
+    const skg_gemm_b16_io io = {w16, nullptr, nullptr, 0};
+    return skg_gemm_b16_single(dh, &io, stream, SKG_B16_F32);
+}
+
+extern "C" int skg_gemm_b16_a16_f32(const skg_gemm_desc* dh, const uint16_t* a16, const uint16_t* w16, void* stream) {
+    if (!a16) return SKG_E_ARG;
+    const skg_gemm_b16_io io = {w16, a16, nullptr, 0};
+    return skg_gemm_b16_single(dh, &io, stream, SKG_B16_A16_F32);
+}
+
+extern "C" int skg_gemm_b16_x(const skg_gemm_desc* dh, const skg_gemm_b16_io* io, void* stream) {
+    return skg_gemm_b16_single(dh, io, stream, SKG_B16_X);
 }
 
 extern "C" int skg_gemm_group_b16_x(const skg_gemm_desc* descs_host, const skg_gemm_b16_io* ios, int n, void* stream) {
     if (!descs_host || !ios || n < 1 || n > SKG_GEMM_GROUP_MAX) return SKG_E_ARG;
-    skg_gemm_desc descs[SKG_GEMM_GROUP_MAX];
-    for (int i = 0; i < n; ++i) {
-        descs[i] = descs_host[i];
-        const int rc = skg_gemm_b16x_check(descs[i], &ios[i]);
-        if (rc) return rc;
-    }
-    const bool small = skg_gemm_group_small(descs, n);                 // (reads M, N, K, lda, ldw, a_rows: not A / C)
     skg_gemm_group_b16x_args a;
     skg_splitk_reduce_group_x_args r;
-    a.g.n = r.g.n = 0;
-    int64_t blocks = 0, rblocks = 0;
+    skg_gemm_group_plan p;
+    bool small;
+    const int rc = skg_gemm_group_b16_fill(descs_host, ios, n, small, a.g, r.g, p);
+    if (rc || a.g.n == 0) return rc;
+    static const skg_gemm_b16_io none = {nullptr, nullptr, nullptr, 0};
     int n_a16 = 0, n_c16 = 0;
-    for (int i = 0; i < n; ++i) {
-        const skg_gemm_desc& d = descs[i];
-        if (d.split_k > 1 && !small) return SKG_E_ARG;                     // split-K only with the 64 x 64 tiles
-        if (d.M == 0) continue;
-        const int64_t nb = skg_gemm_blocks(d.M, d.N, d.K, small ? 1 : 2) * (d.split_k > 1 ? d.split_k : 1);
-        if (blocks + nb > 0x7fffffffLL) return SKG_E_LIMIT;
-        const int m = a.g.n;
-        a.g.d[m] = d;
-        a.w16[m] = ios[i].w16; a.a16[m] = ios[i].a16; a.c16[m] = ios[i].c16; a.ldc16[m] = ios[i].ldc16;
-        a.g.start[m] = (int)blocks;
-        blocks += nb;
-        ++a.g.n;
-        n_a16 += ios[i].a16 != nullptr; n_c16 += ios[i].c16 != nullptr;
-        if (d.split_k > 1) {
-            r.g.d[r.g.n] = d;
-            r.c16[r.g.n] = ios[i].c16; r.ldc16[r.g.n] = ios[i].ldc16;
-            r.g.start[r.g.n] = (int)rblocks;
-            rblocks += ((int64_t)d.M * d.N + 255) / 256;
-            ++r.g.n;
-        }
+    for (int m = 0; m < SKG_GEMM_GROUP_MAX; ++m) {
+        const skg_gemm_b16_io& o = m < a.g.n ? ios[p.src[m]] : none;
+        const skg_gemm_b16_io& ro = m < r.g.n ? ios[p.rsrc[m]] : none;
+        a.w16[m] = o.w16; a.a16[m] = o.a16; a.c16[m] = o.c16; a.ldc16[m] = o.ldc16;
+        r.c16[m] = ro.c16; r.ldc16[m] = ro.ldc16;
+        n_a16 += o.a16 != nullptr; n_c16 += o.c16 != nullptr;
     }
-    if (a.g.n == 0) return 0;
-    for (int i = a.g.n; i <= SKG_GEMM_GROUP_MAX; ++i) a.g.start[i] = (int)blocks;
-    for (int i = a.g.n; i < SKG_GEMM_GROUP_MAX; ++i) { a.w16[i] = nullptr; a.a16[i] = nullptr; a.c16[i] = nullptr; a.ldc16[i] = 0; }
+    const dim3 grid((unsigned)p.blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
     skg_gemm_count(SKG_GEMM_PATH_BF16);
     g_gemm_b16x[0].fetch_add(1, std::memory_order_relaxed);
     g_gemm_b16x[1].fetch_add(n_a16, std::memory_order_relaxed);
     g_gemm_b16x[2].fetch_add(n_c16, std::memory_order_relaxed);
-    if (small) hipLaunchKernelGGL(skg_gemm_group_b16x_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(skg_gemm_group_b16x_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    if (r.g.n) {
-        for (int i = r.g.n; i <= SKG_GEMM_GROUP_MAX; ++i) r.g.start[i] = (int)rblocks;
-        for (int i = r.g.n; i < SKG_GEMM_GROUP_MAX; ++i) { r.c16[i] = nullptr; r.ldc16[i] = 0; }
-        hipLaunchKernelGGL(skg_splitk_reduce_group_x_kernel, dim3((unsigned)rblocks), dim3(256), 0, (hipStream_t)stream, r);
-    }
+    if (small) hipLaunchKernelGGL(skg_gemm_group_b16x_kernel<1>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(skg_gemm_group_b16x_kernel<2>, grid, block, 0, s, a);
+    if (r.g.n) hipLaunchKernelGGL(skg_splitk_reduce_group_x_kernel, dim3((unsigned)p.rblocks), block, 0, s, r);
     return skg_launch_status();
 }

@@ -268,13 +268,33 @@ import threading as _threading
 _TLS = _threading.local()     # .splits: the SplitWeights in force on this thread (inside a fp16x2 engine call), else None
 
 
+class _ThreadCurrent:
+    """Context manager that makes its value "the current one" of the calling thread: entering stores it in _TLS under
+    the class's _slot, leaving puts back what was there, so blocks nest and other threads never see it."""
+    _slot = None
+    _default = None
+
+    def _value(self):
+        return self
+
+    def __enter__(self):
+        self._prev = getattr(_TLS, self._slot, self._default)
+        setattr(_TLS, self._slot, self._value())
+        return self
+
+    def __exit__(self, *a):
+        setattr(_TLS, self._slot, self._prev)
+        return False
+
+
 def _active_splits():
     return getattr(_TLS, "splits", None)
 
 
-class SplitWeights:
+class SplitWeights(_ThreadCurrent):
     """fp16x2 twins of nn.Linear weights for skg_gemm_desc.w_split, made on first use and kept with the packed
     weights they mirror (keyed by the weight view: address, N, K, leading dimension)."""
+    _slot = "splits"
 
     def __init__(self):
         self.twins = {}
@@ -299,25 +319,17 @@ class SplitWeights:
             self.twins[key] = t
         return t[0], t[1]
 
-    def __enter__(self):
-        self._prev = _active_splits()
-        _TLS.splits = self
-        return self
-
-    def __exit__(self, *a):
-        _TLS.splits = self._prev
-        return False
-
 
 def _active_bf16():
     return getattr(_TLS, "bf16", None)
 
 
-class Bf16Weights:
+class Bf16Weights(_ThreadCurrent):
     """bf16 twins of the packed weights for skg_gemm_b16_f32 (inference_precision="bf16"): one twin per packed weight
     tensor, with the tensor's element indexing (a column sub-view of the weight is the twin's base plus the same element
     offset), made on first use -- before any capture: the eager pass ahead of a plan's capture makes them -- and kept with
     the packed weights they mirror."""
+    _slot = "bf16"
 
     def __init__(self):
         self.twins = {}
@@ -337,15 +349,6 @@ class Bf16Weights:
             t = (twin, W)                                    # holding W keeps its address from being reused
             self.twins[key] = t
         return t[0].data_ptr() + 2 * W_off
-
-    def __enter__(self):
-        self._prev = _active_bf16()
-        _TLS.bf16 = self
-        return self
-
-    def __exit__(self, *a):
-        _TLS.bf16 = self._prev
-        return False
 
 
 def gemm_desc(A, W, bias, C_out, M, N, K, epilogue, lda=None, ldw=None, ldc=None, a_rows=None, out_rows=None, P=None,
@@ -411,21 +414,18 @@ def gemm_io(A, W, C_out, kw, io=None):
     return io
 
 
-class activations16:
+class activations16(_ThreadCurrent):
     """While active on this thread, products whose A is a bf16 panel are launched through skg_gemm_b16_x (the eval forward
     under inference_activations='bf16').  Results do not depend on it: only which entry point, and so which counter."""
+
+    _slot = "act16"
+    _default = False
 
     def __init__(self, on=True):
         self.on = bool(on)
 
-    def __enter__(self):
-        self._prev = getattr(_TLS, "act16", False)
-        _TLS.act16 = self.on
-        return self
-
-    def __exit__(self, *a):
-        _TLS.act16 = self._prev
-        return False
+    def _value(self):
+        return self.on
 
 
 # ---- row exponents of the split-operand (fp16x2) GEMMs' A operands (power-of-two row scale, include/skghoi.h): one small
@@ -501,28 +501,47 @@ def bf16_rows(x, W):
     return x
 
 
-def gemm(A, W, bias, C_out, M, N, K, epilogue, **kw):
-    """One skg_gemm_f32 launch (see gemm_desc for the keywords).  A bf16 A (bf16_rows) goes to skg_gemm_b16_a16_f32, which
-    needs the bf16 weight twins (a Bf16Weights context)."""
-    if uses_b16_io(A, C_out, kw):
-        return _gemm_b16x(A, W, bias, C_out, M, N, K, epilogue, **kw)
-    if A.dtype == torch.bfloat16:
-        return _gemm_a16(A, W, bias, C_out, M, N, K, epilogue, **kw)
-    d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
-    w16 = weight_twin(W, kw.get("W_off", 0), kw.get("w_split"))
-    keep_exp = enqueue_row_exponents(d, A.device) if d.w_split else None
-    timed = GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or epilogue in GEMM_TIMER_EPI)
+def gemm_entry(d, w16=0, a16=0, io=None):
+    """-> (entry, arguments) of the single launch of descriptor d, by what comes with it: skg_gemm_b16_x with an io,
+    skg_gemm_b16_a16_f32 with a bf16 A (address a16; needs the twin w16), skg_gemm_b16_f32 with the twin alone, else
+    skg_gemm_f32."""
+    lib = _capi.lib()
+    if io is not None:
+        return lib.skg_gemm_b16_x, (C.byref(d), C.byref(io))
+    if a16:
+        return lib.skg_gemm_b16_a16_f32, (C.byref(d), a16, w16)
+    if w16:
+        return lib.skg_gemm_b16_f32, (C.byref(d), w16)
+    return lib.skg_gemm_f32, (C.byref(d),)
+
+
+def gemm_launch(entry, args, what, timer=None):
+    """entry(*args, stream) under _capi.check, named "entry[what]" in the error.  timer = (M, N, K, epilogue id): the
+    launch sits between two events in GEMM_TIMER when that collects the id."""
+    timed = timer is not None and GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or timer[3] in GEMM_TIMER_EPI)
     if timed:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-    if w16:
-        _capi.check(_capi.lib().skg_gemm_b16_f32(C.byref(d), w16, _stream()),
-                    "skg_gemm_b16_f32[%dx%dx%d epi %d]" % (M, N, K, epilogue))
-    else:
-        _capi.check(_capi.lib().skg_gemm_f32(C.byref(d), _stream()), "skg_gemm_f32[%dx%dx%d epi %d]" % (M, N, K, epilogue))
+    rc = entry(*args, _stream())
+    if rc:
+        _capi.check(rc, "%s[%s]" % (entry.__name__, what))
     if timed:
         e1.record()
-        GEMM_TIMER.append((e0, e1, M, N, K, epilogue))
+        GEMM_TIMER.append((e0, e1) + timer)
+
+
+def gemm(A, W, bias, C_out, M, N, K, epilogue, **kw):
+    """One launch of the eval GEMM (see gemm_desc for the keywords), on the entry gemm_entry picks: a bf16 output, or a bf16
+    A inside activations16(), goes to skg_gemm_b16_x; any other bf16 A (bf16_rows) to skg_gemm_b16_a16_f32; both need the
+    bf16 weight twins (a Bf16Weights context), which alone select skg_gemm_b16_f32."""
+    io = gemm_io(A, W, C_out, kw) if uses_b16_io(A, C_out, kw) else None
+    a16 = A.data_ptr() if (io is None and A.dtype == torch.bfloat16) else 0
+    w16 = weight_twin(W, kw.get("W_off", 0), kw.get("w_split")) if io is None else 0
+    if a16 and not w16:
+        raise _capi.SkgError("a bf16 A operand needs the bf16 weight twins (inference_precision='bf16')")
+    d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
+    keep_exp = enqueue_row_exponents(d, A.device) if (d.w_split and io is None and not a16) else None
+    gemm_launch(*gemm_entry(d, w16, a16, io), "%dx%dx%d epi %d" % (M, N, K, epilogue), (M, N, K, epilogue))
 
 
 # Workgroups a small (64 x 64 tile) grouped launch aims for; split-K supplies them.  Two costs pull against each other at a
@@ -531,39 +550,6 @@ def gemm(A, W, bias, C_out, M, N, K, epilogue, **kw):
 # re-swept at the end of round 4 (64-k steps, two stages in flight): 320 / 384 / 448 / 512 -> single 20 x 20 image 0.483-0.488 /
 # 0.474-0.482 / 0.502-0.504 / 0.498-0.499 ms, batches of 2 and 4 level, a stream of mixed shapes level (0.46-0.47 either way).
 SMALL_GROUP_BLOCKS = int(os.environ.get("SKG_SMALL_GROUP_BLOCKS") or 384)     # (the env override: developer sweeps)
-
-
-def _gemm_a16(A, W, bias, C_out, M, N, K, epilogue, **kw):
-    """gemm() with a bf16 A operand ([M, lda] bf16, lda % 8 == 0): one skg_gemm_b16_a16_f32 launch."""
-    w16 = weight_twin(W, kw.get("W_off", 0), kw.get("w_split"))
-    if not w16:
-        raise _capi.SkgError("a bf16 A operand needs the bf16 weight twins (inference_precision='bf16')")
-    d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
-    d.A = 0                                                  # (not read: the entry takes A from a16)
-    timed = GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or epilogue in GEMM_TIMER_EPI)
-    if timed:
-        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _capi.check(_capi.lib().skg_gemm_b16_a16_f32(C.byref(d), A.data_ptr(), w16, _stream()),
-                "skg_gemm_b16_a16_f32[%dx%dx%d epi %d]" % (M, N, K, epilogue))
-    if timed:
-        e1.record()
-        GEMM_TIMER.append((e0, e1, M, N, K, epilogue))
-
-
-def _gemm_b16x(A, W, bias, C_out, M, N, K, epilogue, **kw):
-    """gemm() with a bf16 A and / or a bf16 output: one skg_gemm_b16_x launch (same launch shape as skg_gemm_b16_f32)."""
-    io = gemm_io(A, W, C_out, kw)
-    d = gemm_desc(A, W, bias, C_out, M, N, K, epilogue, **kw)
-    timed = GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or epilogue in GEMM_TIMER_EPI)
-    if timed:
-        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _capi.check(_capi.lib().skg_gemm_b16_x(C.byref(d), C.byref(io), _stream()),
-                "skg_gemm_b16_x[%dx%dx%d epi %d]" % (M, N, K, epilogue))
-    if timed:
-        e1.record()
-        GEMM_TIMER.append((e0, e1, M, N, K, epilogue))
 
 
 def gemm_group(specs):
@@ -600,19 +586,13 @@ def gemm_group(specs):
                 ws = torch.empty(sk * d.M * d.N, device=specs[0][0][0].device, dtype=torch.float32)
                 keep.append(ws)
                 d.split_k = sk; d.split_ws = ws.data_ptr()
-    timed = GEMM_TIMER is not None and (GEMM_TIMER_EPI is None or 5 in GEMM_TIMER_EPI)
-    if timed:
-        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
     if b16x:
-        _capi.check(lib.skg_gemm_group_b16_x(arr, ios, n, _stream()), "skg_gemm_group_b16_x[%d]" % n)
+        entry, args = lib.skg_gemm_group_b16_x, (arr, ios, n)
     elif any(w16):
-        _capi.check(lib.skg_gemm_group_b16_f32(arr, w16, n, _stream()), "skg_gemm_group_b16_f32[%d]" % n)
+        entry, args = lib.skg_gemm_group_b16_f32, (arr, w16, n)
     else:
-        _capi.check(lib.skg_gemm_group_f32(arr, n, _stream()), "skg_gemm_group_f32[%d]" % n)
-    if timed:
-        e1.record()
-        GEMM_TIMER.append((e0, e1, int(flops // 2), 1, 1, 5))       # epilogue id 5 = grouped launch
+        entry, args = lib.skg_gemm_group_f32, (arr, n)
+    gemm_launch(entry, args, n, (int(flops // 2), 1, 1, 5))               # epilogue id 5 = grouped launch
 
 
 class _NullCtx:

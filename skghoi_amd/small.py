@@ -44,8 +44,8 @@ import numpy as np
 import torch
 
 from . import _capi, layout, transh
-from .engine import Preprocessed, activations16, bf16_rows, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_group, \
-    gemm_io, pick_split_k, _stream, weight_twin
+from .engine import Preprocessed, activations16, bf16_rows, current_stream_of, enqueue_row_exponents, gemm_desc, gemm_entry, \
+    gemm_group, gemm_io, gemm_launch, pick_split_k, _stream, weight_twin
 
 META_WORDS = layout.META_DTYPE.itemsize // 4
 
@@ -559,16 +559,10 @@ class SmallBatchRunner:
         p.bh1_desc.M = n_act                       # plans) its row count
         if p.bh1_desc.w_split:
             p.bh1_exp = enqueue_row_exponents(p.bh1_desc, x0.device)
+        a16 = x16.data_ptr() if (x16 is not None and p.bh1_w16) else 0
         if p.bh1_io is not None:
-            p.bh1_io.a16 = x16.data_ptr() if x16 is not None else None
-            _capi.check(lib.skg_gemm_b16_x(C.byref(p.bh1_desc), C.byref(p.bh1_io), _stream()), "skg_gemm_b16_x[box_head 1]")
-        elif p.bh1_w16 and x16 is not None:
-            _capi.check(lib.skg_gemm_b16_a16_f32(C.byref(p.bh1_desc), x16.data_ptr(), p.bh1_w16, _stream()),
-                        "skg_gemm_b16_a16_f32[box_head 1]")
-        elif p.bh1_w16:
-            _capi.check(lib.skg_gemm_b16_f32(C.byref(p.bh1_desc), p.bh1_w16, _stream()), "skg_gemm_b16_f32[box_head 1]")
-        else:
-            _capi.check(lib.skg_gemm_f32(C.byref(p.bh1_desc), _stream()), "skg_gemm_f32[box_head 1]")
+            p.bh1_io.a16 = a16 or None
+        gemm_launch(*gemm_entry(p.bh1_desc, p.bh1_w16, a16, p.bh1_io), "box_head 1")
         # per-call records: meta (image sizes, result offsets), cell count, TransH entity tables
         if p.h2d_done is not None:
             p.h2d_done.synchronize()               # the staging block's previous copy (normally long finished)

@@ -117,15 +117,24 @@ def transh_forward(ent, rel, nrm, heads, relations, tails):
 
 
 # ----------------------------------------------------------------------------- MBF (HEAD:431-530)
-class Params:
-    """Thin view on a reference-keyed state dict."""
+def plain_linear(name, x, weight, bias):
+    """The default `linear` of this module: every dense layer is F.linear, whatever its name."""
+    return F.linear(x, weight, bias)
 
-    def __init__(self, sd, prefix="box_pair_head."):
+
+class Params:
+    """Thin view on a reference-keyed state dict.  `linear(name, x, weight, bias)`: the one callable
+    every dense layer of this module goes through -- `name` is the layer's state-dict prefix ("box_pair_head.fc_head.0",
+    "box_pair_predictor").  The default is F.linear; a test model may pass another one (tests/bf16_step_model.py rounds the
+    operands the way the bf16 training step does) and treat named layers differently."""
+
+    def __init__(self, sd, prefix="box_pair_head.", linear=None):
         self.sd = sd
         self.p = prefix
+        self.linear = linear or plain_linear
 
     def lin(self, name, x):
-        return F.linear(x, self.sd[self.p + name + ".weight"], self.sd[self.p + name + ".bias"])
+        return self.linear(self.p + name, x, self.sd[self.p + name + ".weight"], self.sd[self.p + name + ".bias"])
 
     def w(self, name):
         return self.sd[self.p + name]
@@ -184,13 +193,13 @@ def compute_prior_scores(x, y, scores, object_class, o2v, K, training):
 
 def graph_head_forward(sd, feat3, image_shapes, pooled, box_coords, box_labels, box_scores, K, human_idx, o2v,
                        targets=None, training=False, num_iter=2, fg_iou_thresh=0.5, tables=None,
-                       row_loop=False, capture=None):
+                       row_loop=False, capture=None, linear=None):
     """GraphHead.forward, HEAD:769-993.  `tables`: optional list of (ent, rel, norm) per *processed* image; when
     None they are drawn from the global CPU RNG exactly as the reference does (one fresh TransH per image).
     `row_loop=True` keeps the reference's Python loop over all G*K embedding rows (HEAD:877-883) instead
     of the equivalent strided slice -- used only when timing the CPU baseline.  `capture`: dict that receives
-    per-image intermediates."""
-    P = Params(sd)
+    per-image intermediates.  `linear`: see Params."""
+    P = Params(sd, linear=linear)
     if training:
         assert targets is not None
     global_features = F.adaptive_avg_pool2d(feat3, 1).flatten(start_dim=1)               # HEAD:811
@@ -295,7 +304,8 @@ def graph_head_forward(sd, feat3, image_shapes, pooled, box_coords, box_labels, 
 
 # ----------------------------------------------------------------------------- losses
 def binary_focal_loss(x, y, alpha=0.5, gamma=2.0, reduction="mean", eps=1e-6):
-    """ops.py:159-211."""
+    """ops.py:159-211.  (labels in the scores' dtype: a no-op in fp32, what lets a float64 state dict through)"""
+    y = y.to(x.dtype)
     loss = (1 - y - alpha).abs() * ((y - x).abs() + eps) ** gamma * F.binary_cross_entropy(x, y, reduction="none")
     return loss.mean() if reduction == "mean" else loss.sum() if reduction == "sum" else loss
 
@@ -338,10 +348,10 @@ def postprocess(logits_p, logits_s, prior, boxes_h, boxes_o, object_class, label
 
 def interaction_head_forward(sd, feat3, detections, image_shapes, pooled_fn, K, human_idx, o2v, targets=None,
                              training=False, max_human=15, max_object=15, box_nms_thresh=0.5, box_score_thresh=0.2,
-                             num_iter=2, fg_iou_thresh=0.5, tables=None, row_loop=False, capture=None):
+                             num_iter=2, fg_iou_thresh=0.5, tables=None, row_loop=False, capture=None, linear=None):
     """InteractionHead.forward, HEAD:341-429.  `pooled_fn(box_coords) -> [sum N, C, p, p]` plays box_roi_pool
     (HEAD:387).  Returns (results, extras) where extras carries logits and, in training, the three loss terms
-    (transH term per `transh_loss_intended`)."""
+    (transH term per `transh_loss_intended`).  `linear`: see Params (the predictor and the suppressor go through it too)."""
     if training:
         assert targets is not None
     det = preprocess(detections, targets, human_idx, box_score_thresh, box_nms_thresh, max_human, max_object,
@@ -350,10 +360,11 @@ def interaction_head_forward(sd, feat3, detections, image_shapes, pooled_fn, K, 
     pooled = pooled_fn(coords)
     gh = graph_head_forward(sd, feat3, image_shapes, pooled, coords, labels, scores, K, human_idx, o2v,
                             targets=targets, training=training, num_iter=num_iter, fg_iou_thresh=fg_iou_thresh,
-                            tables=tables, row_loop=row_loop, capture=capture)
+                            tables=tables, row_loop=row_loop, capture=capture, linear=linear)
     pf = torch.cat(gh["pair_features"])
-    logits_p = F.linear(pf, sd["box_pair_predictor.weight"], sd["box_pair_predictor.bias"])    # HEAD:410
-    logits_s = F.linear(pf, sd["box_pair_suppressor.weight"], sd["box_pair_suppressor.bias"])  # HEAD:411
+    top = Params(sd, prefix="", linear=linear)
+    logits_p = top.lin("box_pair_predictor", pf)                                                # HEAD:410
+    logits_s = top.lin("box_pair_suppressor", pf)                                               # HEAD:411
     results = postprocess(logits_p, logits_s, gh["prior"], gh["boxes_h"], gh["boxes_o"], gh["object_class"],
                           gh["labels"])
     extras = dict(logits_p=logits_p, logits_s=logits_s, pair_features=pf, preprocessed=det, graph=gh)

@@ -36,7 +36,7 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=False, ema=None):
+def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=False, ema=None, class_balanced=None):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_resident_")
     o2v = synth.hico_object_to_verb()
@@ -79,6 +79,14 @@ def main(n_images=16, per_shard=8, out_dir=None, seed=0, dtype="bf16", flip=Fals
     train_set = resident.ResidentFeatureSet(shards["train"], raw, targets, device=dev,
                                             flipped_shard_paths=shards["train_flipped"] if flip else None)
     head.train()
+    if class_balanced is not None:
+        # HOI classes re-weighted by their effective number of training samples: a [80, 117] table indexed by (object class
+        # of the pair, verb) on the HOI focal term; the fused step stays the fused step (another entry of the same kernel)
+        num_anno = torch.zeros(600, dtype=torch.int64)
+        for t in targets:
+            hoi = lut[t["object"], t["labels"]]
+            num_anno += torch.bincount(hoi[hoi >= 0], minlength=600)
+        head.cell_loss_weights = trainer.class_balanced_cell_weights(num_anno, lut, beta=class_balanced)
     train_set.check_alignment(head)                                     # (both variants when there are two)
     net = trainer.wrap_ddp(head, dev)
     opt = trainer.build_optimizer(net, lr=1e-4) if ema is None else \
@@ -122,5 +130,7 @@ if __name__ == "__main__":
     ap.add_argument("--flip", action="store_true", help="produce both variants and train with the reference's fixed coins")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
                     help="keep a moving average of the weights, evaluate under it and export it")
+    ap.add_argument("--class-balanced", type=float, default=None, metavar="BETA",
+                    help="weight the HOI loss cells by trainer.class_balanced_cell_weights(training counts, beta=BETA)")
     a = ap.parse_args()
-    main(a.images, a.per_shard, a.out, dtype=a.dtype, flip=a.flip, ema=a.ema)
+    main(a.images, a.per_shard, a.out, dtype=a.dtype, flip=a.flip, ema=a.ema, class_balanced=a.class_balanced)

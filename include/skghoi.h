@@ -715,6 +715,25 @@ int skg_hoi_loss_f32(const float* logits, int64_t ldl, int K, const skg_image_me
                      int64_t cells_total, const int64_t* index, const int64_t* pred, const float* scores,
                      const float* labels, float* cell_labels, float* unary, float* partial, float* dlogits,
                      void* stream);
+/* The same pass with a configurable loss shape.  skg_hoi_loss_f32 is the rule below at {0.5, 0.2, 0.5, 2.0} without a
+ * table, with the exponents as compile-time constants (the two entries may differ in the last bits there).
+ *   cell c = (pair p, verb v), x = scores[c], y = labels[p, v]:
+ *     term = w * |1 - y - alpha_cell| * (|y - x| + 1e-6)^gamma_cell * BCE(x, y),   w = cell_weights[object[p] * K + v]
+ *     (cell_weights [n_obj, K] fp32 on the device; NULL: w = 1 and object is not read), d term / d logit scaled by the same w;
+ *   pair p, x = sigmoid(logits[p, K]), y = unary[p]:  |1 - y - alpha_pair| * (|y - x| + 1e-6)^gamma_pair * BCE(x, y), unweighted.
+ * object [sumP] int64 = the class of each pair's object box (the packed results' `object`).  object[p] is range-checked
+ * before anything is read through it: a value outside [0, n_obj) gives that pair's cells w = 1.
+ * cell_labels, unary and the two counts of `partial` are those of skg_hoi_loss_f32 and do not depend on cfg or on the
+ * weights (a positive cell of weight 0 still counts), so the normalisers n_p, skg_count_positives_f32, skg_loss_finish_f32
+ * and the data-parallel all-reduce are unchanged.
+ * SKG_E_ARG: cfg NULL, a gamma < 0, a non-finite alpha or gamma, cell_weights != NULL with n_obj <= 0 or object NULL,
+ * and whatever skg_hoi_loss_f32 rejects.  n_active == 0: returns 0, nothing is touched.                                 */
+typedef struct { float alpha_cell, gamma_cell, alpha_pair, gamma_pair; } skg_focal_cfg;
+int skg_hoi_loss_cfg_f32(const float* logits, int64_t ldl, int K, const skg_image_meta* meta, int n_active,
+                         int64_t cells_total, const int64_t* index, const int64_t* pred, const float* scores,
+                         const float* labels, float* cell_labels, float* unary, float* partial, float* dlogits,
+                         const skg_focal_cfg* cfg, const int64_t* object, const float* cell_weights, int n_obj,
+                         void* stream);
 
 /* Data parallel: the three per-rank normaliser counts {#non-zero labels among the scored cells, #pairs with a label, the same
  * again} (HEAD:167-172, 194-199, 223-228 before their all_reduce) from the PREPARED batch -- associated labels [sumP, K],

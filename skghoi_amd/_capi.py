@@ -117,6 +117,11 @@ class Tuning(C.Structure):
     _fields_ = [(n, _i32) for n in ("small_mode", "small_tiles", "route_tiles", "khalves_blocks")]
 
 
+class FocalCfg(C.Structure):
+    """Mirror of skg_focal_cfg: the (alpha, gamma) pairs of the two focal terms (skg_hoi_loss_cfg_f32)."""
+    _fields_ = [(n, _f32) for n in ("alpha_cell", "gamma_cell", "alpha_pair", "gamma_pair")]
+
+
 class TrainPlan(C.Structure):
     """Mirror of skg_train_plan."""
     _fields_ = [(n, _i32) for n in ("NA", "Mg", "Mp", "Mh", "Mn", "A", "K", "Bf", "Cf", "x0_k", "bf16", "ld_logits")] + \
@@ -285,6 +290,8 @@ PROTOTYPES = {
     "skg_transh_sample_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
     "skg_hoi_loss_f32": (C.c_int, [_vp, _i64, C.c_int, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skg_hoi_loss_cfg_f32": (C.c_int, [_vp, _i64, C.c_int, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       C.POINTER(FocalCfg), _vp, _vp, C.c_int, _vp]),
     "skg_count_positives_f32": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _f32, _vp, _vp]),
     "skg_loss_finish_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "skg_scale_dlogits_f32": (C.c_int, [_vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),

@@ -11,6 +11,7 @@ skghoi_amd/engine.py; there is no eager/CPU fallback -- CPU tensors or a missing
 
 Reference file:line for every class is given in its docstring (HEAD = the reference head file).
 """
+import math
 from collections import OrderedDict
 from typing import List, Optional, Tuple
 
@@ -316,6 +317,21 @@ class _Ready:
 _INFERENCE_PRECISIONS = (None, "fp32", "fp16x2", "bf16")
 _INFERENCE_ACTIVATIONS = (None, "fp32", "bf16")
 _TRANSH_RNGS = ("host", "device")
+_HOI_FOCAL = (0.5, 0.2)                    # (alpha, gamma) of the scored cells' focal term (HEAD:175) ...
+_INTERACTIVENESS_FOCAL = (0.5, 2.0)        # ... and of the pair weights' (HEAD:203): the reference's literals
+
+
+def _focal_pair(name, value):
+    """(alpha, gamma) as two Python floats; ValueError naming the argument otherwise."""
+    try:
+        alpha, gamma = (float(v) for v in value)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a pair (alpha, gamma) of numbers, got %r" % (name, value)) from None
+    if not (math.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+        raise ValueError("%s: alpha must lie in [0, 1], got %r" % (name, alpha))
+    if not (math.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError("%s: gamma must be finite and >= 0, got %r" % (name, gamma))
+    return alpha, gamma
 
 
 class InteractionHead(Module):
@@ -360,6 +376,23 @@ class InteractionHead(Module):
           whatever its position, batch, rank or route, and the global generator is never touched.  Two images with the
           same selection share their tables.  Scores of one image in different batch compositions can still differ in the
           last bits: the products' summation order depends on the batch's row count.
+      hoi_focal = (0.5, 0.2), interactiveness_focal = (0.5, 2.0), cell_loss_weights = None -- keyword-only; the shape of the
+        two focal terms of the training loss (HEAD:153-205; ops.py:159-211 takes alpha and gamma as arguments); plain
+        attributes behind validating setters (ValueError naming the attribute), not part of state_dict, kept by
+        copy.deepcopy and pickle:
+        hoi_focal / interactiveness_focal: (alpha, gamma) of the scored cells' term / of the pair weights' term; alpha in
+          [0, 1], gamma >= 0.
+        cell_loss_weights: None, or a float tensor [len(object_class_to_target_class), num_classes] -- the term of the cell
+          (pair p, verb v) and its gradient are multiplied by table[object class of p's object box, v] -- or
+          [num_classes] (per verb, the same for every object class); finite and >= 0.  An object class outside the
+          table weighs 1.  The normalisers n_p stay the unweighted counts of positives.  trainer.class_balanced_cell_weights
+          builds the class-balanced table from training counts.
+        At the defaults the reference's literals run, bit for bit and launch for launch.  Every training route honours
+        them: the fused step in both gradient modes, the autograd route, the two loss methods called on their own.
+        The configuration is read when the step's loss is issued, NOT when a batch is prepared: a batch prepared by the
+        look-ahead (prefetch_train) under one configuration and consumed under another uses the one current at the step.
+        The table lives on the step's device as a copy made at the first step after an assignment, not per step.
+        Validation losses, the TransH margin term and the weights of the three-loss sum are not configurable here.
       reference_quirks: bool = True -- reproduce (a) the node-offset bug on skipped images and (b) the
         eval-mode label-list zip with skipped images in a batch > 1 (HEAD:298-310: truncated results / IndexError).
         With False every image gets its own (possibly empty) result.
@@ -370,7 +403,9 @@ class InteractionHead(Module):
                  box_score_thresh: float = 0.2, max_human: int = 15, max_object: int = 15,
                  distributed: bool = False, reference_quirks: bool = True, precision: str = "fp32",
                  inference_precision: Optional[str] = None, inference_activations: Optional[str] = None, *,
-                 transh_rng: str = "host", transh_seed: int = 0) -> None:
+                 transh_rng: str = "host", transh_seed: int = 0, hoi_focal: Tuple[float, float] = _HOI_FOCAL,
+                 interactiveness_focal: Tuple[float, float] = _INTERACTIVENESS_FOCAL,
+                 cell_loss_weights: Optional[Tensor] = None) -> None:
         super().__init__()
         self.box_roi_pool = box_roi_pool
         self.box_pair_head = box_pair_head
@@ -398,14 +433,17 @@ class InteractionHead(Module):
         self.transh_rng = transh_rng
         self.transh_seed = int(transh_seed)
         self.transh_salt = 0
-        self.fused_training = True      # False: training through autograd over per-layer Functions (skghoi_amd/train_graph.py)
+        self.hoi_focal = hoi_focal
+        self.interactiveness_focal = interactiveness_focal
+        self.cell_loss_weights = cell_loss_weights
+        self.fused_training = True     # False: training through autograd over per-layer Functions (skghoi_amd/train_graph.py)
         self.grad_mode = "autograd"     # "direct": the fused step writes p.grad itself (skghoi_amd/train_fused.py, StepFn)
         self._engine = None
 
     # run-time caches (engine with its streams / captured plans, parameter arena bookkeeping, prefetch state): never part of
     # a copy or a pickle of the module -- they are rebuilt on first use
     _RUNTIME = ("_engine", "_stacked", "_pf_stream", "_prefetched", "_prefetched2", "_last_train", "_last_train_plan",
-                "_train_params")
+                "_train_params", "_cell_weights_dev")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -413,6 +451,78 @@ class InteractionHead(Module):
             if k in state:
                 state[k] = None
         return state
+
+    # ------------------------------------------------------------------------------------------ loss configuration
+    # Plain attributes behind validating setters (nn.Module.__setattr__ hands anything that is no parameter, module or
+    # buffer to object.__setattr__, which honours a property): not in state_dict, kept by copy.deepcopy and pickle.
+    @property
+    def hoi_focal(self) -> Tuple[float, float]:
+        return self.__dict__.get("_hoi_focal", _HOI_FOCAL)
+
+    @hoi_focal.setter
+    def hoi_focal(self, value):
+        self.__dict__["_hoi_focal"] = _focal_pair("hoi_focal", value)
+
+    @property
+    def interactiveness_focal(self) -> Tuple[float, float]:
+        return self.__dict__.get("_interactiveness_focal", _INTERACTIVENESS_FOCAL)
+
+    @interactiveness_focal.setter
+    def interactiveness_focal(self, value):
+        self.__dict__["_interactiveness_focal"] = _focal_pair("interactiveness_focal", value)
+
+    @property
+    def cell_loss_weights(self) -> Optional[Tensor]:
+        """None, or the table as it is used: [object classes, num_classes] fp32 on the CPU."""
+        return self.__dict__.get("_cell_loss_weights")
+
+    @cell_loss_weights.setter
+    def cell_loss_weights(self, value):
+        if value is not None:
+            if not torch.is_tensor(value) or not value.is_floating_point():
+                raise ValueError("cell_loss_weights must be None or a float tensor, got %r" % type(value).__name__)
+            K = int(self.num_classes)
+            o2t = getattr(self.box_pair_head, "object_class_to_target_class", None)
+            n_obj = len(o2t) if o2t is not None else None
+            shape = tuple(value.shape)
+            if not (shape == (K,) and n_obj is not None) and not (len(shape) == 2 and shape[1] == K and shape[0] > 0 and
+                                                                  n_obj in (None, shape[0])):
+                raise ValueError("cell_loss_weights must have shape [%s, %d] or [%d], got %s"
+                                 % ("object classes" if n_obj is None else n_obj, K, K, list(shape)))
+            value = value.detach().to(device="cpu", dtype=torch.float32)
+            if not bool(torch.isfinite(value).all()) or bool((value < 0).any()):
+                raise ValueError("cell_loss_weights must be finite and >= 0")
+            value = (value[None, :].expand(n_obj, K) if value.dim() == 1 else value).contiguous().clone()
+        self.__dict__["_cell_loss_weights"] = value
+        self.__dict__["_cell_weights_dev"] = None          # the device copy is refreshed at the next step
+
+    def loss_config(self, dev=None):
+        """(hoi_focal, interactiveness_focal, table) as the step's loss sees them NOW, or None when all three are the
+        reference's defaults (then nothing but the reference's own code and kernel runs).  table: None, or the
+        [object classes, num_classes] fp32 table on `dev` -- uploaded when first asked for after an assignment, not per
+        step."""
+        hoi, inter, w = self.hoi_focal, self.interactiveness_focal, self.cell_loss_weights
+        if hoi == _HOI_FOCAL and inter == _INTERACTIVENESS_FOCAL and w is None:
+            return None
+        if w is not None and dev is not None:
+            dev = torch.device(dev)
+            c = self.__dict__.get("_cell_weights_dev")
+            if c is None or c.device != dev:
+                c = self.__dict__["_cell_weights_dev"] = w.to(dev)
+            w = c
+        return hoi, inter, w
+
+    def _cell_weights_of(self, results, table):
+        """table[object[index], prediction] of every scored cell of `results`, concatenated; an object class outside
+        the table weighs 1 (the kernel's rule, include/skghoi.h)."""
+        n_obj = table.shape[0]
+        out = []
+        for r in results:
+            o = r["object"][r["index"]]
+            ok = (o >= 0) & (o < n_obj)
+            w = table[o.clamp(0, n_obj - 1), r["prediction"]]
+            out.append(torch.where(ok, w, torch.ones((), dtype=w.dtype, device=w.device)))
+        return torch.cat(out)
 
     def engine(self) -> HeadEngine:
         e = self._engine
@@ -806,7 +916,15 @@ class InteractionHead(Module):
         labels = torch.cat([r["labels"] for r in results]); scores = torch.cat([r["scores"] for r in results])
         if n_p is None:
             n_p = self._n_p(labels)
-        return binary_focal_loss(scores, labels, reduction="sum", gamma=0.2) / n_p
+        cfg = self.loss_config(scores.device)
+        if cfg is None:
+            return binary_focal_loss(scores, labels, reduction="sum", gamma=0.2) / n_p
+        # configured (see the class docstring): the weights scale the cells' terms, never the normaliser n_p
+        (alpha, gamma), _, table = cfg
+        terms = binary_focal_loss(scores, labels, alpha=alpha, gamma=gamma, reduction="none")
+        if table is not None:
+            terms = terms * self._cell_weights_of(results, table)
+        return terms.sum() / n_p
 
     def compute_interactiveness_loss(self, results: List[dict], n_p=None) -> Tensor:
         """HEAD:180-205."""
@@ -814,7 +932,8 @@ class InteractionHead(Module):
         weights = torch.cat([r["weights"] for r in results]); labels = torch.cat([r["unary_labels"] for r in results])
         if n_p is None:
             n_p = self._n_p(labels)
-        return binary_focal_loss(weights, labels, reduction="sum", gamma=2.0) / n_p
+        alpha, gamma = self.interactiveness_focal
+        return binary_focal_loss(weights, labels, reduction="sum", alpha=alpha, gamma=gamma) / n_p
 
     def compute_transH_loss(self, positive_scores, negative_scores, head, relation, relation_norm, tail,
                             results: List[dict], n_p=None) -> Tensor:

@@ -7,6 +7,7 @@
 // forward and one or two backward; reductions over graph neighbourhoods are done per destination row (no atomics, fixed
 // order, deterministic), exactly like the forward aggregation in skg_graph.hip.  All row widths are the head's 1024.
 #include "skg_common.h"
+#include <cfloat>
 
 #define TR_COLS 1024
 
@@ -551,8 +552,12 @@ extern "C" int skg_entity_rows_bwd_f32(const float* dX, int64_t ldx, const int32
 // of pair losses, #positive cells, #positive pairs}: the caller adds them up; the two counts are the loss normalisers
 // n_p (HEAD:162-165, 190-192).
 // dlogits [sumP, ldl] must be zero-filled; columns < K receive d(sum cell loss)/dlp, column K d(sum pair loss)/dls.
-__device__ __forceinline__ float skg_focal(float x, float y, float gamma, float& dldx) {
-    const float alpha = 0.5f, eps = 1e-6f;
+// The configured entry (skg_hoi_loss_cfg_f32) runs the same body with run-time (alpha, gamma) pairs and a per-cell weight
+// w = cell_weights[object[p], v] on the cell term and its gradient (1 when there is no table or object[p] is outside
+// [0, n_obj)); the counts never see the weights.  The default entry keeps its literal alpha and exponents: with them the
+// compiler folds the powers its own way (powf(u, 2.0f) may become u * u), which a run-time gamma cannot reproduce bit for bit.
+__device__ __forceinline__ float skg_focal(float x, float y, float alpha, float gamma, float& dldx) {
+    const float eps = 1e-6f;
     const float c = fabsf(1.f - y - alpha);
     const float u = fabsf(y - x) + eps;
     const float lx = fmaxf(logf(x), -100.f), l1x = fmaxf(logf(1.f - x), -100.f);
@@ -564,11 +569,13 @@ __device__ __forceinline__ float skg_focal(float x, float y, float gamma, float&
     return c * pw * bce;
 }
 
-__global__ __launch_bounds__(256) void skg_hoi_loss_kernel(
+template <bool CFG>
+__device__ __forceinline__ void skg_hoi_loss_body(
     const float* __restrict__ logits, int64_t ldl, int K, const skg_image_meta* __restrict__ meta, int n_active,
     int64_t cells_total, const int64_t* __restrict__ index, const int64_t* __restrict__ pred,
     const float* __restrict__ scores, const float* __restrict__ labels, float* __restrict__ cell_labels,
-    float* __restrict__ unary, float* __restrict__ partial, float* __restrict__ dlogits) {
+    float* __restrict__ unary, float* __restrict__ partial, float* __restrict__ dlogits, const skg_focal_cfg cfg,
+    const int64_t* __restrict__ object, const float* __restrict__ cell_weights, int n_obj) {
     __shared__ float sred[4];
     const int a = blockIdx.x;
     const skg_image_meta mt = meta[a];
@@ -585,7 +592,17 @@ __global__ __launch_bounds__(256) void skg_hoi_loss_kernel(
         cell_labels[c] = y;
         if (y != 0.f) n1 += 1.f;
         float dldx;
-        s1 += skg_focal(x, y, 0.2f, dldx);
+        if (CFG) {
+            float wt = 1.f;
+            if (cell_weights) {
+                const int64_t o = object[p];                 // range-checked before anything is read through it
+                if (o >= 0 && o < (int64_t)n_obj) wt = cell_weights[o * K + v];
+            }
+            s1 += wt * skg_focal(x, y, cfg.alpha_cell, cfg.gamma_cell, dldx);
+            dldx *= wt;
+        } else {
+            s1 += skg_focal(x, y, 0.5f, 0.2f, dldx);
+        }
         const float sg = 1.f / (1.f + expf(-logits[p * ldl + v]));
         dlogits[p * ldl + v] = dldx * x * (1.f - sg);
     }
@@ -603,7 +620,7 @@ __global__ __launch_bounds__(256) void skg_hoi_loss_kernel(
         if (y != 0.f) n2 += 1.f;
         const float w = 1.f / (1.f + expf(-logits[p * ldl + K]));
         float dldw;
-        s2 += skg_focal(w, y, 2.0f, dldw);
+        s2 += CFG ? skg_focal(w, y, cfg.alpha_pair, cfg.gamma_pair, dldw) : skg_focal(w, y, 0.5f, 2.0f, dldw);
         dlogits[p * ldl + K] = dldw * w * (1.f - w);
     }
     s1 = skg_block_sum256(s1, sred);
@@ -616,17 +633,67 @@ __global__ __launch_bounds__(256) void skg_hoi_loss_kernel(
     }
 }
 
-extern "C" int skg_hoi_loss_f32(const float* logits, int64_t ldl, int K, const skg_image_meta* meta, int n_active,
-                                int64_t cells_total, const int64_t* index, const int64_t* pred, const float* scores,
-                                const float* labels, float* cell_labels, float* unary, float* partial, float* dlogits,
-                                void* stream) {
+__global__ __launch_bounds__(256) void skg_hoi_loss_kernel(
+    const float* __restrict__ logits, int64_t ldl, int K, const skg_image_meta* __restrict__ meta, int n_active,
+    int64_t cells_total, const int64_t* __restrict__ index, const int64_t* __restrict__ pred,
+    const float* __restrict__ scores, const float* __restrict__ labels, float* __restrict__ cell_labels,
+    float* __restrict__ unary, float* __restrict__ partial, float* __restrict__ dlogits) {
+    skg_hoi_loss_body<false>(logits, ldl, K, meta, n_active, cells_total, index, pred, scores, labels, cell_labels, unary,
+                             partial, dlogits, skg_focal_cfg{}, nullptr, nullptr, 0);
+}
+
+__global__ __launch_bounds__(256) void skg_hoi_loss_cfg_kernel(
+    const float* __restrict__ logits, int64_t ldl, int K, const skg_image_meta* __restrict__ meta, int n_active,
+    int64_t cells_total, const int64_t* __restrict__ index, const int64_t* __restrict__ pred,
+    const float* __restrict__ scores, const float* __restrict__ labels, float* __restrict__ cell_labels,
+    float* __restrict__ unary, float* __restrict__ partial, float* __restrict__ dlogits, const skg_focal_cfg cfg,
+    const int64_t* __restrict__ object, const float* __restrict__ cell_weights, int n_obj) {
+    skg_hoi_loss_body<true>(logits, ldl, K, meta, n_active, cells_total, index, pred, scores, labels, cell_labels, unary,
+                            partial, dlogits, cfg, object, cell_weights, n_obj);
+}
+
+// cfg: NULL = the default entry; else the configured one with (object, cell_weights, n_obj)
+static int skg_hoi_loss_launch(const float* logits, int64_t ldl, int K, const skg_image_meta* meta, int n_active,
+                               int64_t cells_total, const int64_t* index, const int64_t* pred, const float* scores,
+                               const float* labels, float* cell_labels, float* unary, float* partial, float* dlogits,
+                               const skg_focal_cfg* cfg, const int64_t* object, const float* cell_weights, int n_obj,
+                               void* stream) {
     if (n_active < 0 || K <= 0 || ldl <= K || cells_total < 0) return SKG_E_ARG;
     if (n_active == 0) return 0;
     if (!logits || !meta || !index || !pred || !scores || !labels || !cell_labels || !unary || !partial || !dlogits)
         return SKG_E_ARG;
-    hipLaunchKernelGGL(skg_hoi_loss_kernel, dim3(n_active, SKG_LOSS_CHUNKS), dim3(256), 0, (hipStream_t)stream, logits, ldl, K, meta, n_active,
-                       cells_total, index, pred, scores, labels, cell_labels, unary, partial, dlogits);
+    const dim3 grid(n_active, SKG_LOSS_CHUNKS);
+    if (cfg)
+        hipLaunchKernelGGL(skg_hoi_loss_cfg_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, ldl, K, meta, n_active,
+                           cells_total, index, pred, scores, labels, cell_labels, unary, partial, dlogits, *cfg, object,
+                           cell_weights, n_obj);
+    else
+        hipLaunchKernelGGL(skg_hoi_loss_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, ldl, K, meta, n_active,
+                           cells_total, index, pred, scores, labels, cell_labels, unary, partial, dlogits);
     return skg_launch_status();
+}
+
+extern "C" int skg_hoi_loss_f32(const float* logits, int64_t ldl, int K, const skg_image_meta* meta, int n_active,
+                                int64_t cells_total, const int64_t* index, const int64_t* pred, const float* scores,
+                                const float* labels, float* cell_labels, float* unary, float* partial, float* dlogits,
+                                void* stream) {
+    return skg_hoi_loss_launch(logits, ldl, K, meta, n_active, cells_total, index, pred, scores, labels, cell_labels, unary,
+                               partial, dlogits, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int skg_hoi_loss_cfg_f32(const float* logits, int64_t ldl, int K, const skg_image_meta* meta, int n_active,
+                                    int64_t cells_total, const int64_t* index, const int64_t* pred, const float* scores,
+                                    const float* labels, float* cell_labels, float* unary, float* partial, float* dlogits,
+                                    const skg_focal_cfg* cfg, const int64_t* object, const float* cell_weights, int n_obj,
+                                    void* stream) {
+    if (!cfg) return SKG_E_ARG;
+    const float four[4] = {cfg->alpha_cell, cfg->gamma_cell, cfg->alpha_pair, cfg->gamma_pair};
+    for (float f : four)
+        if (!(fabsf(f) <= FLT_MAX)) return SKG_E_ARG;                    // NaN or infinite
+    if (cfg->gamma_cell < 0.f || cfg->gamma_pair < 0.f) return SKG_E_ARG;
+    if (cell_weights && (n_obj <= 0 || !object)) return SKG_E_ARG;
+    return skg_hoi_loss_launch(logits, ldl, K, meta, n_active, cells_total, index, pred, scores, labels, cell_labels, unary,
+                               partial, dlogits, cfg, object, cell_weights, n_obj, stream);
 }
 
 // The three per-rank normaliser counts of the loss terms from what the PREPARATION of a batch knows (HEAD:162-172, 190-199,

@@ -482,7 +482,9 @@ class TrainJob:
     # ------------------------------------------------------------------------------------------------ losses
     def loss_forward(self, logits):
         """Both focal terms summed (HEAD:162-165, 190-192 before the division by n_p) + d/dlogits, from the packed result
-        arrays `self.result` (skg_postprocess_f32 on these logits) and the label matrix `self.labels`."""
+        arrays `self.result` (skg_postprocess_f32 on these logits) and the label matrix `self.labels`.  The head's loss
+        configuration (hoi_focal, interactiveness_focal, cell_loss_weights) is read HERE, when the kernel is issued: at
+        the defaults the reference's kernel runs, otherwise the configured one (skg_hoi_loss_cfg_f32)."""
         lib = _capi.lib()
         lay, dev, K = self.lay, self.dev, self.K
         r = self.result
@@ -492,10 +494,22 @@ class TrainJob:
         self.cell_labels = torch.empty(max(Lt, 1), **f32)
         self.unary = torch.empty(max(Mp, 1), **f32)
         partial = torch.empty(lay.n_active * _capi.LOSS_CHUNKS, 4, **f32)
-        _check(lib.skg_hoi_loss_f32(logits.data_ptr(), logits.stride(0), K, self.meta.data_ptr(), lay.n_active, Lt,
-                                    r["index"].data_ptr(), r["prediction"].data_ptr(), r["scores"].data_ptr(),
-                                    self.labels.data_ptr(), self.cell_labels.data_ptr(), self.unary.data_ptr(),
-                                    partial.data_ptr(), self.dlogits.data_ptr(), _stream()), "skg_hoi_loss_f32")
+        cfg = self.head.loss_config(dev)
+        if cfg is None:
+            _check(lib.skg_hoi_loss_f32(logits.data_ptr(), logits.stride(0), K, self.meta.data_ptr(), lay.n_active, Lt,
+                                        r["index"].data_ptr(), r["prediction"].data_ptr(), r["scores"].data_ptr(),
+                                        self.labels.data_ptr(), self.cell_labels.data_ptr(), self.unary.data_ptr(),
+                                        partial.data_ptr(), self.dlogits.data_ptr(), _stream()), "skg_hoi_loss_f32")
+        else:
+            (a_cell, g_cell), (a_pair, g_pair), table = cfg
+            if table is not None and (table.dim() != 2 or table.shape[1] != K or not table.is_contiguous()):
+                raise _capi.SkgError("cell_loss_weights: a [object classes, %d] table, got %s" % (K, list(table.shape)))
+            _check(lib.skg_hoi_loss_cfg_f32(
+                logits.data_ptr(), logits.stride(0), K, self.meta.data_ptr(), lay.n_active, Lt, r["index"].data_ptr(),
+                r["prediction"].data_ptr(), r["scores"].data_ptr(), self.labels.data_ptr(), self.cell_labels.data_ptr(),
+                self.unary.data_ptr(), partial.data_ptr(), self.dlogits.data_ptr(),
+                C.byref(_capi.FocalCfg(a_cell, g_cell, a_pair, g_pair)), r["object"].data_ptr(), _ptr(table),
+                table.shape[0] if table is not None else 0, _stream()), "skg_hoi_loss_cfg_f32")
         self.partial = partial                            # rows of {cell loss, pair loss, #positive cells, #positive pairs}
         return partial
 

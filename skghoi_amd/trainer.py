@@ -1411,6 +1411,37 @@ def seed_everything(seed: int = 42) -> None:
     torch.manual_seed(seed)
 
 
+def class_balanced_cell_weights(num_anno, lut=None, beta: float = 0.999) -> torch.Tensor:
+    """The table for InteractionHead.cell_loss_weights that re-weights the HOI classes by their effective number of
+    training samples (Cui et al., "Class-Balanced Loss Based on Effective Number of Samples", CVPR 2019):
+        E_c = (1 - beta^max(n_c, 1)) / (1 - beta),   w_c = 1 / E_c, scaled so that the classes present in `lut` average 1;
+        table[o, v] = w[lut[o][v]] where lut[o][v] >= 0, and 1 elsewhere.
+    num_anno [classes]: training annotations per HOI class (a count of 0 is treated as 1).  lut [object classes, verbs]:
+    HOI class of (object, verb) or -1; default: HICO-DET's (evaluate.hico_object_n_verb_to_interaction).  beta in [0, 1):
+    0 gives all ones, values near 1 approach inverse frequency.  Computed in float64 and rounded once; returns
+    [object classes, verbs] fp32 on the CPU."""
+    beta = float(beta)
+    if not 0.0 <= beta < 1.0:
+        raise ValueError("beta must lie in [0, 1), got %r" % beta)
+    if lut is None:
+        from .evaluate import hico_object_n_verb_to_interaction
+        lut = hico_object_n_verb_to_interaction()
+    lut = torch.as_tensor(lut, dtype=torch.int64).cpu()
+    n = torch.as_tensor(num_anno).detach().cpu().to(torch.float64).reshape(-1)
+    if lut.dim() != 2:
+        raise ValueError("lut must be [object classes, verbs], got %s" % list(lut.shape))
+    valid = lut >= 0
+    present = torch.unique(lut[valid])
+    if present.numel() == 0 or int(present.max()) >= n.numel():
+        raise ValueError("lut names classes 0..%d but num_anno has %d entries" % (int(lut.max()), n.numel()))
+    eff = (1.0 - torch.pow(torch.tensor(beta, dtype=torch.float64), n.clamp(min=1.0))) / (1.0 - beta)
+    w = 1.0 / eff
+    w = w / w[present].mean()
+    table = torch.ones(lut.shape, dtype=torch.float64)
+    table[valid] = w[lut[valid]]
+    return table.to(torch.float32)
+
+
 def filter_detections(detection: dict, human_idx: int, box_score_thresh_h: float = 0.2,
                       box_score_thresh_o: float = 0.2) -> dict:
     """DataFactory.filter_detections (utils.py:97-119): humans above their threshold first, then the other classes above

@@ -6,6 +6,8 @@
   against synthetic ground truth, in HICO-DET's Default and Known Object settings (full / rare / non-rare; --errors: the
   error breakdown of the Default setting, cells by category and ground-truth pairs by status; --pair-nms THRESH: the same
   numbers again behind the pair NMS over the scored triplets, evaluate.pair_nms -- opt-in, not the reference's;
+  --score-thresh T / --topk K: that second evaluation behind a score threshold and the K best cells of every image too,
+  the chain threshold -> pair NMS -> top-k of evaluate.select_results -- opt-in, this project's own rule;
   --bootstrap N: confidence intervals of every mean from N image-level bootstrap replicates, and with --pair-nms the paired
   comparison of the filtered run against the plain run; --transh-rng device: the per-image TransH tables generated on the
   device from each image's detections instead of drawn from the global CPU generator -- opt-in, this project's own rule)
@@ -33,7 +35,8 @@ from skghoi_amd.roi_pool import MultiScaleRoIAlign
 runtime.configure()           # process-level HIP runtime settings, before the first GPU use
 
 
-def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None, bootstrap=None, transh_rng="host"):
+def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None, bootstrap=None, transh_rng="host", topk=None,
+         score_thresh=None):
     dev = torch.device("cuda", 0)
     out_dir = out_dir or tempfile.mkdtemp(prefix="skg_cache_")
     o2v = synth.hico_object_to_verb()
@@ -93,21 +96,25 @@ def main(n_images=16, batch=8, out_dir=None, seed=0, errors=False, pair_nms=None
         print(evaluate.format_bootstrap(summ))
     if errors:                                                   # where the Default mAP is lost: cells by category, pairs by status
         print(evaluate.format_error_table(summ))
-    if pair_nms is not None:                                     # the remedy for the `duplicate` row: the same evaluation, filtered
-        filtered = evaluate.pair_nms(outputs, pair_nms)
+    if pair_nms is not None or topk is not None or score_thresh is not None:
+        # the remedy for the `duplicate` row and a bounded result list: the same evaluation, filtered -- score threshold ->
+        # pair NMS -> top-k per image, each stage off where its flag is absent, one host synchronisation for the chain
+        filtered = evaluate.select_results(outputs, nms_thresh=pair_nms, score_thresh=score_thresh, topk=topk)
+        what = ", ".join("%s=%g" % kv for kv in (("score_thresh", score_thresh), ("pair_nms thresh", pair_nms), ("topk", topk))
+                         if kv[1] is not None)
         ev_f = evaluate.HOIEvaluator(num_gt, lut, num_anno_train=num_anno_train, known_object=True, errors=errors,
                                      bootstrap=bootstrap)
         for out, t in zip(filtered, targets):
             ev_f.add(out, t)
         summ_f = ev_f.summary()
-        print("behind pair_nms(thresh=%g): %d of %d cells" % (pair_nms, sum(len(o["scores"]) for o in filtered),
-                                                             sum(len(o["scores"]) for o in outputs)))
+        print("behind select_results(%s): %d of %d cells" % (what, sum(len(o["scores"]) for o in filtered),
+                                                            sum(len(o["scores"]) for o in outputs)))
         for name, s in (("Default", summ_f), ("Known Object", summ_f["known_object"])):
             print("%-12s full %.4f  rare %.4f  non-rare %.4f" % (name, s["full"], s["rare"], s["non_rare"]))
         if bootstrap:                                            # the same images in the same order: the replicates are paired
             for key in ("full", "rare", "non_rare"):
                 c = evaluate.bootstrap_compare(summ_f, summ, key)
-                print("pair_nms - plain, %-8s delta %+.4f  replicates %+.4f [%+.4f, %+.4f]  P(filtered better) %.3f" % (
+                print("filtered - plain, %-8s delta %+.4f  replicates %+.4f [%+.4f, %+.4f]  P(filtered better) %.3f" % (
                     key, c["delta"], c["mean"], c["lo"], c["hi"], c["p_a_better"]))
         if errors:
             print(evaluate.format_error_table(summ_f))
@@ -135,10 +142,16 @@ if __name__ == "__main__":
     ap.add_argument("--errors", action="store_true", help="print the error breakdown of the Default setting")
     ap.add_argument("--pair-nms", type=float, default=None, metavar="THRESH",
                     help="evaluate a second time behind evaluate.pair_nms(outputs, THRESH); with --errors both tables are printed")
+    ap.add_argument("--topk", type=int, default=None, metavar="K",
+                    help="keep the K best cells of every image in that second evaluation (evaluate.select_results; behind the "
+                         "pair NMS when --pair-nms is given too)")
+    ap.add_argument("--score-thresh", type=float, default=None, metavar="T",
+                    help="drop the cells scored below T in that second evaluation (evaluate.select_results)")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="N image-level bootstrap replicates: intervals of every mean; with --pair-nms the paired comparison")
     ap.add_argument("--transh-rng", choices=("host", "device"), default="host",
                     help="device: TransH tables keyed by each image's detections (opt-in, not the reference's stream): the "
                          "numbers no longer depend on --batch or on the order of the images, up to the last bits of the products")
     a = ap.parse_args()
-    main(a.images, a.batch, a.out, errors=a.errors, pair_nms=a.pair_nms, bootstrap=a.bootstrap, transh_rng=a.transh_rng)
+    main(a.images, a.batch, a.out, errors=a.errors, pair_nms=a.pair_nms, bootstrap=a.bootstrap, transh_rng=a.transh_rng,
+         topk=a.topk, score_thresh=a.score_thresh)

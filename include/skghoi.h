@@ -971,8 +971,8 @@ int skg_eval_pair_cover_u8(const float* det_boxes, const int64_t* det_labels, co
 /* Pair NMS: suppression of duplicate (human, object, class) triplets among the scored cells of an image -- what the error
  * breakdown's `duplicate` category asks for.  NOT part of the reference, which ranks every cell: opt-in post-processing,
  * restated from the published idea (PPDM's PNMS; the triplet_nms_filter of QPIC and CDN) -- parity unpinned.  CDN's fractional
- * exponents (ih^alpha * io^beta) are left out: powf is not bit-reproducible between host and device.  Top-k per image, merging
- * over ranks and a mask input of the association are not part of it either.
+ * exponents (ih^alpha * io^beta) are left out: powf is not bit-reproducible between host and device.  Top-k per image is
+ * skg_hoi_topk_u8 below; merging over ranks and a mask input of the association are not part of either.
  *
  * For a batch in the layout of skg_eval_associate_f32 (boxes_h / boxes_o [sumP, 4], object [sumP], index / pred / scores [L],
  * index local to the image, cell_off [n_images + 1]; pair_off with n_images + 1 entries).  No lut: V-COCO results alike.
@@ -1008,6 +1008,35 @@ int skg_eval_pair_cover_u8(const float* det_boxes, const int64_t* det_labels, co
 int skg_hoi_pair_nms_u8(const float* boxes_h, const float* boxes_o, const int64_t* object, const int32_t* pair_off,
                         const int64_t* index, const int64_t* pred, const float* scores, const int32_t* cell_off, int n_images,
                         const int64_t* order, int measure, float thresh, uint8_t* keep, int32_t* status, void* stream);
+
+/* Top-k: score threshold and top-k per image over the scored cells -- the last stage of a detector's post-processing
+ * (torchvision's postprocess_detections: score threshold, NMS, detections_per_img; the one-stage HOI literature reports mAP at
+ * 100 triplets per image).  NOT part of the reference, which ranks every cell: opt-in post-processing, this project's own
+ * rule -- parity unpinned.  Top-k per class or per pair, merging over ranks and a mask input of the association are not part
+ * of it.
+ *
+ * scores [L] float32 in arrival order (the order of `scores` in the head's result dicts), cell_off [n_images + 1] int32 as in
+ * skg_eval_associate_f32; no grouping and no lut: V-COCO results alike.  Cells of different images never interact.
+ * Per image:
+ *   candidate a cell c is a candidate iff (a) keep_in is NULL or keep_in[c] != 0, (b) scores[c] is not NaN and (c)
+ *             scores[c] >= score_thresh, a float32 comparison (-0 >= +0 is true).  score_thresh = -INFINITY is "no threshold":
+ *             every score that is a number passes, -INFINITY too.
+ *   rank      the candidates go score descending, compared as floats with -0 equal to +0 (the rank is taken on
+ *             scores[c] + 0.f); equal scores in arrival order (the lower cell index first).
+ *   keep      keep[c] = 1 iff c is a candidate and its rank, from 0, is < k; else 0.  k = INT32_MAX is "no cap".
+ *   kept      kept[a] = the number of ones in image a.
+ * keep [L] uint8 and kept [n_images] int32: every byte of keep[0 .. cell_off[n_images]) and every kept[a] is written exactly
+ * once.  keep_in [L] uint8 or NULL, for instance the flags of skg_hoi_pair_nms_u8: the chain score threshold -> pair NMS ->
+ * top-k needs no mask input of the NMS, because inside a group a cell below the threshold ranks behind every cell at or above
+ * it and only earlier kept cells suppress -- the NMS over all cells followed by the threshold keeps exactly the cells that the
+ * threshold followed by the NMS keeps.  keep_in and keep may not overlap.
+ * Any number of cells per image (one workgroup per image, a radix select over the image's scores; no caps, no status).  The
+ * output is the same bytes on every run.
+ * Errors, before any device call: SKG_E_ARG for n_images < 0, k <= 0 or a NaN score_thresh; n_images == 0 returns 0 and
+ * launches nothing; SKG_E_ARG for a null scores / cell_off / keep / kept; SKG_E_ALIGN for scores / cell_off / kept not 4-byte
+ * aligned.                                                                                                               */
+int skg_hoi_topk_u8(const float* scores, const int32_t* cell_off, int n_images, int k, float score_thresh,
+                    const uint8_t* keep_in /* may be NULL */, uint8_t* keep, int32_t* kept /* [n_images] */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Order-independent 64-bit checksum of the live parameters (bit patterns weighted by position) over a table of

@@ -286,6 +286,7 @@ PROTOTYPES = {
                                          _vp, _vp, _vp, _vp, _vp]),
     "skg_eval_pair_cover_u8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _f32, _vp, _vp]),
     "skg_hoi_pair_nms_u8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _f32, _vp, _vp, _vp]),
+    "skg_hoi_topk_u8": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp]),
     "skg_transh_sample_ws_ints": (C.c_int64, [C.c_int, C.c_int]),
     "skg_transh_sample_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),

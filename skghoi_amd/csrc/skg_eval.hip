@@ -48,6 +48,12 @@
 //                              into an LDS list, then one wave per group walks the candidates in sequence while its lanes
 //                              clear the alive bits of the later cells they own, in registers.
 //
+// Score threshold and top-k per image over the same cells (opt-in, this project's own rule, stated in include/skghoi.h):
+//
+//   skg_hoi_topk_u8          : one workgroup per image, any number of cells: a count of the candidates, a radix select of the
+//                              k-th largest score key (four 8-bit passes over an LDS histogram), and a sweep in arrival order
+//                              that keeps the keys above it and the first of the equal ones.
+//
 // Bootstrap confidence intervals of the mAP (opt-in, this project's own definition; the rule is stated in include/skghoi.h):
 //
 //   skg_eval_ap_boot_f64     : one wave per (class, 64 replicates) over the same sorted labels and the image id of every cell:
@@ -861,6 +867,127 @@ extern "C" int skg_hoi_pair_nms_u8(const float* boxes_h, const float* boxes_o, c
     if (!skg_aligned16(boxes_h) || !skg_aligned16(boxes_o)) return SKG_E_ALIGN;
     hipLaunchKernelGGL(skg_hoi_pair_nms_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, boxes_h, boxes_o, object,
                        pair_off, index, pred, scores, cell_off, order, measure, thresh, keep, status);
+    return skg_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ top-k per image
+// Score threshold and top-k over the scored cells of an image -- the last stage of a detector's post-processing (threshold,
+// NMS, detections per image).  Not part of the reference, which ranks every cell: opt-in, this project's own rule, stated in
+// include/skghoi.h (skg_hoi_topk_u8) -- parity unpinned.  One workgroup of 256 lanes per image, any number of cells.  A cell is
+// a candidate iff keep_in admits it, its score is a number and score >= thresh; its key is ev_orderable(score + 0.f), so the
+// keys order like the floats and -0 equals +0.  Sweep 1 counts the candidates; an image with at most k of them keeps them all.
+// Otherwise a radix select, most significant byte first: four sweeps over the image (in L2 after the first), each one an LDS
+// histogram of the byte over the candidates that share the prefix found so far, then the first wave scans the 256 bins from
+// the top and picks the bin of the k-th largest key.  That gives T, the key of the k-th candidate, and `above`, the candidates
+// over it.  The last sweep goes in arrival order in chunks of 256: key > T is kept, and of the cells with key == T the first
+// k - above -- an exclusive count of the equal flags over the chunk (ballot and popcount in a wave, the four wave totals through
+// LDS) on top of a base carried from chunk to chunk.  Every loop bound and every branch around a barrier is uniform and there
+// is no return in front of one; counters are 32 bits (cell_off is); the histogram takes integer LDS atomics only, whose sums
+// do not depend on their order, so the bytes are the same on every run.  LDS: 1 KB + a few words.
+__device__ __forceinline__ bool tk_candidate(const float* __restrict__ scores, const uint8_t* __restrict__ keep_in, uint32_t i,
+                                             float thresh, uint32_t& key) {
+    const float s = scores[i];
+    key = ev_orderable(s + 0.f);
+    return (keep_in == nullptr || keep_in[i] != 0) && s == s && s >= thresh;
+}
+
+__global__ __launch_bounds__(256) void skg_hoi_topk_kernel(const float* __restrict__ scores, const int32_t* __restrict__ cell_off,
+                                                           int k, float thresh, const uint8_t* __restrict__ keep_in,
+                                                           uint8_t* __restrict__ keep, int32_t* __restrict__ kept) {
+    __shared__ uint32_t hist[256];                           // bin b: the candidates whose byte is 255 - b (the largest first)
+    __shared__ uint32_t swave[4];
+    __shared__ uint32_t sel[2];                              // the chosen bin, the candidates in the bins in front of it
+    const int a = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int c0 = cell_off[a], c1 = cell_off[a + 1];
+    const uint32_t n = c1 > c0 ? (uint32_t)(c1 - c0) : 0u;   // the same in every lane, like everything derived from it
+    scores += c0; keep += c0;
+    if (keep_in) keep_in += c0;
+
+    // ---- sweep 1: the candidates of the image
+    uint32_t mine = 0;
+    for (uint32_t i = tid; i < n; i += 256) {
+        uint32_t key;
+        mine += tk_candidate(scores, keep_in, i, thresh, key) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if (lane == 0) swave[wv] = mine;
+    __syncthreads();
+    const uint32_t total = (swave[0] + swave[1]) + (swave[2] + swave[3]);
+    __syncthreads();                                         // swave is read: the last sweep writes it again
+
+    if (total <= (uint32_t)k) {                              // uniform: nothing to cut (an image without cells too)
+        for (uint32_t i = tid; i < n; i += 256) {
+            uint32_t key;
+            keep[i] = tk_candidate(scores, keep_in, i, thresh, key) ? (uint8_t)1 : (uint8_t)0;
+        }
+        if (tid == 0) kept[a] = (int32_t)total;
+    } else {
+        // ---- radix select: the key of the k-th largest candidate
+        uint32_t prefix = 0, known = 0;                      // its bytes found so far, their mask
+        uint32_t need = (uint32_t)k;                         // its rank among the candidates that share the prefix, from 1
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            for (uint32_t i = tid; i < n; i += 256) {
+                uint32_t key;
+                if (tk_candidate(scores, keep_in, i, thresh, key) && (key & known) == prefix)
+                    atomicAdd(&hist[255u - ((key >> shift) & 255u)], 1u);
+            }
+            __syncthreads();
+            if (wv == 0) {                                   // the first wave: four bins per lane, a scan over the lanes
+                const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+                const uint32_t sum = (h0 + h1) + (h2 + h3);
+                uint32_t incl = sum;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t up = __shfl_up(incl, off, 64);
+                    if (lane >= off) incl += up;
+                }
+                uint32_t front = incl - sum;
+                if (front < need && need <= incl) {          // exactly one lane: the bin of the need-th largest is one of its four
+                    uint32_t b = 4 * lane;
+                    if (need > front + h0) { front += h0; ++b;
+                        if (need > front + h1) { front += h1; ++b;
+                            if (need > front + h2) { front += h2; ++b; } } }
+                    sel[0] = b; sel[1] = front;
+                }
+            }
+            __syncthreads();
+            need -= sel[1];
+            prefix |= (255u - sel[0]) << shift;
+            known |= 255u << shift;
+        }
+        // prefix is T; k - need candidates lie above it, and the first `need` of the equal ones are wanted (need >= 1)
+
+        // ---- last sweep, in arrival order: key > T, and the first `need` cells with key == T
+        uint32_t base = 0;                                   // the equal cells in the chunks so far
+        for (uint32_t i0 = 0; i0 < n; i0 += 256) {           // uniform
+            const uint32_t i = i0 + tid;
+            uint32_t key = 0;
+            const bool cand = i < n && tk_candidate(scores, keep_in, i, thresh, key);
+            const bool equal = cand && key == prefix;
+            const unsigned long long b = __ballot(equal);
+            if (lane == 0) swave[wv] = (uint32_t)__popcll(b);
+            __syncthreads();
+            uint32_t pos = base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+            for (int w = 0; w < wv; ++w) pos += swave[w];
+            if (i < n) keep[i] = (cand && (key > prefix || (equal && pos < need))) ? (uint8_t)1 : (uint8_t)0;
+            base += (swave[0] + swave[1]) + (swave[2] + swave[3]);
+            __syncthreads();                                 // swave is read
+        }
+        if (tid == 0) kept[a] = k;
+    }
+}
+
+extern "C" int skg_hoi_topk_u8(const float* scores, const int32_t* cell_off, int n_images, int k, float score_thresh,
+                               const uint8_t* keep_in, uint8_t* keep, int32_t* kept, void* stream) {
+    if (n_images < 0 || k <= 0 || score_thresh != score_thresh) return SKG_E_ARG;
+    if (n_images == 0) return 0;
+    if (!scores || !cell_off || !keep || !kept) return SKG_E_ARG;
+    if ((((uintptr_t)scores) | ((uintptr_t)cell_off) | ((uintptr_t)kept)) & 3u) return SKG_E_ALIGN;
+    hipLaunchKernelGGL(skg_hoi_topk_kernel, dim3(n_images), dim3(256), 0, (hipStream_t)stream, scores, cell_off, k, score_thresh,
+                       keep_in, keep, kept);
     return skg_launch_status();
 }
 

@@ -17,6 +17,8 @@ The detections behind the head (hicodet/detections/eval_detections.py: object-de
 kept boxes, generate_gt_detections.py) are judged by DetectionEvaluator / DeviceDetectionEvaluator, which add pair coverage.
 pair_nms / pair_nms_keep suppress duplicate (human, object, class) triplets among the scored cells of an image before they reach
 an evaluator or an exporter (skg_hoi_pair_nms_u8) -- opt-in, the published PNMS idea restated, not the reference's.
+top_cells / top_cells_keep cut an image's cells at a score threshold and to its k best (skg_hoi_topk_u8); select_results runs
+score threshold -> pair NMS -> top-k with one host synchronisation -- opt-in, this project's own rule, not the reference's.
 The two HOI evaluators give confidence intervals of their means by a paired image-level bootstrap (`bootstrap=`;
 skg_eval_ap_boot_f64, bootstrap_weights / bootstrap_compare / format_bootstrap) -- opt-in, this project's own definition.
 
@@ -1426,8 +1428,9 @@ class DeviceDetectionEvaluator(_DetectionEvaluatorBase):
 # arrival order; the overlap of two cells is min(ih, io) ("min") or ih * io ("product", one fp32 multiply) of the IoUs of their
 # human and their object boxes in the association's fp32 arithmetic, a comparison with NaN false; a cell is suppressed iff an
 # earlier cell of its group THAT WAS KEPT has overlap > thresh, strictly; a cell with a NaN score is dropped and suppresses
-# nothing.  `thresh` has no default: there is no dataset in the tree to tune one on.  Top-k per image, merging over ranks and a
-# mask input of the association are not part of it.
+# nothing.  `thresh` has no default: there is no dataset in the tree to tune one on.  The score threshold and the top-k per
+# image are top_cells / select_results below (skg_hoi_topk_u8); merging over ranks and a mask input of the association are not
+# part of either.
 PAIR_NMS_MEASURES = ("min", "product")                           # SKG_PAIR_NMS_MIN, SKG_PAIR_NMS_PRODUCT
 _PER_CELL_KEYS = {"index": 0, "prediction": 0, "scores": 0, "labels": 0, "prior": 1}      # key -> the dimension of the cells
 
@@ -1568,11 +1571,150 @@ def pair_nms(outputs, thresh, measure="min"):
     counts = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, image, keep[:L].long())
     host = torch.cat([counts, status.long()]).cpu()              # the one synchronisation
     _pair_nms_raise(host[n:].tolist())
-    kept = host[:n].tolist()
-    # the kept cells in arrival order, their number known: nothing below waits for the device
+    return _select_kept(outputs, keep, host[:n].tolist(), cpi)
+
+
+def _select_kept(outputs, keep, kept, cpi):
+    """The result dicts at the cells flagged in keep (flat uint8 device tensor), kept = the flags' per-image sums as a host
+    list: the kept cells in arrival order, their number known -- nothing here waits for the device."""
+    L = int(sum(cpi))
     sel = torch.sort(keep[:L], descending=True, stable=True).indices[:int(sum(kept))].split(kept)
     first = np.concatenate([[0], np.cumsum(cpi)]).tolist()
     return [_pair_nms_filtered(o, s - first[a]) for a, (o, s) in enumerate(zip(outputs, sel))]
+
+
+# ----------------------------------------------------------------------------------------------- threshold and top-k per image
+# The last stage of a detector's post-processing (torchvision's postprocess_detections: score threshold, NMS,
+# detections_per_img; QPIC, CDN and GEN-VLKT report mAP at 100 triplets per image).  NOT the reference's, which ranks every
+# cell: opt-in, this project's own rule, stated in include/skghoi.h (skg_hoi_topk_u8) -- parity unpinned.  Per image, over the
+# cells in arrival order: a cell is a candidate iff its mask (when one is given) is not 0, its score is not NaN and score >=
+# score_thresh as float32 (-inf: no threshold, -inf passes; -0 >= +0); the candidates go score descending with -0 equal to +0,
+# equal scores in arrival order; the first k are kept (INT32_MAX: no cap).  No grouping, no LUT: V-COCO results alike.
+# The chain is score threshold -> pair NMS -> top-k, and the NMS kernel needs no mask input for it: inside a group a cell below
+# the threshold ranks behind every cell at or above it and only earlier kept cells suppress, so the NMS over all cells followed
+# by the threshold keeps exactly what the threshold followed by the NMS keeps -- select_results runs the NMS launch as it is and
+# hands its flags to the top-k launch as the mask.
+INT32_MAX = 2 ** 31 - 1
+
+
+def _top_args(k, score_thresh):
+    k = INT32_MAX if k is None else min(int(k), INT32_MAX)
+    if k < 1:
+        raise ValueError("k is %d: at least 1 (None for no cap)" % k)
+    thresh = float("-inf") if score_thresh is None else float(score_thresh)
+    if thresh != thresh:
+        raise ValueError("score_thresh is NaN")
+    return k, thresh
+
+
+def _top_masks(outputs, keep):
+    """The optional per-image masks of top_cells_keep checked against the images' cell counts -> a list of flat tensors."""
+    if keep is None:
+        return None
+    keep = [torch.as_tensor(m).reshape(-1) for m in keep]
+    if len(keep) != len(outputs):
+        raise ValueError("%d masks for %d images" % (len(keep), len(outputs)))
+    for a, (m, o) in enumerate(zip(keep, outputs)):
+        if m.numel() != o["scores"].numel():
+            raise ValueError("image %d: a mask of %d entries for %d cells" % (a, m.numel(), o["scores"].numel()))
+    return keep
+
+
+def _top_keep_host(scores, k, thresh, mask=None):
+    """The rule on one image's scores in plain torch on the host -> uint8 keep [n_cells]: the restatement the kernel is
+    checked against."""
+    sc = scores.reshape(-1).cpu().float()
+    cand = ~torch.isnan(sc) & (sc >= torch.tensor(thresh, dtype=torch.float32))
+    if mask is not None:
+        cand &= mask.reshape(-1).cpu() != 0
+    idx = torch.nonzero(cand).squeeze(1)
+    if idx.numel() > k:
+        idx = idx[torch.sort(sc[idx] + 0., descending=True, stable=True).indices[:k]]      # -0 like +0; arrival order on ties
+    keep = torch.zeros(sc.numel(), dtype=torch.uint8)
+    keep[idx] = 1
+    return keep
+
+
+def _top_device(outputs, k, thresh, mask, dev):
+    """One skg_hoi_topk_u8 launch on the current stream, no host synchronisation.  mask: None, or one flat uint8 device tensor
+    over the batch's cells.  Returns keep (uint8 device tensor, its first sum(cells) entries), kept (int32 device tensor
+    [n_images]) and the cells per image."""
+    from . import _capi
+    from .engine import _stream
+    n = len(outputs)
+    cpi = [int(o["scores"].numel()) for o in outputs]
+    L = int(sum(cpi))
+    scores = _pad_row(_cat_results(outputs, "scores", dev).float().reshape(-1).contiguous())
+    keep = torch.empty(max(L, 1), dtype=torch.uint8, device=dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    offs_d, (cell_off,) = _offset_table(dev, cpi)
+    _capi.check(_capi.lib().skg_hoi_topk_u8(
+        scores.data_ptr(), cell_off, n, k, thresh, None if mask is None else mask.data_ptr(), keep.data_ptr(), kept.data_ptr(),
+        _stream()), "skg_hoi_topk_u8")
+    return keep, kept, cpi
+
+
+def _flat_mask(masks, dev):
+    return None if masks is None else _pad_row(torch.cat([m.to(dev) for m in masks]).ne(0).to(torch.uint8).contiguous())
+
+
+def top_cells_keep(outputs, k=None, score_thresh=None, keep=None):
+    """The flags of the score threshold and the top-k per image over the head's result dicts of a batch (the rule above
+    INT32_MAX): per image a uint8 tensor [n_cells], 1 = kept.  k=None is no cap (INT32_MAX), score_thresh=None no threshold
+    (-inf); `keep` is an optional list of per-image uint8 masks, for instance pair_nms_keep's: a cell whose mask is 0 is no
+    candidate.  On the device: views of one device tensor, written by ONE skg_hoi_topk_u8 launch on the current stream, WITHOUT
+    a host synchronisation; any number of cells per image.  On CPU tensors: the host restatement.  k < 1, a NaN threshold or a
+    mask whose length is not its image's cell count raises ValueError.  An empty list gives []."""
+    k, thresh = _top_args(k, score_thresh)
+    masks = _top_masks(outputs, keep)
+    if len(outputs) == 0:
+        return []
+    dev = outputs[0]["scores"].device
+    if dev.type != "cuda":
+        return [_top_keep_host(o["scores"], k, thresh, None if masks is None else masks[a]) for a, o in enumerate(outputs)]
+    flags, _, cpi = _top_device(outputs, k, thresh, _flat_mask(masks, dev), dev)
+    return list(flags[:int(sum(cpi))].split(cpi))
+
+
+def top_cells(outputs, k=None, score_thresh=None):
+    """The head's result dicts of a batch cut to the cells at or above score_thresh and, of those, the k best of every image
+    (the rule above INT32_MAX): new dicts like pair_nms's -- the inputs are not touched, `index`, `prediction`, `scores`,
+    `labels` (when present) and `prior` (along dim 1) hold the kept cells in their arrival order, everything per pair is
+    passed through.  On the device: ONE synchronisation per call, the read of the per-image kept counts."""
+    return select_results(outputs, score_thresh=score_thresh, topk=k)
+
+
+def select_results(outputs, nms_thresh=None, measure="min", score_thresh=None, topk=None):
+    """Score threshold -> pair NMS -> top-k per image over the head's result dicts of a batch, torchvision's order: each stage
+    is off at None.  New dicts like pair_nms's; what comes out goes into the evaluators, hicodet_mat_cells and vcoco_results
+    like any result list, and `functools.partial(select_results, nms_thresh=0.7, topk=100)` is a `postprocess` of trainer.test.
+    With all four arguments None the cells come back unchanged except that cells with a NaN score are dropped.
+
+    On the device: the NMS launch (when nms_thresh is given) over all cells, its flags as the mask of one skg_hoi_topk_u8
+    launch -- the threshold commutes with the NMS, see above INT32_MAX -- and ONE synchronisation per call: one read that
+    carries the per-image kept counts and, when the NMS ran, its three status words (an image above a cap of the NMS kernel
+    raises SkgError as in pair_nms, a malformed `index` IndexError)."""
+    k, thresh = _top_args(topk, score_thresh)
+    if nms_thresh is not None:
+        nms_thresh, code = _pair_nms_args(nms_thresh, measure)
+    elif measure not in PAIR_NMS_MEASURES:
+        raise ValueError("unknown measure %r: one of %s" % (measure, ", ".join(PAIR_NMS_MEASURES)))
+    if len(outputs) == 0:
+        return []
+    dev = outputs[0]["scores"].device
+    n = len(outputs)
+    if dev.type != "cuda":
+        masks = [None] * n if nms_thresh is None else [_pair_nms_keep_host(o, nms_thresh, code) for o in outputs]
+        return [_pair_nms_filtered(o, torch.nonzero(_top_keep_host(o["scores"], k, thresh, m)).squeeze(1).to(dev))
+                for o, m in zip(outputs, masks)]
+    mask = status = None
+    if nms_thresh is not None:
+        mask, status, _, _ = _pair_nms_device(outputs, nms_thresh, code, dev)
+    keep, kept, cpi = _top_device(outputs, k, thresh, mask, dev)
+    host = (kept if status is None else torch.cat([kept, status])).cpu()      # the one synchronisation
+    if status is not None:
+        _pair_nms_raise(host[n:].tolist())
+    return _select_kept(outputs, keep, host[:n].tolist(), cpi)
 
 
 # ----------------------------------------------------------------------------------------------- exporters

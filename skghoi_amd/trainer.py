@@ -1555,7 +1555,10 @@ def test(net, test_loader, evaluator, device=None, lookahead=True, postprocess=N
 
     postprocess: a callable applied to the forward's result list before `evaluator.add` -- for example
     `functools.partial(evaluate.pair_nms, thresh=0.7)`, the pair NMS over the scored triplets (not the reference's: opt-in;
-    on the device it costs one host synchronisation per image, behind the look-ahead's launches).  None: the loop as it is."""
+    on the device it costs one host synchronisation per image, behind the look-ahead's launches), or
+    `functools.partial(evaluate.select_results, nms_thresh=0.7, topk=100)`: score threshold -> pair NMS -> top-k per image
+    (each stage optional; opt-in and not the reference's either; still one synchronisation per image, the read that carries
+    the kept counts and the NMS kernel's status).  None: the loop as it is."""
     mod = net.module if isinstance(net, nn.parallel.DistributedDataParallel) else net
     if device is None:
         p = next(mod.parameters(), None)
